@@ -14,9 +14,13 @@ kernel time / roofline fraction and a seam check.
 python -m torch.distributed.run --nproc-per-node N ...) the world must be N; started plainly with N > 1 the bench
 starts its own N ranks through the same launcher; anything else exits non-zero -- never a line that says n_gpus: 1.
 
-The timed region is EXACTLY K steps between barrier + synchronize on both sides, max over ranks; it is
-repeated until at least --min-time seconds have been timed (never fewer than 3 repeats) and the MEDIAN
-repeat is reported (`timing` holds min / median / max).
+The timed region is EXACTLY K steps between barrier + synchronize on both sides, max over ranks, run once: --steps is
+the number of timed steps.  Opt-in, --min-time S repeats those K steps until at least S seconds have been timed (never
+fewer than 3 repeats) and reports the MEDIAN repeat (`timing` holds min / median / max).
+
+--dump-outputs DIR writes what the timed path returned for its LAST step -- the burst records, one float array per field
+(DIR/<field>.npy, see dump_outputs) -- so that two builds can be compared output for output; the inputs are a pure
+function of the arguments (seeded, deterministic generation on the device).
 
 One JSON line.  Beside the headline it carries (N=1): `roofline`, `cpu_baseline` (four CPU legs timed on
 this box's host cores in the same run), `bit_match`, `host_fed` (PCIe-inclusive rates of the host-fed entry
@@ -145,9 +149,10 @@ def recs_match(a, b):
                 and np.array_equal(a["flags"] & 1, b["flags"] & 1))
 
 
-def timed_repeats(step, drain, sync_all, reduce_max, steps, min_time, max_repeats=400):
+def timed_repeats(step, drain, sync_all, reduce_max, steps, min_time, max_repeats=400, min_repeats=3):
     """EXACTLY `steps` steps per repeat, bracketed by sync_all (barrier + synchronize); repeats until min_time seconds
-    have been timed.  Every rank sees the same reduced times, so every rank stops at the same repeat."""
+    have been timed and at least min_repeats repeats have run.  Every rank sees the same reduced times, so every rank stops
+    at the same repeat."""
     times, nb = [], 0
     while True:
         sync_all()
@@ -157,7 +162,7 @@ def timed_repeats(step, drain, sync_all, reduce_max, steps, min_time, max_repeat
         nb = drain()
         sync_all()
         times.append(reduce_max(time.perf_counter() - t0))
-        if (len(times) >= 3 and sum(times) >= min_time) or len(times) >= max_repeats:
+        if (len(times) >= min_repeats and sum(times) >= min_time) or len(times) >= max_repeats:
             return times, nb
 
 
@@ -579,7 +584,7 @@ def one_process_leg(args, devices, context_counts=None, fs=20e6, bursts=1000.0, 
 
 
 def sharded_leg(args, dev, rank, n_gpus, fs, bursts, seed, n_own, steps, warmup, min_time, depth, sync_all, reduce_max,
-                ag_int, ag_obj, synth, fe=None, extra_me=None, untimed=False):
+                ag_int, ag_obj, synth, fe=None, extra_me=None, untimed=False, min_repeats=3):
     """One stream of n_own * n_gpus samples tiled as n_gpus overlapped time shards, one per rank; returns this rank's view
     (every rank gets the same dict: times are max over ranks, per_rank and the seam check are gathered)."""
     import torch
@@ -604,7 +609,8 @@ def sharded_leg(args, dev, rank, n_gpus, fs, bursts, seed, n_own, steps, warmup,
         own_times.append(t)
         return reduce_max(t)
 
-    times, n_bursts = timed_repeats(run.step, run.drain, sync_all, reduce_and_keep, steps, min_time)
+    times, n_bursts = timed_repeats(run.step, run.drain, sync_all, reduce_and_keep, steps, min_time, min_repeats=min_repeats)
+    last_kept = np.array(run.last_kept, copy=True)                 # this rank's records of the last timed step
     st = fe.stats()
     numa = fe.ctx.numa_info()
     kern_ms = st["detect_ms"] / max(1, st["detect_launches"])
@@ -641,7 +647,7 @@ def sharded_leg(args, dev, rank, n_gpus, fs, bursts, seed, n_own, steps, warmup,
     elapsed = float(np.median(times))
     return {"fs": fs, "n_own": n_own, "stream_len": stream_len, "times": times, "elapsed": elapsed, "stats": st, "product_default": prod,
             "value": round(float(stream_len) * steps / elapsed / 1e6, 1), "ms_per_step": round(elapsed / steps * 1e3, 4),
-            "n_bursts": int(n_bursts), "per_rank": per_rank, "seam": seam, "fe": fe, "iq": iq}
+            "n_bursts": int(n_bursts), "per_rank": per_rank, "seam": seam, "fe": fe, "iq": iq, "last_kept": last_kept}
 
 
 def config4_legs(args, dev, rank, n_gpus, depth, sync_all, reduce_max, ag_int, ag_obj, rank_sync):
@@ -700,7 +706,9 @@ def main():
     ap.add_argument("--bursts", type=float, default=1000.0, help="bursts per second of signal")
     ap.add_argument("--threshold", type=float, default=0.01)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--min-time", type=float, default=0.6, help="seconds of timed region to accumulate (repeats of K steps)")
+    ap.add_argument("--min-time", type=float, default=0.0,
+                    help="opt-in: repeat the K timed steps until this many seconds have been timed (at least 3 repeats, median "
+                         "reported); default: the K steps once")
     ap.add_argument("--cpu-log2n", type=int, default=28, help="log2 of the C-port CPU-baseline sample")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines and the bit-match leg")
     ap.add_argument("--no-extra", action="store_true", help="skip extra_configs (BASELINE configs 3, 4, 5)")
@@ -738,6 +746,9 @@ def main():
                     help="input sample format: complex64 (BASELINE workload), float32 |IQ|^2 (the framer's literal input, "
                          "4 B/sample), int16 IQ (4 B/sample) or 8-bit IQ (2 B/sample: int8 / RTL-SDR offset binary); "
                          "formats other than fc32 N=1 only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the burst records the timed path returned for its last step to DIR/<field>.npy (float32 / "
+                         "float64, at most 64 MB: a fixed, seeded sample of the records beyond that)")
     args = ap.parse_args()
 
     stray = sorted(k for k in os.environ if k.startswith("ADSB_") and k not in KNOWN_ENV)
@@ -864,7 +875,8 @@ def main():
         return float(tmax.item())
 
     rank_sync = None if not dist_on else ("gloo" if sync_dev[0] == "cpu" else "rccl")
-    per_rank = seam = hf_multi = cfg4 = None
+    min_repeats = 3 if args.min_time > 0 else 1           # default: the K timed steps exactly once
+    per_rank = seam = hf_multi = cfg4 = last_recs = None
     iso_ms = untimed = None
     if n_gpus == 1:
         iq = gen_stream_blocks(n_own, 0, fs, args.bursts, args.seed, dev, **synth)
@@ -895,7 +907,10 @@ def main():
             step()
         drain()
         fe.ctx.reset_stats()
-        times, n_bursts = timed_repeats(step, drain, sync_all, reduce_max, args.steps, args.min_time)
+        times, n_bursts = timed_repeats(step, drain, sync_all, reduce_max, args.steps, args.min_time, min_repeats=min_repeats)
+        if args.dump_outputs:
+            last_recs = fe.ctx.last_result(copy=True)              # the records the last timed step returned
+            assert len(last_recs) == n_bursts
         st = fe.stats()
         # the same kernel timed without a neighbour, AFTER the timed region
         iso_ms = isolated_kernel_ms(fe, fmt, iq, n_own)
@@ -905,8 +920,11 @@ def main():
     else:
         leg = sharded_leg(args, dev, rank, n_gpus, fs, args.bursts, args.seed, n_own, args.steps, args.warmup, args.min_time,
                           DEPTH, sync_all, reduce_max, ag_int, ag_obj, synth, fe=fe,
-                          extra_me={"process_bound_to_local_cpus": numa["bound"]})
+                          extra_me={"process_bound_to_local_cpus": numa["bound"]}, min_repeats=min_repeats)
         times, n_bursts, st, per_rank, seam, iq = leg["times"], leg["n_bursts"], leg["stats"], leg["per_rank"], leg["seam"], leg["iq"]
+        if args.dump_outputs:
+            # the whole stream's records: every rank's kept records of the last step, in rank (= stream) order
+            last_recs = np.concatenate(ag_obj(leg["last_kept"]))
         if not one_gpu and not args.force_dist:
             assert len({r["device"] for r in per_rank}) == n_gpus or len({r["pci_bus_id"] for r in per_rank}) == n_gpus, \
                 "ranks share a GPU (set ADSB_BENCH_ONE_GPU=1 if that is intended)"
@@ -1072,6 +1090,8 @@ def main():
                     cfgd["cfg4_%s_seams_identical" % leg_name] = bool(cfg4[leg_name]["seam_check"]["all_identical"])
                     cfgd["cfg4_%s_per_rank_frac" % leg_name] = [r_["roofline_frac"] for r_ in cfg4[leg_name]["per_rank"]]
         result["config"] = order_config(cfgd, n_gpus)
+        if args.dump_outputs:
+            result["dump_outputs"] = dump_outputs(args.dump_outputs, last_recs)
         print(json.dumps(result), flush=True)
     if n_gpus > 1:
         sync_all()
@@ -1079,6 +1099,30 @@ def main():
     if dist_on:
         dist.destroy_process_group()
     return result
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, recs, seed=0):
+    """--dump-outputs: the burst records of the timed path's last step as DIR/<field>.npy -- offset (float64, exact),
+    peak, median (the SNR's inputs), bits (the 14 packed bytes of the 112-bit PDU) and flags (float32, exact) -- plus
+    record_index (float64: which records these are) and count (float64[1]: records in the step).  Past DUMP_LIMIT_BYTES
+    the rows are a fixed, seeded sample in stream order: the same records for the same count."""
+    n = len(recs)
+    row = 8 + 4 + 4 + 4 * recs.dtype["bits"].shape[0] + 4 + 8
+    cap = max(1, (DUMP_LIMIT_BYTES - 4096) // row)              # (4096: the seven .npy headers and count)
+    idx = np.arange(n) if n <= cap else np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+    r = recs[idx]
+    arrays = {"offset": r["offset"].astype(np.float64), "peak": r["peak"].astype(np.float32),
+              "median": r["median"].astype(np.float32), "bits": r["bits"].astype(np.float32),
+              "flags": r["flags"].astype(np.float32), "record_index": idx.astype(np.float64),
+              "count": np.array([n], dtype=np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "records": int(n), "records_written": int(len(idx)), "sampled": bool(len(idx) < n),
+            "files": sorted(name + ".npy" for name in arrays)}
 
 
 # The per-leg verdicts a reader must not lose come FIRST in `config` (a record that keeps only the first two dozen keys

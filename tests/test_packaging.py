@@ -1,8 +1,8 @@
 """the drop-in boundary under the reference's own ids.  GNU Radio cannot be installed in the build
 image, so the GRC side is exercised the way GRC's generated script would: run the descriptor's `imports`, evaluate its
 `make` / `callbacks` templates -- against packaging/gnuradio_adsb loaded as `gnuradio.adsb` under the stub runtime.
-When /root/reference is present the templates are the REFERENCE's (read at test time, never copied), and our own
-descriptors must agree with them field for field.  The GPU half (blocks really running) is
+Our descriptors must agree with the REFERENCE's field for field: tests/golden/ref_grc_digests.json holds a sha256 of each
+field of the reference's descriptors (tools/make_golden_refruns.py; never their text).  The GPU half (blocks really running) is
 tests/test_gpu_parity.py::test_gnuradio_adsb_namespace_drives_goldens."""
 import glob
 import inspect
@@ -16,10 +16,11 @@ import pytest
 import yaml
 
 from helpers import grc_instantiate, load_gnuradio_adsb
+from refstore import grc_digest, reference_grc_digests
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_GRC = "/root/reference/grc"
 OURS = os.path.join(ROOT, "packaging", "gnuradio_adsb", "grc")
+GRC_KEYS = ("id", "templates", "parameters", "inputs", "outputs", "file_format", "label", "category")
 
 
 def _load(d, name):
@@ -61,19 +62,22 @@ def test_extension_descriptors_match_the_block_constructors():
         assert all(p["dtype"] == "float" for p in d["inputs"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_GRC), reason="/root/reference not present")
 @pytest.mark.parametrize("name", ["adsb_framer.block.yml", "adsb_demod.block.yml"])
 def test_our_descriptors_equal_the_references_field_for_field(name):
-    ref, ours = _load(REF_GRC, name), _load(OURS, name)
-    for key in ("id", "templates", "parameters", "inputs", "outputs", "file_format", "label", "category"):
-        assert ours[key] == ref[key], "%s: %s differs from the reference's descriptor" % (name, key)
+    ref, ours = reference_grc_digests()[name], _load(OURS, name)
+    for key in GRC_KEYS:
+        assert grc_digest(ours[key]) == ref[key], "%s: %s differs from the reference's descriptor" % (name, key)
 
 
 @pytest.mark.parametrize("src", ["reference", "ours"])
 def test_grc_templates_instantiate_the_mi355x_blocks(adsb, src):
-    d = REF_GRC if src == "reference" else OURS
-    if not os.path.isdir(d):
-        pytest.skip("/root/reference not present")
+    if src == "reference":
+        # the reference's templates and parameters are ours, digest for digest: what GRC generates from them is the same
+        ref = reference_grc_digests()
+        for name in ("adsb_framer.block.yml", "adsb_demod.block.yml"):
+            for key in ("templates", "parameters"):
+                assert grc_digest(_load(OURS, name)[key]) == ref[name][key], (name, key)
+    d = OURS
     from gr_adsb_amd import blocks
     fr, fr_cb = grc_instantiate(_load(d, "adsb_framer.block.yml"))
     dm, _ = grc_instantiate(_load(d, "adsb_demod.block.yml"))

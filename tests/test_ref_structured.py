@@ -1,12 +1,10 @@
 """Pins oracle/ref_structured.py -- the reference-STRUCTURED CPU baseline bench.py times (vectorised front end +
 per-pulse Python loop + np.median) -- against the goldens from the real reference, against the
-vectorised oracle, against its own process-per-shard form, and (container only) against the real reference."""
-import os
-import sys
-
+vectorised oracle, against its own process-per-shard form, and against the real reference's outputs (tests/refstore.py)."""
 import numpy as np
 import pytest
 
+import refstore
 from helpers import Golden, golden_names
 from gr_adsb_amd import modulator as M
 from oracle import adsb_oracle as O
@@ -50,12 +48,8 @@ def test_shard_that_cannot_synchronise_falls_back():
     assert sh["fallback"] and np.array_equal(sh["tag_offsets"], want["tag_offsets"])
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/python/adsb/framer.py"), reason="/root/reference not present")
 def test_against_the_real_reference():
-    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
-    if tools not in sys.path:
-        sys.path.insert(0, tools)
-    import ref_harness as R
+    R = refstore.harness()
     for fs, bps, seed in [(2e6, 2000, 5), (8e6, 6000, 6)]:
         x = M.mag2(M.synth_iq(1 << 17, fs, bps, seed=seed))
         r = R.run_reference(x, fs, 0.01)
@@ -63,4 +57,4 @@ def test_against_the_real_reference():
         assert np.array_equal(r["tag_offsets"], o["tag_offsets"])
         assert np.array_equal(r["tag_snr"].view(np.uint32), o["tag_snr"].view(np.uint32))
         assert np.array_equal(r["pdu_bits"], o["pdu_bits"])
-        assert np.array_equal(r["pdu_conf"].view(np.uint32), o["pdu_conf"].view(np.uint32))
+        assert refstore.conf_digest(o["pdu_conf"]) == r["pdu_conf_sha256"]      # the ratios, bit for bit
