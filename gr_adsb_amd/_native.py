@@ -22,6 +22,7 @@ FLAG_SINGLE_STREAM = 8    # profiling aid: the sparse tail of a pass on the comp
 FLAG_FRAMER_SLICES = 32   # adsb_framer_work also returns the 112 bits of tags whose burst ends inside the call's input
 FLAG_NO_NUMA_BINDING = 64 # host side not placed on the GPU's NUMA node (default: page-locked buffers and copy threads are)
 FLAG_LOW_LATENCY = 16     # the tail of a pass runs beside the next pass's k_detect: results a pass earlier, 1-2 % less throughput
+FLAG_FEC_CONSERVATIVE = 128  # opt-in: the decoder's "Conservative" 1-2-bit burst repair on the device (decoder.py:738-780)
 ABI_VERSION = 5
 # input sample formats (include/adsb_hip.h ADSB_FMT_*): numpy dtype of the flat host array, items per sample
 FMT_FC32, FMT_MAG2, FMT_SC16, FMT_SC8, FMT_CU8 = 0, 1, 2, 3, 4
@@ -35,6 +36,8 @@ BURST_LONG = 64
 BURST_KNOWN_DF = 128
 BURST_DF_SHIFT = 8
 BURST_LONG_HINT = 0x2000 # records of a long-aware context: this burst holds the gate for 119*sps
+BURST_FEC_FIXED = 0x4000 # FLAG_FEC_CONSERVATIVE: bits repaired, the pre-filter bits are the repaired reply's
+BURST_FEC_DF = 0x8000    # FLAG_FEC_CONSERVATIVE: the decoder's repair would change the DF; bits left raw
 MAX_IN_FLIGHT = 3
 
 EXPORTS = [
@@ -44,7 +47,7 @@ EXPORTS = [
     "adsb_set_iq16_scale", "adsb_process_iq16", "adsb_process_iq16_device",
     "adsb_set_format_scale", "adsb_process_format", "adsb_process_format_device", "adsb_submit_format_device",
     "adsb_submit_format_host", "adsb_last_confidence",
-    "adsb_framer_work", "adsb_framer_work_passthrough", "adsb_demod_work", "adsb_shard_bounds", "adsb_process_sharded_device", "adsb_shard_device", "adsb_shard_host", "adsb_shard_fixup", "adsb_stitch", "adsb_snr_db", "adsb_mode_s_syndrome", "adsb_plan_chunks", "adsb_get_stats",
+    "adsb_framer_work", "adsb_framer_work_passthrough", "adsb_demod_work", "adsb_shard_bounds", "adsb_process_sharded_device", "adsb_shard_device", "adsb_shard_host", "adsb_shard_fixup", "adsb_stitch", "adsb_snr_db", "adsb_mode_s_syndrome", "adsb_mode_s_fec", "adsb_plan_chunks", "adsb_get_stats",
     "adsb_process_sharded_multi", "adsb_device_alloc", "adsb_device_free", "adsb_device_upload", "adsb_clear_pending_events",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
 ]
@@ -143,6 +146,8 @@ def load():
     lib.adsb_snr_db.restype = f32
     lib.adsb_mode_s_syndrome.argtypes = [vp, c.POINTER(i32), c.POINTER(i32)]
     lib.adsb_mode_s_syndrome.restype = c.c_uint32
+    lib.adsb_mode_s_fec.argtypes = [vp, vp, c.POINTER(i32), c.POINTER(i32)]
+    lib.adsb_mode_s_fec.restype = c.c_uint32
     lib.adsb_plan_chunks.argtypes = [i64, i64, c.POINTER(i64), c.POINTER(i64)]
     lib.adsb_plan_chunks.restype = c.c_int32
     lib.adsb_get_stats.argtypes = [vp, c.POINTER(Stats)]
@@ -400,7 +405,7 @@ class Context:
                                            ctypes.c_void_p(tags.ctypes.data), nt, ctypes.c_void_p(bits.ctypes.data),
                                            ctypes.c_void_p(ok.ctypes.data),
                                            ctypes.c_void_p(ratio.ctypes.data) if want_ratio else None))
-        self.last_demod_flags = ok        # ok[t] = BURST_DEMOD | parity pre-filter bits (0 = dropped)
+        self.last_demod_flags = ok        # ok[t] = BURST_DEMOD | parity pre-filter bits (0 = dropped); see demod_flags
         return bits, ok.astype(bool), ratio
 
     def process_sharded_device(self, fmt, dev_ptr, n, shards, abs_offset=0, out=None):
@@ -663,6 +668,25 @@ def mode_s_syndrome(bits14):
     df, nb = ctypes.c_int32(), ctypes.c_int32()
     syn = load().adsb_mode_s_syndrome(b.ctypes.data_as(ctypes.c_void_p), ctypes.byref(df), ctypes.byref(nb))
     return int(syn), df.value, nb.value
+
+
+def mode_s_fec(bits14):
+    """adsb_mode_s_fec: (flags, repaired bits14, first_bit, nflip) of one 14-byte payload -- the rule FLAG_FEC_CONSERVATIVE
+    applies on the device (flags: pre-filter bits of the result | BURST_FEC_FIXED or BURST_FEC_DF)."""
+    b = np.ascontiguousarray(bits14, dtype=np.uint8)
+    assert b.size == 14
+    out = np.zeros(14, dtype=np.uint8)
+    first, nflip = ctypes.c_int32(), ctypes.c_int32()
+    fl = load().adsb_mode_s_fec(b.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(first),
+                                ctypes.byref(nflip))
+    return int(fl), out, first.value, nflip.value
+
+
+def demod_flags(ok):
+    """adsb_demod_work's ok[] bytes -> the record flag layout (uint16): bits 0, 5-7 are the same, the FEC verdicts of an
+    FLAG_FEC_CONSERVATIVE context travel in bits 1 / 2 (BURST_FEC_FIXED >> 13 / BURST_FEC_DF >> 13)."""
+    ok = np.asarray(ok, dtype=np.uint16)
+    return (ok & 0xE1) | ((ok & 6) << 13)
 
 
 def unpack_bits(bits14):

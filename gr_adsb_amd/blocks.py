@@ -240,6 +240,7 @@ class framer(gr.sync_block):
             self.set_output_multiple(int(min_chunk))
         # the framer's device pass also slices the bits of every burst that ends inside its chunk: a demod paired with
         # this block (demod(fs, framer=this)) publishes them without a second upload / device pass of the same samples
+        self._ctx_device = device
         self._ctx = _native.Context(fs, threshold, device=device,
                                     flags=(_native.FLAG_LONG_AWARE_GATE if self.long_aware else 0) |
                                           (0 if self.improved else _native.FLAG_FRAMER_SLICES))
@@ -248,6 +249,17 @@ class framer(gr.sync_block):
         self._slices = _SliceStore()      # bits of the bursts this block's pass already sliced, for a paired demod
         self._paired = False              # set by demod(fs, framer=self): only then are the slices kept
         self._pmt_key, self._pmt_src = pmt.to_pmt("burst"), pmt.to_pmt("framer")
+
+    def _enable_fec(self):
+        """demod(fs, framer=self, error_corr="Conservative"): this block's device pass also repairs the bits it slices
+        (FLAG_FEC_CONSERVATIVE).  A context's flags are fixed at creation, so the (still unused) context is re-created."""
+        if self.nitems_written(0):
+            raise RuntimeError("a framer can only be paired with a Conservative demod before its first work() call")
+        flags = _native.FLAG_FEC_CONSERVATIVE | (_native.FLAG_LONG_AWARE_GATE if self.long_aware else 0) | \
+            (0 if self.improved else _native.FLAG_FRAMER_SLICES)
+        device = self._ctx_device
+        self._ctx.close()
+        self._ctx = _native.Context(self.fs, self.threshold, device=device, flags=flags)
 
     def set_threshold(self, threshold):
         self.threshold = threshold            # read once per work(), like the reference (framer.py:84)
@@ -358,20 +370,25 @@ def _passthrough(ctx, out0, src):
 
 _DF_WEIGHTS = np.array([16, 8, 4, 2, 1])
 _PI_FORMATS = (11, 17, 18, 19)
+_ERROR_CORR = ("None", "Conservative", "Brute Force")      # decoder(error_corr=...) (grc/adsb_decoder.block.yml)
 
 
-def _prefilter_pass(flags, df):
+def _prefilter_pass(flags, df, fec=False):
     """A PDU can still pass decoder.check_parity(): known DF, and for the parity/interrogator formats a zero
-    syndrome (address/parity formats need the decoder's aircraft table and always go through)."""
+    syndrome (address/parity formats need the decoder's aircraft table and always go through).  fec: the bits were
+    published after the device's Conservative repair -- a repaired PDU has a zero syndrome, and one whose repair would
+    change its DF (BURST_FEC_DF, bits raw) is kept for the decoder's own repair."""
     if not flags & _native.BURST_KNOWN_DF:
         return False
-    return bool(flags & _native.BURST_PARITY_OK) if df in _PI_FORMATS else True
+    if df in _PI_FORMATS:
+        return bool(flags & _native.BURST_PARITY_OK) or (fec and bool(flags & _native.BURST_FEC_DF))
+    return True
 
 
 class demod(gr.sync_block):
     """PPM bit slicer / PDU publisher (reference python/adsb/demod.py:31-136)."""
 
-    def __init__(self, fs, device=0, parity_filter=False, improved=False, framer=None, min_chunk=0):
+    def __init__(self, fs, device=0, parity_filter=False, improved=False, framer=None, min_chunk=0, error_corr="None"):
         """framer (extension, default None = an independent block, like the reference's): the framer block of the same
         flowgraph whose output feeds this block.  That framer's device pass has already sliced the bits of every burst
         that ends inside its chunk; a paired demod publishes those PDUs straight from the framer's records -- the same
@@ -388,8 +405,20 @@ class demod(gr.sync_block):
 
         parity_filter (extension, default off = the reference's behaviour: every PDU is published): when
         True, PDUs the decoder's check_parity() would reject outright -- unknown DF, or DF 11/17/18/19 with
-        a non-zero syndrome (decoder.py:560-688) -- are counted in `self.filtered` and not published.  Only
-        for decoders run with error_corr="None": a dropped PDU can no longer be repaired by their FEC."""
+        a non-zero syndrome (decoder.py:560-688) -- are counted in `self.filtered` and not published.  Pair it with the
+        error_corr of the decoder downstream: with "None" a PDU its FEC could have repaired would be lost.
+
+        error_corr (extension, named after the decoder's parameter; default "None" = the reference demod): "Conservative"
+        applies the decoder's Conservative error correction (decoder.py:738-780) on the device before publishing: a
+        DF 11/17/18/19 PDU with a 1-bit or 2-adjacent-bit error is published repaired (counted in `self.corrected`), one
+        whose repair would change its DF is published raw, for the decoder to repair.  With parity_filter=True exactly
+        the PDUs a Conservative decoder can accept are kept.  "Brute Force" behaves as "None", like the decoder, whose
+        branch only logs (decoder.py:772-776)."""
+        if error_corr not in _ERROR_CORR:
+            raise ValueError("error_corr must be one of %s, not %r" % (", ".join(_ERROR_CORR), error_corr))
+        self.error_corr = error_corr
+        self._fec = error_corr == "Conservative"
+        self.corrected = 0
         gr.sync_block.__init__(self, name="demod", in_sig=[np.float32], out_sig=[np.float32])
         self.parity_filter = bool(parity_filter)
         self.filtered = 0
@@ -411,6 +440,8 @@ class demod(gr.sync_block):
         if framer is not None and (framer.improved or self.improved):
             raise ValueError("framer= pairing is for the reference-exact blocks (improved=False on both)")
         if framer is not None:
+            if self._fec:
+                framer._enable_fec()
             framer._paired = True
         self.device_calls = 0             # work() calls that went to the device (paired mode: only the fall-back)
         self.want_confidence = framer is None  # demod.py:101 computes it on every burst
@@ -419,7 +450,7 @@ class demod(gr.sync_block):
             self.set_output_multiple(int(min_chunk))
         self._pmt_port, self._pmt_key = pmt.to_pmt("demodulated"), pmt.to_pmt("burst")
         self.message_port_register_out(self._pmt_port)
-        self._ctx = _native.Context(fs, 0.0, device=device)
+        self._ctx = _native.Context(fs, 0.0, device=device, flags=_native.FLAG_FEC_CONSERVATIVE if self._fec else 0)
 
     def work(self, input_items, output_items):
         in0 = input_items[0]
@@ -462,12 +493,14 @@ class demod(gr.sync_block):
                     offs = np.array(offl, dtype=np.int64)
                 # demod.py:79 indexes with nitems_written(0); equal to nitems_read(0) for this sync block
                 bits, ok, ratio = self._ctx.demod_work(in0, self.nitems_written(0), offs, want_ratio=self.want_confidence)
-                pf = self._ctx.last_demod_flags
+                pf = _native.demod_flags(self._ctx.last_demod_flags)
                 self.device_calls += 1
             # one PDU per burst is the only per-burst work the API forces (demod.py:104-110)
             ts0, fs, port, pub = self.start_timestamp, self.fs, self._pmt_port, self.message_port_pub
             to_pmt, to_python, cons = pmt.to_pmt, pmt.to_python, pmt.cons
             if ratio is None and not self.parity_filter and bool(ok.all()):
+                if self._fec:
+                    self.corrected += int(np.count_nonzero(np.asarray(pf) & _native.BURST_FEC_FIXED))
                 for i, tag in enumerate(tags):
                     pub(port, cons(to_pmt({"timestamp": ts0 + tag.offset / fs, "snr": to_python(tag.value)[1]}), to_pmt(bits[i])))
                 self.bits = bits[-1]                  # demod.py:95 keeps the last burst's bits on the block
@@ -479,9 +512,11 @@ class demod(gr.sync_block):
                     if not ok[i]:
                         self.straddled_packet = 1     # demod.py:130-133: dropped
                         continue
-                    if self.parity_filter and not _prefilter_pass(int(pf[i]), int(bits[i][:5] @ _DF_WEIGHTS)):
+                    if self.parity_filter and not _prefilter_pass(int(pf[i]), int(bits[i][:5] @ _DF_WEIGHTS), self._fec):
                         self.filtered += 1
                         continue
+                    if self._fec and int(pf[i]) & _native.BURST_FEC_FIXED:
+                        self.corrected += 1
                     self.bits = bits[i]
                     if ratio is not None:
                         self.bit_confidence = conf[i]                   # as it stands when this PDU is published
@@ -502,14 +537,16 @@ class demod(gr.sync_block):
                 buf, pos = in0, nread
             offs = np.array([o for o, _ in pend], dtype=np.int64)
             bits, ok, ratio = self._ctx.demod_work(buf, pos, offs, want_ratio=self.want_confidence)
-            pf = self._ctx.last_demod_flags
+            pf = _native.demod_flags(self._ctx.last_demod_flags)
             for i, (off, value) in enumerate(pend):
                 if not ok[i]:
                     self._pending.append((off, value))    # completed by a later call
                     continue
-                if self.parity_filter and not _prefilter_pass(int(pf[i]), int(bits[i][:5] @ _DF_WEIGHTS)):
+                if self.parity_filter and not _prefilter_pass(int(pf[i]), int(bits[i][:5] @ _DF_WEIGHTS), self._fec):
                     self.filtered += 1
                     continue
+                if self._fec and int(pf[i]) & _native.BURST_FEC_FIXED:
+                    self.corrected += 1
                 self.bits = bits[i].copy()
                 if ratio is not None:
                     with np.errstate(all="ignore"):

@@ -79,6 +79,9 @@ enum RecFlags : unsigned {
   kKnownDf = 128u,   // DF is one the reference decoder checks parity for (0,4,5,11,16-21,24)
   kDfShift = 8u,     // bits 8..12: the downlink format (first five bits, MSB first)
   kRecLongHint = 0x2000u,   // records of a long-aware context: this burst holds the gate for 119*sps, not 63*sps
+  // opt-in Conservative error correction (k_fec; decoder.py:738-780), kDemod only:
+  kFecFixed = 0x4000u,      // a 1-bit / 2-adjacent-bit error was repaired: bits and parity bits are those of the repaired reply
+  kFecDf = 0x8000u,         // the decoder's repair would change the downlink format: bits left raw
 };
 
 // x^j mod G, j = 0..111, G = x^24 + 0xFFF409 (decoder.py:268-269: the 25 coefficients spell 0x1FFF409).  The
@@ -556,6 +559,87 @@ __device__ __forceinline__ unsigned parity_flags_of(unsigned long long w2, unsig
     if ((crc ^ last) == 0u) flags |= kParityOk;
   }
   return flags;
+}
+// the same syndrome, crc(bits[0:L-24]) ^ bits[L-24:L] for the first nb = L/8 bytes, for k_fec.  (parity_flags_of keeps its own
+// loop: built on this function, k_compact and the one-workgroup tails compiled to different code -- same resources, not measured)
+__device__ __forceinline__ unsigned syndrome_of(unsigned long long w2, unsigned long long w3, int nb) {
+  static constexpr Crc8Tab tab = make_crc8_tab();
+  unsigned crc = 0u, last = 0u;
+  for (int k = 0; k < nb; ++k) {
+    const unsigned byte = (unsigned)((k < 8 ? (w2 >> (8 * k)) : (w3 >> (8 * (k - 8)))) & 0xFFu);
+    if (k < nb - 3) crc = ((crc << 8) ^ tab.t[((crc >> 16) ^ byte) & 0xFFu]) & 0xFFFFFFu;
+    else last = (last << 8) | byte;
+  }
+  return crc ^ last;
+}
+
+// Conservative error correction (opt-in; decoder.py:270-273,304-323 build the table, :738-780 apply it).  The decoder's table
+// holds every 1-bit and 2-adjacent-bit error pattern e of a 56- and of a 112-bit reply (111 / 223 patterns), keyed by
+// compute_crc_2(bits[0:L]) = the message polynomial mod x*G, 25 bits.  x*G has no constant term, so that key is the pair
+// (syndrome S = message mod G, last message bit): a reply matches e iff S(bits) == S(e) and bits[L-1] == e[L-1] -- a reply
+// whose last bit differs from e's is never repaired, a quirk kept as it is.  A pattern is named by j = L-1-(its first bit) and
+// its length: S = x^j or x^(j-1)*(x+1) mod G, the same for both lengths (the 56-bit table is the patterns with j < 56), and
+// e[L-1] = 1 exactly for the single bit j = 0 and the pair j = 1.  The 223 syndromes are distinct (static_assert below):
+// sorted, one lookup is a binary search.
+constexpr int kFecPatterns = 223;
+struct FecTab { unsigned key[kFecPatterns]; unsigned char code[kFecPatterns]; };   // code = j, + 128 for a pair
+constexpr FecTab make_fec_tab() {
+  const CrcTab r = make_crc_tab();
+  FecTab t{};
+  int n = 0;
+  for (int j = 0; j < 112; ++j) { t.key[n] = r.r[j]; t.code[n++] = (unsigned char)j; }
+  for (int j = 1; j < 112; ++j) { t.key[n] = r.r[j] ^ r.r[j - 1]; t.code[n++] = (unsigned char)(j | 128); }
+  for (int i = 1; i < n; ++i)
+    for (int k = i; k > 0 && t.key[k - 1] > t.key[k]; --k) {
+      const unsigned kk = t.key[k]; t.key[k] = t.key[k - 1]; t.key[k - 1] = kk;
+      const unsigned char cc = t.code[k]; t.code[k] = t.code[k - 1]; t.code[k - 1] = cc;
+    }
+  return t;
+}
+constexpr bool fec_tab_distinct() {
+  const FecTab t = make_fec_tab();
+  for (int i = 1; i < kFecPatterns; ++i) if (t.key[i - 1] >= t.key[i]) return false;
+  return t.key[0] != 0u;
+}
+static_assert(fec_tab_distinct(), "decoder.py:314-316: the table's syndromes are distinct and non-zero");
+
+// correct_burst_errors() for one record: w2 / w3 = its words (bits, flags << 48).  Acts on kDemod records of DF 11/17/18/19
+// whose syndrome is non-zero (the address/parity formats need the consumer's aircraft table: left alone, as by the
+// pre-filter).  A hit whose repaired DF is again one of those, with the same length: bits repaired, parity bits recomputed,
+// + kFecFixed.  A hit that would change the format: bits left raw, + kFecDf (a "Conservative" decoder repairs those itself,
+// decoder.py:342-347).  Returns whether w2 / w3 changed.
+__device__ __forceinline__ bool fec_record(unsigned long long& w2, unsigned long long& w3) {
+  static constexpr FecTab tab = make_fec_tab();
+  const unsigned fl = (unsigned)(w3 >> 48);
+  const unsigned dfb = 1u << ((unsigned)(w2 & 0xFFu) >> 3);
+  if (!(fl & kDemod) || (fl & kParityOk) || !(dfb & kDfPiSet)) return false;
+  const bool lng = (dfb & kDfLongSet) != 0;
+  const int L = lng ? 112 : 56;
+  const unsigned syn = syndrome_of(w2, w3, L / 8);
+  int lo = 0, hi = kFecPatterns;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (tab.key[mid] < syn) lo = mid + 1; else hi = mid;
+  }
+  if (lo == kFecPatterns || tab.key[lo] != syn) return false;
+  const int j = tab.code[lo] & 127, nflip = tab.code[lo] >> 7 ? 2 : 1;
+  if (j >= L) return false;
+  const unsigned last = (unsigned)(lng ? (w3 >> 40) : (w2 >> 48)) & 1u;          // bits[L-1]: bit 0 of byte L/8-1
+  if (last != (j == nflip - 1 ? 1u : 0u)) return false;
+  unsigned long long a = w2, b = w3 & 0xFFFFFFFFFFFFull;
+  for (int i = L - 1 - j; i < L - 1 - j + nflip; ++i) {
+    const unsigned long long m = 1ull << (8 * ((i >> 3) & 7) + 7 - (i & 7));
+    if (i < 64) a ^= m; else b ^= m;
+  }
+  const unsigned dfb2 = 1u << ((unsigned)(a & 0xFFu) >> 3);
+  if ((dfb2 & kDfPiSet) && ((dfb2 & kDfLongSet) != 0) == lng) {
+    const unsigned keep = fl & ~(kParityOk | kLongFmt | kKnownDf | (31u << kDfShift));
+    w2 = a;
+    w3 = b | ((unsigned long long)(keep | parity_flags_of(a, b) | kFecFixed) << 48);
+  } else {
+    w3 |= (unsigned long long)kFecDf << 48;
+  }
+  return true;
 }
 
 // Record of a centre whose samples come from global memory (k_longrun: pulses longer than the LDS window).
@@ -2024,6 +2108,38 @@ __global__ void __launch_bounds__(kThreads) k_confidence(DetectArgs a, const Rec
       const float y1 = xg<MODE>(a.data, a.n, s1, a.scale), y0 = xg<MODE>(a.data, a.n, s1 + half, a.scale);
       ratio[(long long)t * 112 + 64 + lane] = __fdiv_rn(y1, y0);
     }
+  }
+}
+
+// ---- k_fec: opt-in Conservative error correction of a pass's delivered records (ADSB_FLAG_FEC_CONSERVATIVE) ---------------
+// One thread per record, in place, queued behind the pass's compaction: out[0 .. sum->n_kept) are the records; host_out: a
+// mid-size pass also stored its first host_cap records in pinned host memory (adsb_hip.hip: enqueue), repaired there as well.
+// Nearly every record is done after reading its flags; the lookup is for the few DF 11/17/18/19 replies that failed parity.
+__global__ void __launch_bounds__(kThreads) k_fec(Rec* out, const Summary* sum, int out_cap, Rec* host_out, int host_cap) {
+  int n = sum->n_kept;
+  if (n > out_cap) n = out_cap;
+  for (int t = (int)(blockIdx.x * kThreads + threadIdx.x); t < n; t += (int)(gridDim.x * kThreads)) {
+    unsigned long long w2 = out[t].w[2], w3 = out[t].w[3];
+    if (!fec_record(w2, w3)) continue;
+    out[t].w[2] = w2; out[t].w[3] = w3;
+    if (t < host_cap) { host_out[t].w[2] = w2; host_out[t].w[3] = w3; }
+  }
+}
+
+// The same for the stand-alone demod's slices (k_slice's bits14 / ok, one thread per tag).  ok[t]'s bits 0, 5, 6, 7 are the
+// record flags kDemod, kParityOk, kLongFmt, kKnownDf; kFecFixed / kFecDf travel in bits 1 / 2 (the flag >> 13), which k_slice
+// leaves zero.
+__global__ void __launch_bounds__(kThreads) k_fec_slices(unsigned char* bits14, unsigned char* ok, int ntags) {
+  for (int t = (int)(blockIdx.x * kThreads + threadIdx.x); t < ntags; t += (int)(gridDim.x * kThreads)) {
+    unsigned char* p = bits14 + (long long)t * 14;
+    unsigned long long w2 = 0, w3 = (unsigned long long)ok[t] << 48;
+    for (int k = 0; k < 8; ++k) w2 |= (unsigned long long)p[k] << (8 * k);
+    for (int k = 0; k < 6; ++k) w3 |= (unsigned long long)p[8 + k] << (8 * k);
+    if (!fec_record(w2, w3)) continue;
+    for (int k = 0; k < 8; ++k) p[k] = (unsigned char)(w2 >> (8 * k));
+    for (int k = 0; k < 6; ++k) p[8 + k] = (unsigned char)(w3 >> (8 * k));
+    const unsigned fl = (unsigned)(w3 >> 48);
+    ok[t] = (unsigned char)((fl & 0xE1u) | ((fl & (kFecFixed | kFecDf)) >> 13));
   }
 }
 

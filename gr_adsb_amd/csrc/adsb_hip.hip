@@ -554,6 +554,16 @@ void launch_confidence(hipStream_t st, int grid, const DetectArgs& a, const Rec*
   hipLaunchKernelGGL((k_confidence<MODE>), dim3(grid), dim3(kThreads), 0, st, a, out, sum, cap, ratio);
 }
 
+// opt-in Conservative FEC (ADSB_FLAG_FEC_CONSERVATIVE) of a pass's records, in place: one thread per list slot up to 2048
+// workgroups, each leaves at once past sum->n_kept
+void launch_fec(hipStream_t st, const Slot& s, Rec* out, const Summary* sum) {
+  long long g = (s.tot + kThreads - 1) / kThreads;
+  if (g > 2048) g = 2048;
+  if (g < 1) g = 1;
+  hipLaunchKernelGGL(k_fec, dim3((unsigned)g), dim3(kThreads), 0, st, out, sum, (int)s.tot,
+                     (Rec*)(s.host_cap > 0 ? s.h_out : nullptr), s.host_cap);
+}
+
 // adsb_wait_for_event: the caller's pending events are waited for by `st`, the stream the next call's first operation runs on
 int apply_ext(adsb_ctx* c, hipStream_t st) {
   for (int i = 0; i < c->n_ext; ++i) HIPCHK(c, hipStreamWaitEvent(st, c->ext_ev[i], 0));
@@ -584,6 +594,12 @@ int enqueue_tail(adsb_ctx* c, Slot& s) {
     t.seq = s.seq;
     if (s.fused) launch_pass_small(ts, a, t);
     else ADSB_BY_MODE(pl.mode, launch_tail_small, ts, a, t);
+    if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) {
+      // the repair follows the published pass number: the host waits for the event behind it instead of polling
+      launch_fec(ts, s, (Rec*)s.h_out, &misc->sum);
+      HIPCHK(c, hipEventRecord(s.done, ts));
+      return 0;
+    }
     // the host polls the pass number in the pinned summary (finish): no completion event on the stream
     s.polled = true;
     return 0;
@@ -625,6 +641,7 @@ int enqueue_tail(adsb_ctx* c, Slot& s) {
   hipLaunchKernelGGL(k_compact, dim3(ag), dim3(kThreads), 0, ts, (const unsigned long long*)sorted, (const Rec*)a.recs, (const unsigned*)sorted_src,
                      &misc->sum, (const int*)s.d_seg.p, fmask, fwant, pl.head_n, (Rec*)(s.direct ? s.h_out : s.d_out.p), (int)s.tot,
                      a.long_count, a.long_lastp, &misc->acc, s.h_sum, (Rec*)(s.host_cap > 0 ? s.h_out : nullptr), s.host_cap);
+  if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) launch_fec(ts, s, (Rec*)s.d_out.p, &misc->sum);
   HIPCHK(c, hipEventRecord(s.done, ts));
   return 0;
 }
@@ -1029,6 +1046,56 @@ uint32_t adsb_mode_s_syndrome(const uint8_t bits[14], int32_t* df_out, int32_t* 
   if (df_out) *df_out = (int32_t)df;
   if (nbits_out) *nbits_out = known ? L : 0;
   return syn;
+}
+
+// pre-filter flags of one payload (the device's parity_flags_of, from adsb_mode_s_syndrome)
+static uint32_t host_parity_flags(const uint8_t b[14]) {
+  int32_t df = 0, nbits = 0;
+  const uint32_t syn = adsb_mode_s_syndrome(b, &df, &nbits);
+  uint32_t f = (uint32_t)df << ADSB_BURST_DF_SHIFT;
+  if (nbits == 112) f |= ADSB_BURST_LONG;
+  if (nbits) f |= ADSB_BURST_KNOWN_DF;
+  if (((1u << df) & kDfPiSet) && syn == 0) f |= ADSB_BURST_PARITY_OK;
+  return f;
+}
+
+uint32_t adsb_mode_s_fec(const uint8_t in[14], uint8_t out[14], int32_t* first_bit, int32_t* nflip) {
+  // decoder.py:304-323: for burst lengths 1, 2 and every position, key = compute_crc_2 of the pattern; :738-763: the payload's
+  // key looked up, the pattern applied.  compute_crc_2(bits[0:L]) (:716-736) is the L-bit message mod x*G(x) -- 25 bits
+  static constexpr CrcTab tab = make_crc_tab();
+  auto key = [](const uint8_t* b, int L) {        // sum over set bits i of x^(L-1-i) mod x*G = x * (x^(L-2-i) mod G), or 1
+    uint32_t k = 0;
+    for (int i = 0; i < L; ++i)
+      if ((b[i >> 3] >> (7 - (i & 7))) & 1) k ^= (i == L - 1) ? 1u : (tab.r[L - 2 - i] << 1);
+    return k;
+  };
+  uint8_t b[14];
+  memcpy(b, in, 14);
+  if (first_bit) *first_bit = -1;
+  if (nflip) *nflip = 0;
+  const uint32_t flags = host_parity_flags(b);
+  const unsigned df = b[0] >> 3;
+  if (out) memcpy(out, b, 14);
+  if (!((1u << df) & kDfPiSet) || (flags & ADSB_BURST_PARITY_OK)) return flags;
+  const int L = (flags & ADSB_BURST_LONG) ? 112 : 56;
+  const uint32_t k = key(b, L);
+  for (int len = 1; len <= 2; ++len)
+    for (int i = 0; i + len <= L; ++i) {
+      uint8_t e[14] = {0};
+      for (int q = i; q < i + len; ++q) e[q >> 3] |= (uint8_t)(0x80u >> (q & 7));
+      if (key(e, L) != k) continue;
+      if (first_bit) *first_bit = i;
+      if (nflip) *nflip = len;
+      for (int q = 0; q < 14; ++q) e[q] ^= b[q];
+      const uint32_t f2 = host_parity_flags(e);
+      const unsigned df2 = e[0] >> 3;
+      if (((1u << df2) & kDfPiSet) && ((f2 & ADSB_BURST_LONG) == (flags & ADSB_BURST_LONG))) {
+        if (out) memcpy(out, e, 14);
+        return f2 | ADSB_BURST_FEC_FIXED;
+      }
+      return flags | ADSB_BURST_FEC_DF;
+    }
+  return flags;
 }
 
 float adsb_snr_db(float peak, float median) {
@@ -1444,6 +1511,11 @@ int adsb_demod_work(adsb_ctx* c, const float* in0, int64_t n, int64_t nitems_rea
   hipLaunchKernelGGL((k_slice<1>), dim3(nb), dim3(kThreads), 0, c->stream, (const void*)d, (long long)n,
                      (const long long*)loc, (int)ntags, c->sps, (unsigned char*)(h + o_bits),
                      (unsigned char*)(h + o_ok), ratio ? (float*)(h + o_ratio) : (float*)nullptr);
+  if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) {
+    const int fb = (int)((nt + kThreads - 1) / kThreads < 2048 ? (nt + kThreads - 1) / kThreads : 2048);
+    hipLaunchKernelGGL(k_fec_slices, dim3(fb), dim3(kThreads), 0, c->stream, (unsigned char*)(h + o_bits),
+                       (unsigned char*)(h + o_ok), (int)ntags);
+  }
   hipError_t he = hipStreamSynchronize(c->stream);            // always: nothing stays queued behind an error return
   if (he == hipSuccess) he = hipGetLastError();
   if (he != hipSuccess) return fail(c, -EIO, "k_slice", he);
@@ -1747,9 +1819,9 @@ int adsb_process_sharded_multi(adsb_ctx* const* ctxs, int32_t n_ctx, int fmt, co
     if (!c) return -EINVAL;
     for (int j = 0; j < k; ++j) if (ctxs[j] == c) return fail(c0, -EINVAL, "adsb_process_sharded_multi: a context listed twice");
     // one stream, one set of rules: every context must have been created with the same rate, threshold, gate and scale
-    if (c->sps != c0->sps || !(c->thr == c0->thr) || ((c->flags ^ c0->flags) & ADSB_FLAG_LONG_AWARE_GATE) ||
+    if (c->sps != c0->sps || !(c->thr == c0->thr) || ((c->flags ^ c0->flags) & (ADSB_FLAG_LONG_AWARE_GATE | ADSB_FLAG_FEC_CONSERVATIVE)) ||
         !(c->scale[fmt] == c0->scale[fmt]))
-      return fail(c0, -EINVAL, "adsb_process_sharded_multi: contexts differ in rate, threshold, gate or format scale");
+      return fail(c0, -EINVAL, "adsb_process_sharded_multi: contexts differ in rate, threshold, gate, FEC or format scale");
     if (c->flags & ADSB_FLAG_CONFIDENCE) return fail(c0, -EINVAL, "adsb_process_sharded_multi: not for ADSB_FLAG_CONFIDENCE contexts");
     if (!c->own_stream) return fail(c0, -EINVAL, "adsb_process_sharded_multi: not for contexts on a caller-owned stream");
     for (const Slot& sl : c->slot) if (sl.busy) return fail(c0, -EBUSY, "a submitted call is still pending on one of the contexts");

@@ -87,6 +87,14 @@ extern "C" {
  * SURVEY.md §8e) half of the host-fed traffic would otherwise cross the socket interconnect.  This flag turns it off
  * (adsb_numa_info still reports what was found).  No reference counterpart: the reference is one Python thread. */
 #define ADSB_FLAG_NO_NUMA_BINDING 64u
+/* Opt-in: the decoder's error_corr="Conservative" (decoder.py:738-780) on the device.  Every delivered record with
+ * ADSB_BURST_DEMOD whose DF is 11/17/18/19 and whose syndrome is non-zero is looked up in the decoder's table of 1-bit and
+ * 2-adjacent-bit error patterns (adsb_mode_s_fec states the rule): a repair that keeps a DF of that set and its length is
+ * applied to bits[] (ADSB_BURST_FEC_FIXED, the pre-filter bits then describe the repaired reply); a repair that would change
+ * the format leaves the bits raw (ADSB_BURST_FEC_DF).  One small kernel per pass, queued before the records reach the host;
+ * every entry point that returns records applies it, and adsb_demod_work applies it to its slices.  Without the flag nothing
+ * is launched and no byte changes.  Confidence ratios stay those of the raw slice (demod.py:101). */
+#define ADSB_FLAG_FEC_CONSERVATIVE 128u
 
 /* adsb_burst.flags */
 #define ADSB_BURST_DEMOD 1u /* eob inside the demod input: bits[] valid, a PDU is published (demod.py:82) */
@@ -102,6 +110,9 @@ extern "C" {
 #define ADSB_BURST_DF_SHIFT 8    /* (flags >> 8) & 31 = downlink format (decoder.py:551) */
 #define ADSB_BURST_DF(flags) (((flags) >> ADSB_BURST_DF_SHIFT) & 31u)
 #define ADSB_BURST_LONG_HINT 0x2000u /* long-aware contexts only: this burst holds the gate for 119*sps */
+/* ADSB_FLAG_FEC_CONSERVATIVE contexts only (kDemod records of DF 11/17/18/19 that failed parity): */
+#define ADSB_BURST_FEC_FIXED 0x4000u /* a 1-bit / 2-adjacent-bit error was repaired: bits[] and the pre-filter bits are the repaired reply's */
+#define ADSB_BURST_FEC_DF 0x8000u    /* the decoder's repair would change the DF (or its length): bits[] left raw */
 
 typedef struct adsb_ctx adsb_ctx;
 
@@ -269,7 +280,8 @@ int adsb_framer_work_passthrough(adsb_ctx* ctx, const float* in0, int64_t n_in0,
  * for a sync block); tag_offsets = absolute offsets of the "burst" tags inside [nitems_read,
  * nitems_read+n).  bits112: ntags*112 bytes of 0/1 (the u8vector the PDU carries); ok[t] != 0 when the
  * burst was demodulated, 0 when it straddles the end of the chunk and is dropped (demod.py:82,130-133);
- * a non-zero ok[t] is ADSB_BURST_DEMOD | the pre-filter bits ADSB_BURST_PARITY_OK / _LONG / _KNOWN_DF.
+ * a non-zero ok[t] is ADSB_BURST_DEMOD | the pre-filter bits ADSB_BURST_PARITY_OK / _LONG / _KNOWN_DF, and on an
+ * ADSB_FLAG_FEC_CONSERVATIVE context ADSB_BURST_FEC_FIXED >> 13 (2) / ADSB_BURST_FEC_DF >> 13 (4), with bits112 repaired.
  * ratio (optional, may be NULL): ntags*112 floats bit1_amp/bit0_amp; 10*log10 of it is
  * demod.bit_confidence (demod.py:101). */
 int adsb_demod_work(adsb_ctx* ctx, const float* in0, int64_t n, int64_t nitems_read,
@@ -370,6 +382,14 @@ float adsb_snr_db(float peak, float median);
  * *nbits = 56 / 112, or 0 for a DF check_parity() does not know (the 56-bit reading is returned).
  * Pure host arithmetic on one 14-byte payload; out pointers may be NULL. */
 uint32_t adsb_mode_s_syndrome(const uint8_t bits[14], int32_t* df, int32_t* nbits);
+
+/* The rule of ADSB_FLAG_FEC_CONSERVATIVE for one 14-byte payload of a demodulated burst, as plain host arithmetic: the
+ * decoder's correct_burst_errors() (decoder.py:304-323 table, :738-763 lookup) for DF 11/17/18/19 with a non-zero syndrome,
+ * the pattern looked up by its 25-bit compute_crc_2 key.  Returns the flags the device gives the record: the pre-filter bits
+ * (ADSB_BURST_PARITY_OK / _LONG / _KNOWN_DF / DF) of out, plus ADSB_BURST_FEC_FIXED or ADSB_BURST_FEC_DF.  out = the repaired
+ * payload when FEC_FIXED, else a copy of in (in and out may be the same array).  *first_bit / *nflip = the table's pattern
+ * (bits first_bit .. first_bit+nflip-1) on a hit, FEC_DF included; -1 / 0 without one.  Out pointers may be NULL. */
+uint32_t adsb_mode_s_fec(const uint8_t in[14], uint8_t out[14], int32_t* first_bit, int32_t* nflip);
 
 /* How one call over n_samples is cut on a device that keeps `resident_wavefronts` wavefronts of the streaming kernel
  * resident (adsb_stats.detect_grid / blocks_per_cu tell what a context uses: CUs x blocks_per_cu x 4, or x 1 for the 8-bit formats): *units chunks of
