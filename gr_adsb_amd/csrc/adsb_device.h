@@ -36,8 +36,24 @@
 // kernels run on a machine without a GPU.
 #pragma once
 
+// ADSB_ROUTE(id, offset): a test hook at every site that slices a burst's 112 bits (id: the Route below, offset: the burst's
+// stream offset).  Empty here, so the product's code objects do not depend on it; tests/sim/sim_driver.cpp defines it to log
+// which route built which record.
+#ifndef ADSB_ROUTE
+#define ADSB_ROUTE(id, offset) ((void)0)
+#endif
 
 namespace adsb {
+
+enum Route : int {
+  kRouteWindow = 0,       // k_detect: every bit sample in the LDS window
+  kRoutePend = 1,         // k_detect: first pairs now, the rest from later tiles (pending list)
+  kRoutePendFull = 2,     // k_detect: pending list full -- the missing samples from global memory
+  kRouteFlush = 3,        // k_detect: still pending at the end of the wavefront's chunk (pend_flush)
+  kRouteLongFast = 4,     // k_longrun: burst_finish, whole footprint inside the buffer
+  kRouteLongClipped = 5,  // k_longrun: burst_finish, clipped noise window or burst near the end of the buffer
+  kRouteCount = 6
+};
 
 constexpr int kThreads = 256;            // 4 wavefronts per workgroup: the tail kernels and the one-launch small pass
 constexpr int kWaves = kThreads / 64;
@@ -652,6 +668,7 @@ __device__ void burst_finish(const DetectArgs& a, const BurstFetch<MODE>& f, Rec
   float peak, v0, v1, x1, x0, y1, y0;
   bool val0, val1;
   if (f.fast) {                                          // wave-uniform
+    ADSB_ROUTE(kRouteLongFast, a.origin + p);
     nwin = kNoise; val0 = true; val1 = lane < kNoise - 64;
     peak = raw_mag2<MODE>(f.peak, a.scale);
     v0 = raw_mag2<MODE>(f.w0, a.scale);
@@ -659,6 +676,7 @@ __device__ void burst_finish(const DetectArgs& a, const BurstFetch<MODE>& f, Rec
     x1 = raw_mag2<MODE>(f.x1, a.scale); x0 = raw_mag2<MODE>(f.x0, a.scale);
     y1 = raw_mag2<MODE>(f.y1, a.scale); y0 = raw_mag2<MODE>(f.y0, a.scale);
   } else {
+    ADSB_ROUTE(kRouteLongClipped, a.origin + p);
     long long wlo = p - kNoise;
     if (wlo < a.in0_base) wlo = a.in0_base;
     nwin = (int)(p - wlo);
@@ -741,8 +759,10 @@ __device__ __forceinline__ void burst_from_window(WinArgs<CP> a, const float* s_
   if (dem) {                                                 // wave-uniform
     if (p + 119 * sps + half < kWWin) {
       // every 2 Msps burst that starts in the tile: all 224 bit samples lie in the LDS window
+      ADSB_ROUTE(kRouteWindow, a.origin + P);
       slice_window(s_x, p, sps, half, 0, lane, &ma, &mb);
     } else if (*n_pend < kMaxPend) {
+      ADSB_ROUTE(kRoutePend, a.origin + P);
       slice_window(s_x, p, sps, half, 0, lane, &ma, &mb);    // what is here already; the rest when it arrives
       if (lane == 0) {
         PendEntry e;
@@ -752,6 +772,7 @@ __device__ __forceinline__ void burst_from_window(WinArgs<CP> a, const float* s_
       *n_pend += 1;
       return;
     } else {
+      ADSB_ROUTE(kRoutePendFull, a.origin + P);
       const int j0 = p + 8 * sps + lane * sps;               // demod.py:75,87
       auto smp = [&](int j) -> float { return (j < kWWin) ? s_x[j] : xg<MODE>(a.c->data, a.c->n, t0 + j, a.scale); };
       const float x1 = smp(j0), x0 = smp(j0 + half);
@@ -849,6 +870,7 @@ __device__ __forceinline__ void pend_flush(const PendList* pend, int n_pend, Win
   const int sps = a.sps, half = sps >> 1;
   for (int i = 0; i < n_pend; ++i) {
     const PendEntry e = pend->e[i];                          // p relative to t0 (the last tile's start)
+    ADSB_ROUTE(kRouteFlush, a.origin + t0 + e.p);
     const int ja = e.p + 8 * sps + lane * sps, jb = ja + 64 * sps;
     auto smp = [&](int j) -> float { return (j < kWWin) ? s_x[j] : xg<MODE>(a.c->data, a.c->n, t0 + j, a.scale); };
     const bool ta = ja + half >= kWWin, tb = lane < 48 && jb + half >= kWWin;     // pairs no window has held

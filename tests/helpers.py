@@ -40,6 +40,13 @@ def pathological_names():
     return _names("P*.npz")
 
 
+def path_golden_names():
+    """Burst-route vectors (tools/make_golden_paths.py): long-pulse bursts, a preamble train and a burst that straddles the
+    end, float32 |IQ|^2 at 4 / 8 / 20 / 12 Msps, single call, fixed-2048, random 1-3000 and
+    fixed-8192 schedules."""
+    return _names("Qpaths_*.npz")
+
+
 def schedules_of(name):
     z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
     return [k[:-len("_schedule")] for k in z.files if k.endswith("_schedule")]

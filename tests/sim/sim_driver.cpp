@@ -4,10 +4,18 @@
 // oracle in the GPU-less build container.  Never linked into libadsb_hip.so.
 #include "hipsim.h"
 
+#include <vector>
+
+// ADSB_ROUTE (adsb_device.h): which site sliced the bits of which burst -- one entry per burst (lane 0 of the wavefront
+// that builds it), the stream offset of its centre, kept until sim_route_reset()
+static std::vector<long long> g_route_off[8];
+static void sim_route(int id, long long offset) {
+  if ((threadIdx.x & 63u) == 0 && id >= 0 && id < 8) g_route_off[id].push_back(offset);
+}
+#define ADSB_ROUTE(id, offset) sim_route((id), (long long)(offset))
+
 #include "../../gr_adsb_amd/csrc/adsb_device.h"
 #include "../../gr_adsb_amd/csrc/adsb_plan.h"
-
-#include <vector>
 
 using namespace adsb;
 
@@ -176,6 +184,15 @@ void sim_set_long_aware(int v) { g_long_aware = v; }
 void sim_geometry(int* tile, int* fwd, int* back) { *tile = kWTile; *fwd = kFwd; *back = kBack; }
 void sim_set_confidence_out(float* p) { g_conf_out = p; }
 void sim_set_tail_mode(int m) { g_tail_mode = m; }
+void sim_route_reset() { for (auto& v : g_route_off) v.clear(); }
+// number of bursts route `id` has sliced since the last reset; their offsets (in order of slicing) to out[0 .. cap)
+long long sim_route_offsets(int id, long long* out, long long cap) {
+  if (id < 0 || id >= 8) return -1;
+  const std::vector<long long>& v = g_route_off[id];
+  for (long long i = 0; i < (long long)v.size() && i < cap; ++i) out[i] = v[(size_t)i];
+  return (long long)v.size();
+}
+int sim_route_count() { return kRouteCount; }
 
 // k_detect's own conversion of one 16-byte load (body_convert) for the 8-bit formats: words[4*k .. 4*k+4) -> out[8*k .. 8*k+8).
 // mode 3 int8, 4 offset-binary uint8, 5 / 6 their power-of-two-scale instances (v_dot4c_i32_i8, see adsb_device.h).

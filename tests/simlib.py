@@ -127,14 +127,15 @@ def sim_shard(mode, data, origin, own_lo, own_hi, stream_len, fs, thr, head_cand
     return _call(lib().sim_shard, args, max(16, len(data) // 2 + 16), gate=False)
 
 
-def sim_slice(in0, tag_idx, sps, want_ratio=True):
+def sim_slice(in0, tag_idx, sps, want_ratio=True, fill=0):
+    """k_slice over the tags; fill: the byte every output array holds before the kernel runs"""
     c = ctypes
     in0 = np.ascontiguousarray(in0, dtype=np.float32)
     tag_idx = np.ascontiguousarray(tag_idx, dtype=np.int64)
     nt = len(tag_idx)
-    bits = np.zeros((nt, 14), dtype=np.uint8)
-    ok = np.zeros(nt, dtype=np.uint8)
-    ratio = np.zeros((nt, 112), dtype=np.float32)
+    bits = np.full((nt, 14), fill, dtype=np.uint8)
+    ok = np.full(nt, fill, dtype=np.uint8)
+    ratio = np.full((nt, 112 * 4), fill, dtype=np.uint8).view(np.float32)
     lib().sim_slice(in0.ctypes.data_as(c.c_void_p), c.c_longlong(len(in0)), tag_idx.ctypes.data_as(c.c_void_p), c.c_int(nt),
                     c.c_int(sps), bits.ctypes.data_as(c.c_void_p), ok.ctypes.data_as(c.c_void_p),
                     ratio.ctypes.data_as(c.c_void_p) if want_ratio else None)
@@ -156,6 +157,43 @@ class tail_mode:
 
     def __exit__(self, *a):
         lib().sim_set_tail_mode(0)
+
+
+# the slicing sites of adsb_device.h (enum Route), logged by the emulator's ADSB_ROUTE
+ROUTES = ("window", "pend", "pend_full", "flush", "long_fast", "long_clipped")
+
+
+def route_reset():
+    lib().sim_route_reset()
+
+
+def route_offsets():
+    """{route name: int64[] stream offsets of the bursts it sliced since route_reset(), in the order they were sliced}"""
+    L = lib()
+    L.sim_route_offsets.restype = ctypes.c_longlong
+    assert L.sim_route_count() == len(ROUTES)
+    out = {}
+    for k, name in enumerate(ROUTES):
+        n = L.sim_route_offsets(ctypes.c_int(k), None, ctypes.c_longlong(0))
+        buf = np.zeros(max(n, 1), dtype=np.int64)
+        L.sim_route_offsets(ctypes.c_int(k), buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_longlong(n))
+        out[name] = buf[:n]
+    return out
+
+
+class confidence_out:
+    """with simlib.confidence_out(cap) as ratio: ... -- the runs inside also run k_confidence (ADSB_FLAG_CONFIDENCE) into
+    ratio[cap][112] float32; row t belongs to kept record t of the LAST run, rows of records without a PDU are untouched.
+    The array is filled with an all-ones bit pattern first."""
+    def __init__(self, cap):
+        self.buf = np.full((cap, 112), 0xFFFFFFFF, dtype=np.uint32).view(np.float32)
+
+    def __enter__(self):
+        lib().sim_set_confidence_out(self.buf.ctypes.data_as(ctypes.c_void_p))
+        return self.buf
+
+    def __exit__(self, *a):
+        lib().sim_set_confidence_out(None)
 
 
 class long_aware_gate:

@@ -5,8 +5,8 @@ import os
 import numpy as np
 import pytest
 
-from helpers import (GOLDEN_DIR, SCHEDULES, Golden, bulk_golden_names, golden_names, large_golden_names, pathological_names,
-                     rate_golden_names, schedules_of, snr_bits, unpack)
+from helpers import (GOLDEN_DIR, SCHEDULES, Golden, bulk_golden_names, golden_names, large_golden_names, path_golden_names,
+                     pathological_names, rate_golden_names, schedules_of, snr_bits, unpack)
 from oracle import adsb_oracle as O
 from oracle import c_oracle as C
 
@@ -120,6 +120,21 @@ def test_oracles_match_pathological_reference_goldens(name):
     """tests/golden/P*.npz: NaN / inf, thresholds <= 0, plateaus over several tiles, start / end high, ties, tiny inputs
     -- the reference's own outputs, so the GPU box does not rest on the C oracle alone for these."""
     g = Golden(name)
+    for sched in schedules_of(name):
+        _numpy_oracle_vs(g, sched)
+    _c_oracle_vs(g)
+
+
+@pytest.mark.parametrize("name", path_golden_names())
+def test_oracles_match_path_reference_goldens(name):
+    """tests/golden/Qpaths_*.npz (tools/make_golden_paths.py): long-pulse bursts, a preamble train and a burst straddling
+    the end -- the reference's own outputs; the stored input is what tests/burst_paths.py generates."""
+    import burst_paths as B
+    g = Golden(name)
+    x, thr = B.fixture_stream(g.sps)
+    assert np.array_equal(x.view(np.uint32), g.x.view(np.uint32)) and np.float32(thr) == np.float32(g.thr)
+    assert len(path_golden_names()) == 4 and sorted(schedules_of(name)) == ["fixed2048", "fixed8192", "random", "single"]
+    assert len(g.get("fixed8192", "pdu_offsets")) > 5           # chunked calls that publish PDUs at every rate
     for sched in schedules_of(name):
         _numpy_oracle_vs(g, sched)
     _c_oracle_vs(g)
