@@ -23,6 +23,7 @@ FLAG_FRAMER_SLICES = 32   # adsb_framer_work also returns the 112 bits of tags w
 FLAG_NO_NUMA_BINDING = 64 # host side not placed on the GPU's NUMA node (default: page-locked buffers and copy threads are)
 FLAG_LOW_LATENCY = 16     # the tail of a pass runs beside the next pass's k_detect: results a pass earlier, 1-2 % less throughput
 FLAG_FEC_CONSERVATIVE = 128  # opt-in: the decoder's "Conservative" 1-2-bit burst repair on the device (decoder.py:738-780)
+FLAG_AIRCRAFT_TABLE = 256    # opt-in: the decoder's aircraft table on the device: verdicts for address/parity replies
 ABI_VERSION = 5
 # input sample formats (include/adsb_hip.h ADSB_FMT_*): numpy dtype of the flat host array, items per sample
 FMT_FC32, FMT_MAG2, FMT_SC16, FMT_SC8, FMT_CU8 = 0, 1, 2, 3, 4
@@ -38,6 +39,8 @@ BURST_DF_SHIFT = 8
 BURST_LONG_HINT = 0x2000 # records of a long-aware context: this burst holds the gate for 119*sps
 BURST_FEC_FIXED = 0x4000 # FLAG_FEC_CONSERVATIVE: bits repaired, the pre-filter bits are the repaired reply's
 BURST_FEC_DF = 0x8000    # FLAG_FEC_CONSERVATIVE: the decoder's repair would change the DF; bits left raw
+BURST_AP_FEC = 0x0004    # FLAG_AIRCRAFT_TABLE + FLAG_FEC_CONSERVATIVE: AA unknown, the decoder's repair accepts the reply
+BURST_AP_KNOWN = 0x0008  # FLAG_AIRCRAFT_TABLE: the AA of this address/parity reply was announced by an earlier PDU
 MAX_IN_FLIGHT = 3
 
 EXPORTS = [
@@ -47,7 +50,7 @@ EXPORTS = [
     "adsb_set_iq16_scale", "adsb_process_iq16", "adsb_process_iq16_device",
     "adsb_set_format_scale", "adsb_process_format", "adsb_process_format_device", "adsb_submit_format_device",
     "adsb_submit_format_host", "adsb_last_confidence",
-    "adsb_framer_work", "adsb_framer_work_passthrough", "adsb_demod_work", "adsb_shard_bounds", "adsb_process_sharded_device", "adsb_shard_device", "adsb_shard_host", "adsb_shard_fixup", "adsb_stitch", "adsb_snr_db", "adsb_mode_s_syndrome", "adsb_mode_s_fec", "adsb_plan_chunks", "adsb_get_stats",
+    "adsb_framer_work", "adsb_framer_work_passthrough", "adsb_demod_work", "adsb_shard_bounds", "adsb_process_sharded_device", "adsb_shard_device", "adsb_shard_host", "adsb_shard_fixup", "adsb_stitch", "adsb_snr_db", "adsb_mode_s_syndrome", "adsb_mode_s_fec", "adsb_mode_s_aircraft", "adsb_plan_chunks", "adsb_get_stats",
     "adsb_process_sharded_multi", "adsb_device_alloc", "adsb_device_free", "adsb_device_upload", "adsb_clear_pending_events",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
 ]
@@ -148,6 +151,8 @@ def load():
     lib.adsb_mode_s_syndrome.restype = c.c_uint32
     lib.adsb_mode_s_fec.argtypes = [vp, vp, c.POINTER(i32), c.POINTER(i32)]
     lib.adsb_mode_s_fec.restype = c.c_uint32
+    lib.adsb_mode_s_aircraft.argtypes = [vp, i32, c.POINTER(i32), c.POINTER(i32), c.POINTER(i32)]
+    lib.adsb_mode_s_aircraft.restype = c.c_uint32
     lib.adsb_plan_chunks.argtypes = [i64, i64, c.POINTER(i64), c.POINTER(i64)]
     lib.adsb_plan_chunks.restype = c.c_int32
     lib.adsb_get_stats.argtypes = [vp, c.POINTER(Stats)]
@@ -682,11 +687,25 @@ def mode_s_fec(bits14):
     return int(fl), out, first.value, nflip.value
 
 
+def mode_s_aircraft(bits14, fec=False):
+    """adsb_mode_s_aircraft: (ap_fec, aa, announce, fec_announce) of one 14-byte payload -- the per-PDU rule FLAG_AIRCRAFT_TABLE
+    applies on the device (aa: the AA of an address/parity reply or -1; announce: the address the PDU announces whatever the
+    table holds, or -1; ap_fec: an unknown address/parity reply the Conservative repair accepts, then announcing
+    fec_announce, or -1)."""
+    b = np.ascontiguousarray(bits14, dtype=np.uint8)
+    assert b.size == 14
+    aa, ann, fann = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    r = load().adsb_mode_s_aircraft(b.ctypes.data_as(ctypes.c_void_p), 1 if fec else 0, ctypes.byref(aa), ctypes.byref(ann),
+                                    ctypes.byref(fann))
+    return bool(r & BURST_AP_FEC), aa.value, ann.value, fann.value
+
+
 def demod_flags(ok):
     """adsb_demod_work's ok[] bytes -> the record flag layout (uint16): bits 0, 5-7 are the same, the FEC verdicts of an
-    FLAG_FEC_CONSERVATIVE context travel in bits 1 / 2 (BURST_FEC_FIXED >> 13 / BURST_FEC_DF >> 13)."""
+    FLAG_FEC_CONSERVATIVE context travel in bits 1 / 2 (BURST_FEC_FIXED >> 13 / BURST_FEC_DF >> 13), the aircraft table's
+    of a FLAG_AIRCRAFT_TABLE context in bits 3 / 4 (BURST_AP_KNOWN / BURST_AP_FEC << 2)."""
     ok = np.asarray(ok, dtype=np.uint16)
-    return (ok & 0xE1) | ((ok & 6) << 13)
+    return (ok & 0xE1) | ((ok & 6) << 13) | (ok & BURST_AP_KNOWN) | ((ok & 16) >> 2)
 
 
 def unpack_bits(bits14):

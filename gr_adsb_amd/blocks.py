@@ -371,24 +371,33 @@ def _passthrough(ctx, out0, src):
 _DF_WEIGHTS = np.array([16, 8, 4, 2, 1])
 _PI_FORMATS = (11, 17, 18, 19)
 _ERROR_CORR = ("None", "Conservative", "Brute Force")      # decoder(error_corr=...) (grc/adsb_decoder.block.yml)
+_MSG_FILTER = ("All Messages", "Extended Squitter Only")   # decoder(msg_filter=...)
+_ES_FORMATS = (17, 18, 19)
 
 
-def _prefilter_pass(flags, df, fec=False):
+def _prefilter_pass(flags, df, fec=False, msg_filter=None):
     """A PDU can still pass decoder.check_parity(): known DF, and for the parity/interrogator formats a zero
-    syndrome (address/parity formats need the decoder's aircraft table and always go through).  fec: the bits were
-    published after the device's Conservative repair -- a repaired PDU has a zero syndrome, and one whose repair would
-    change its DF (BURST_FEC_DF, bits raw) is kept for the decoder's own repair."""
+    syndrome.  fec: the bits were published after the device's Conservative repair -- a repaired PDU has a zero
+    syndrome, and one whose repair would change its DF (BURST_FEC_DF, bits raw) is kept for the decoder's own repair.
+    msg_filter None: the address/parity formats always go through; "All Messages": they pass iff the device's aircraft
+    table knows their AA (BURST_AP_KNOWN) or, with fec, the decoder's repair accepts them (BURST_AP_FEC);
+    "Extended Squitter Only": only DF 17/18/19 can pass (decoder.py:562,667)."""
     if not flags & _native.BURST_KNOWN_DF:
+        return False
+    if msg_filter == "Extended Squitter Only" and df not in _ES_FORMATS:
         return False
     if df in _PI_FORMATS:
         return bool(flags & _native.BURST_PARITY_OK) or (fec and bool(flags & _native.BURST_FEC_DF))
+    if msg_filter == "All Messages":
+        return bool(flags & _native.BURST_AP_KNOWN) or (fec and bool(flags & _native.BURST_AP_FEC))
     return True
 
 
 class demod(gr.sync_block):
     """PPM bit slicer / PDU publisher (reference python/adsb/demod.py:31-136)."""
 
-    def __init__(self, fs, device=0, parity_filter=False, improved=False, framer=None, min_chunk=0, error_corr="None"):
+    def __init__(self, fs, device=0, parity_filter=False, improved=False, framer=None, min_chunk=0, error_corr="None", *,
+                 msg_filter=None):
         """framer (extension, default None = an independent block, like the reference's): the framer block of the same
         flowgraph whose output feeds this block.  That framer's device pass has already sliced the bits of every burst
         that ends inside its chunk; a paired demod publishes those PDUs straight from the framer's records -- the same
@@ -413,9 +422,23 @@ class demod(gr.sync_block):
         DF 11/17/18/19 PDU with a 1-bit or 2-adjacent-bit error is published repaired (counted in `self.corrected`), one
         whose repair would change its DF is published raw, for the decoder to repair.  With parity_filter=True exactly
         the PDUs a Conservative decoder can accept are kept.  "Brute Force" behaves as "None", like the decoder, whose
-        branch only logs (decoder.py:772-776)."""
+        branch only logs (decoder.py:772-776).
+
+        msg_filter (extension, named after the decoder's parameter; default None = every address/parity PDU goes through
+        the parity filter): the msg_filter of the decoder downstream, used with parity_filter=True.  "Extended Squitter
+        Only" keeps only the DF 17/18/19 PDUs such a decoder accepts.  "All Messages" also gives the address/parity
+        formats (DF 0/4/5/16/20/21/24) a verdict: the context keeps the decoder's aircraft table on the device
+        (FLAG_AIRCRAFT_TABLE: every PDU this block publishes announces its address as the decoder would), and such a PDU is
+        kept iff its AA was announced before -- or, with error_corr="Conservative", the decoder's repair accepts it.  Not
+        with framer= (there the framer's pass runs before this block's chunk decides what is published)."""
         if error_corr not in _ERROR_CORR:
             raise ValueError("error_corr must be one of %s, not %r" % (", ".join(_ERROR_CORR), error_corr))
+        if msg_filter is not None and msg_filter not in _MSG_FILTER:
+            raise ValueError("msg_filter must be None or one of %s, not %r" % (", ".join(_MSG_FILTER), msg_filter))
+        if framer is not None and msg_filter == "All Messages":
+            raise ValueError('msg_filter="All Messages" needs the demod\'s own device pass: not with framer=')
+        self.msg_filter = msg_filter
+        self._air = bool(parity_filter) and msg_filter == "All Messages"
         self.error_corr = error_corr
         self._fec = error_corr == "Conservative"
         self.corrected = 0
@@ -450,7 +473,8 @@ class demod(gr.sync_block):
             self.set_output_multiple(int(min_chunk))
         self._pmt_port, self._pmt_key = pmt.to_pmt("demodulated"), pmt.to_pmt("burst")
         self.message_port_register_out(self._pmt_port)
-        self._ctx = _native.Context(fs, 0.0, device=device, flags=_native.FLAG_FEC_CONSERVATIVE if self._fec else 0)
+        self._ctx = _native.Context(fs, 0.0, device=device, flags=(_native.FLAG_FEC_CONSERVATIVE if self._fec else 0) |
+                                                                   (_native.FLAG_AIRCRAFT_TABLE if self._air else 0))
 
     def work(self, input_items, output_items):
         in0 = input_items[0]
@@ -512,7 +536,7 @@ class demod(gr.sync_block):
                     if not ok[i]:
                         self.straddled_packet = 1     # demod.py:130-133: dropped
                         continue
-                    if self.parity_filter and not _prefilter_pass(int(pf[i]), int(bits[i][:5] @ _DF_WEIGHTS), self._fec):
+                    if self.parity_filter and not _prefilter_pass(int(pf[i]), int(bits[i][:5] @ _DF_WEIGHTS), self._fec, self.msg_filter):
                         self.filtered += 1
                         continue
                     if self._fec and int(pf[i]) & _native.BURST_FEC_FIXED:
@@ -542,7 +566,7 @@ class demod(gr.sync_block):
                 if not ok[i]:
                     self._pending.append((off, value))    # completed by a later call
                     continue
-                if self.parity_filter and not _prefilter_pass(int(pf[i]), int(bits[i][:5] @ _DF_WEIGHTS), self._fec):
+                if self.parity_filter and not _prefilter_pass(int(pf[i]), int(bits[i][:5] @ _DF_WEIGHTS), self._fec, self.msg_filter):
                     self.filtered += 1
                     continue
                 if self._fec and int(pf[i]) & _native.BURST_FEC_FIXED:

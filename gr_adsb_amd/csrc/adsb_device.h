@@ -42,6 +42,20 @@
 #ifndef ADSB_ROUTE
 #define ADSB_ROUTE(id, offset) ((void)0)
 #endif
+// ADSB_AIR_MIN / _LOAD / _STORE: the aircraft table's accesses, agent-scope atomics (the table is shared by every XCD: a
+// plain load could hit a stale line of another XCD's L2).  A host build without HIP (the SIMT emulator of tests/sim, whose
+// fibers run one at a time) gets plain memory operations.
+#ifndef ADSB_AIR_MIN
+#if defined(__HIP__)
+#define ADSB_AIR_MIN(p, v) __hip_atomic_fetch_min((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define ADSB_AIR_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define ADSB_AIR_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#else
+#define ADSB_AIR_MIN(p, v) atomicMin((p), (v))
+#define ADSB_AIR_LOAD(p) (*(p))
+#define ADSB_AIR_STORE(p, v) ((void)(*(p) = (v)))
+#endif
+#endif
 
 namespace adsb {
 
@@ -98,6 +112,10 @@ enum RecFlags : unsigned {
   // opt-in Conservative error correction (k_fec; decoder.py:738-780), kDemod only:
   kFecFixed = 0x4000u,      // a 1-bit / 2-adjacent-bit error was repaired: bits and parity bits are those of the repaired reply
   kFecDf = 0x8000u,         // the decoder's repair would change the downlink format: bits left raw
+  // opt-in aircraft table (k_air_*; decoder.py:576-665), kDemod records of the address/parity formats only.  They reuse the
+  // values of kNoMatch / kPending, which never reach a delivered record (k_count drops such words):
+  kApFec = 4u,      // AA unknown, but the decoder's Conservative repair accepts the reply (bits stay raw)
+  kApKnown = 8u,    // AA announced by an earlier published reply
 };
 
 // x^j mod G, j = 0..111, G = x^24 + 0xFFF409 (decoder.py:268-269: the 25 coefficients spell 0x1FFF409).  The
@@ -619,19 +637,12 @@ constexpr bool fec_tab_distinct() {
 }
 static_assert(fec_tab_distinct(), "decoder.py:314-316: the table's syndromes are distinct and non-zero");
 
-// correct_burst_errors() for one record: w2 / w3 = its words (bits, flags << 48).  Acts on kDemod records of DF 11/17/18/19
-// whose syndrome is non-zero (the address/parity formats need the consumer's aircraft table: left alone, as by the
-// pre-filter).  A hit whose repaired DF is again one of those, with the same length: bits repaired, parity bits recomputed,
-// + kFecFixed.  A hit that would change the format: bits left raw, + kFecDf (a "Conservative" decoder repairs those itself,
-// decoder.py:342-347).  Returns whether w2 / w3 changed.
-__device__ __forceinline__ bool fec_record(unsigned long long& w2, unsigned long long& w3) {
+// The decoder's table lookup (decoder.py:738-763) for one reply of syndrome `syn`, 112 bits (lng) or 56: on a hit, a / b =
+// its words w2 / w3 (flags dropped) with the pattern applied.  For the address/parity formats the syndrome is the AA itself.
+__device__ __forceinline__ bool fec_repair(unsigned long long w2, unsigned long long w3, bool lng, unsigned syn,
+                                           unsigned long long& a, unsigned long long& b) {
   static constexpr FecTab tab = make_fec_tab();
-  const unsigned fl = (unsigned)(w3 >> 48);
-  const unsigned dfb = 1u << ((unsigned)(w2 & 0xFFu) >> 3);
-  if (!(fl & kDemod) || (fl & kParityOk) || !(dfb & kDfPiSet)) return false;
-  const bool lng = (dfb & kDfLongSet) != 0;
   const int L = lng ? 112 : 56;
-  const unsigned syn = syndrome_of(w2, w3, L / 8);
   int lo = 0, hi = kFecPatterns;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
@@ -642,11 +653,26 @@ __device__ __forceinline__ bool fec_record(unsigned long long& w2, unsigned long
   if (j >= L) return false;
   const unsigned last = (unsigned)(lng ? (w3 >> 40) : (w2 >> 48)) & 1u;          // bits[L-1]: bit 0 of byte L/8-1
   if (last != (j == nflip - 1 ? 1u : 0u)) return false;
-  unsigned long long a = w2, b = w3 & 0xFFFFFFFFFFFFull;
+  a = w2; b = w3 & 0xFFFFFFFFFFFFull;
   for (int i = L - 1 - j; i < L - 1 - j + nflip; ++i) {
     const unsigned long long m = 1ull << (8 * ((i >> 3) & 7) + 7 - (i & 7));
     if (i < 64) a ^= m; else b ^= m;
   }
+  return true;
+}
+
+// correct_burst_errors() for one record: w2 / w3 = its words (bits, flags << 48).  Acts on kDemod records of DF 11/17/18/19
+// whose syndrome is non-zero (the address/parity formats need the aircraft table: k_air_verdict).  A hit whose repaired DF
+// is again one of those, with the same length: bits repaired, parity bits recomputed, + kFecFixed.  A hit that would change
+// the format: bits left raw, + kFecDf (a "Conservative" decoder repairs those itself, decoder.py:342-347).  Returns whether
+// w2 / w3 changed.
+__device__ __forceinline__ bool fec_record(unsigned long long& w2, unsigned long long& w3) {
+  const unsigned fl = (unsigned)(w3 >> 48);
+  const unsigned dfb = 1u << ((unsigned)(w2 & 0xFFu) >> 3);
+  if (!(fl & kDemod) || (fl & kParityOk) || !(dfb & kDfPiSet)) return false;
+  const bool lng = (dfb & kDfLongSet) != 0;
+  unsigned long long a, b;
+  if (!fec_repair(w2, w3, lng, syndrome_of(w2, w3, lng ? 14 : 7), a, b)) return false;
   const unsigned dfb2 = 1u << ((unsigned)(a & 0xFFu) >> 3);
   if ((dfb2 & kDfPiSet) && ((dfb2 & kDfLongSet) != 0) == lng) {
     const unsigned keep = fl & ~(kParityOk | kLongFmt | kKnownDf | (31u << kDfShift));
@@ -2162,6 +2188,209 @@ __global__ void __launch_bounds__(kThreads) k_fec_slices(unsigned char* bits14, 
     for (int k = 0; k < 6; ++k) p[8 + k] = (unsigned char)(w3 >> (8 * k));
     const unsigned fl = (unsigned)(w3 >> 48);
     ok[t] = (unsigned char)((fl & 0xE1u) | ((fl & (kFecFixed | kFecDf)) >> 13));
+  }
+}
+
+// ---- opt-in aircraft table (ADSB_FLAG_AIRCRAFT_TABLE): the decoder's plane_dict as check_parity uses it -------------------
+// The decoder accepts an address/parity (AP) reply -- DF 0/4/5/16/20/21/24 -- iff AA = crc(bits[0:L-24]) ^ bits[L-24:L] is
+// a key of plane_dict (decoder.py:576-665), and a published reply adds its address there iff decode_message reaches
+// update_plane.  The table holds, per 24-bit address, the KEY of its first announcement: (pass << 32) | the record's
+// position in the pass's delivered list (adsb_demod_work: its slice index), kAirEmpty if none.  An AP reply at key p is
+// known iff table[AA] < p.  atomicMin keeps the first announcement whatever order the threads run in.
+constexpr unsigned long long kAirEmpty = ~0ull;
+constexpr unsigned kDfApSet = (1u << 0) | (1u << 4) | (1u << 5) | (1u << 16) | (1u << 20) | (1u << 21) | (1u << 24);
+constexpr int kAirCondCap = 1024;
+constexpr unsigned kAirSkipped = 1u << 31;   // Summary::flags: this pass's table step was skipped (an earlier pass overflowed)
+// per-context state beside the table; only one table step runs at a time (adsb_hip.hip chains them with an event)
+struct AirState {
+  int broken;               // a pass's centre list overflowed: the passes behind it skip their table step until it is re-run
+  int ncond;                // candidates of the pass's conditional step
+  unsigned cond[kAirCondCap];
+};
+
+// The address a reply whose parity passed announces (decode_message / decode_me: decoder.py:883-947,1065-1232), from bits
+// 0..63 (be = big-endian: bit i of the message is bit 63-i), or -1.  DF 11: always; DF 17, 18 with CF 0/1/6, 19 with AF 0:
+// TC 1-4, 9-18, or 19 with ST 1/2.  The AP formats re-announce their AA, which is present already (see air_classify).
+__device__ __forceinline__ int air_announce(unsigned long long be) {
+  const unsigned df = (unsigned)(be >> 59), sub = (unsigned)(be >> 56) & 7u;
+  const unsigned tc = (unsigned)(be >> 27) & 31u, st = (unsigned)(be >> 24) & 7u;
+  const int aa = (int)((be >> 32) & 0xFFFFFFu);
+  if (df == 11) return aa;
+  if (df < 17 || df > 19 || (df == 18 && sub != 0 && sub != 1 && sub != 6) || (df == 19 && sub != 0)) return -1;
+  return ((tc >= 1 && tc <= 4) || (tc >= 9 && tc <= 18) || (tc == 19 && (st == 1 || st == 2))) ? aa : -1;
+}
+
+// One published record (w2 / w3: bits, flags << 48, after k_fec) as the table sees it.  ap = its AA (AP formats) or -1;
+// ann = its unconditional announcement or -1; with fec (Conservative contexts) rep = an AP reply the decoder's repair
+// accepts when AA is unknown, cann = what that path announces: the pre-repair AA when the repaired DF is an AP format that
+// reaches update_plane (not 24: decoder.py:890,930 use self.aa_str of check_parity), the repaired reply's own announcement
+// when it became DF 11/17/18/19, else -1.  A DF 11/17/18/19 record left raw by k_fec (kFecDf) announces what the decoder
+// decodes after its own repair (an AP result has aa_str == "", which matches no AA).
+__device__ __forceinline__ void air_classify(unsigned long long w2, unsigned long long w3, bool fec, int& ap, int& ann,
+                                             bool& rep, int& cann) {
+  ap = -1; ann = -1; rep = false; cann = -1;
+  const unsigned fl = (unsigned)(w3 >> 48);
+  if (!(fl & kDemod)) return;
+  const unsigned dfb = 1u << ((unsigned)(w2 & 0xFFu) >> 3);
+  const bool lng = (dfb & kDfLongSet) != 0;
+  unsigned long long a, b;
+  if (dfb & kDfApSet) {
+    ap = (int)syndrome_of(w2, w3, lng ? 14 : 7);
+    if (fec && fec_repair(w2, w3, lng, (unsigned)ap, a, b)) {
+      rep = true;
+      const unsigned dfb2 = 1u << ((unsigned)(a & 0xFFu) >> 3);
+      cann = (dfb2 & kDfApSet & ~(1u << 24)) ? ap : air_announce(__builtin_bswap64(a));
+    }
+  } else if (dfb & kDfPiSet) {
+    if (fl & kParityOk) ann = air_announce(__builtin_bswap64(w2));
+    else if ((fl & kFecDf) && fec_repair(w2, w3, lng, syndrome_of(w2, w3, lng ? 14 : 7), a, b))
+      ann = air_announce(__builtin_bswap64(a));
+  }
+}
+
+// What a table step reads and flags: a pass's delivered list (out; mirror = the pinned copy of its first mirror_cap records,
+// as for k_fec) or adsb_demod_work's slices (bits14 / ok, whose ok[] bits 3 / 4 carry kApKnown / kApFec).
+struct AirArgs {
+  Rec* out; Rec* mirror; int mirror_cap;
+  unsigned char* bits14; unsigned char* ok;
+  const Summary* sum;          // list: n = min(sum->n_kept, cap); slices: null, n = cap
+  int cap;
+  Summary* host_sum;           // list: the pass's pinned summary (kAirSkipped)
+  unsigned long long* table;   // 2^24 keys
+  AirState* st;
+  unsigned long long pass;     // key of position 0 of this pass
+  int fec;
+  int force;                   // a skipped step re-run by the host: `broken` no longer concerns it
+};
+__device__ __forceinline__ int air_n(const AirArgs& a) {
+  if (!a.sum) return a.cap;
+  return a.sum->n_kept < a.cap ? a.sum->n_kept : a.cap;
+}
+__device__ __forceinline__ void air_load(const AirArgs& a, int t, unsigned long long& w2, unsigned long long& w3) {
+  if (a.out) { w2 = a.out[t].w[2]; w3 = a.out[t].w[3]; return; }
+  const unsigned char* p = a.bits14 + (long long)t * 14;
+  const unsigned o = a.ok[t];
+  w2 = 0; w3 = 0;
+  for (int k = 0; k < 8; ++k) w2 |= (unsigned long long)p[k] << (8 * k);
+  for (int k = 0; k < 6; ++k) w3 |= (unsigned long long)p[8 + k] << (8 * k);
+  const unsigned fl = (o & 0xE1u) | ((o & 6u) << 13) | (o & kApKnown) | ((o & 16u) ? kApFec : 0u);
+  w3 |= (unsigned long long)fl << 48;
+}
+__device__ __forceinline__ void air_set(const AirArgs& a, int t, unsigned long long w3, unsigned fl) {
+  if (a.out) {
+    const unsigned long long v = (w3 & 0xFFFFFFFFFFFFull) | ((unsigned long long)fl << 48);
+    a.out[t].w[3] = v;
+    if (t < a.mirror_cap) a.mirror[t].w[3] = v;
+    return;
+  }
+  a.ok[t] = (unsigned char)((fl & 0xE1u) | ((fl & (kFecFixed | kFecDf)) >> 13) | (fl & kApKnown) | ((fl & kApFec) ? 16u : 0u));
+}
+// a pass whose list overflowed is re-run (adsb_hip.hip: finish); the passes queued behind it skip their step until then
+__device__ __forceinline__ bool air_skip(const AirArgs& a) {
+  return (a.sum && a.sum->overflow) || (!a.force && ADSB_AIR_LOAD(&a.st->broken) != 0);
+}
+
+// Step 1: every unconditional announcement of the pass.
+__global__ void __launch_bounds__(kThreads) k_air_announce(AirArgs a) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) ADSB_AIR_STORE(&a.st->ncond, 0);
+  if (air_skip(a)) return;
+  const int n = air_n(a);
+  for (int t = (int)(blockIdx.x * kThreads + threadIdx.x); t < n; t += (int)(gridDim.x * kThreads)) {
+    unsigned long long w2, w3;
+    air_load(a, t, w2, w3);
+    int ap, ann, cann;
+    bool rep;
+    air_classify(w2, w3, a.fec != 0, ap, ann, rep, cann);
+    if (ann >= 0) ADSB_AIR_MIN(&a.table[ann], a.pass | (unsigned)t);
+  }
+}
+
+// Step 2 (again = 0): the verdict of every AP reply against the table as steps 1 left it; an unknown one the repair accepts
+// is a candidate of step 3 (kApFec for now, its index listed).  Step 4 (again = 1), only if step 3 had candidates: the
+// verdict of the other AP replies again, now that step 3's announcements are in.  A later pass's announcements racing this
+// verdict cannot change it: their keys exceed every key of this pass, so table[AA] < p holds before them iff after them.
+__global__ void __launch_bounds__(kThreads) k_air_verdict(AirArgs a, int again) {
+  if (a.sum && a.sum->overflow) {
+    if (!again && blockIdx.x == 0 && threadIdx.x == 0) ADSB_AIR_STORE(&a.st->broken, 1);
+    return;
+  }
+  if (!a.force && ADSB_AIR_LOAD(&a.st->broken) != 0) {
+    if (!again && a.host_sum && blockIdx.x == 0 && threadIdx.x == 0) {
+      a.host_sum->flags |= kAirSkipped;
+      __threadfence_system();
+    }
+    return;
+  }
+  if (again && ADSB_AIR_LOAD(&a.st->ncond) == 0) return;
+  const int n = air_n(a);
+  for (int t = (int)(blockIdx.x * kThreads + threadIdx.x); t < n; t += (int)(gridDim.x * kThreads)) {
+    unsigned long long w2, w3;
+    air_load(a, t, w2, w3);
+    int ap, ann, cann;
+    bool rep;
+    air_classify(w2, w3, a.fec != 0, ap, ann, rep, cann);
+    if (ap < 0 || (again && rep)) continue;            // (step 4: the candidates' verdicts are step 3's)
+    const unsigned fl = (unsigned)(w3 >> 48);
+    const bool known = ADSB_AIR_LOAD(&a.table[ap]) < (a.pass | (unsigned)t);
+    unsigned nf = (fl & ~(kApKnown | kApFec)) | (known ? kApKnown : 0u);
+    if (!known && rep) {
+      nf |= kApFec;
+      const int k = atomicAdd(&a.st->ncond, 1);
+      if (k < kAirCondCap) a.st->cond[k] = (unsigned)t;
+    }
+    if (nf != fl) air_set(a, t, w3, nf);
+  }
+}
+
+// Step 3, one wavefront: the candidates in list order.  Each is accepted iff its AA is still unknown at its position --
+// an earlier candidate may have announced it -- and then makes its announcement (cann).  Practically never has work: an
+// AP reply with an unknown AA whose (AA, last bit) is one of the 223 error patterns.  More than kAirCondCap candidates:
+// found by a scan of the list in order instead.
+__global__ void __launch_bounds__(64) k_air_cond(AirArgs a) {
+  if (air_skip(a)) return;
+  const int nc = ADSB_AIR_LOAD(&a.st->ncond);
+  if (nc == 0) return;
+  const int lane = (int)threadIdx.x;
+  auto walk = [&](int t) {
+    unsigned long long w2, w3;
+    air_load(a, t, w2, w3);
+    int ap, ann, cann;
+    bool rep;
+    air_classify(w2, w3, a.fec != 0, ap, ann, rep, cann);
+    const unsigned long long key = a.pass | (unsigned)t;
+    const unsigned fl = (unsigned)(w3 >> 48);
+    if (ADSB_AIR_LOAD(&a.table[ap]) < key) {
+      air_set(a, t, w3, (fl & ~kApFec) | kApKnown);
+    } else if (cann >= 0) {
+      ADSB_AIR_MIN(&a.table[cann], key);
+    }
+  };
+  if (nc <= kAirCondCap) {
+    if (lane == 0) {
+      for (int i = 1; i < nc; ++i)                    // insertion sort: list order
+        for (int k = i; k > 0 && a.st->cond[k - 1] > a.st->cond[k]; --k) {
+          const unsigned x = a.st->cond[k]; a.st->cond[k] = a.st->cond[k - 1]; a.st->cond[k - 1] = x;
+        }
+      for (int i = 0; i < nc; ++i) walk((int)a.st->cond[i]);
+    }
+    return;
+  }
+  const int n = air_n(a);
+  for (int base = 0; base < n; base += 64) {
+    bool cand = false;
+    const int t = base + lane;
+    if (t < n) {
+      unsigned long long w2, w3;
+      air_load(a, t, w2, w3);
+      cand = ((unsigned)(w3 >> 48) & (kDemod | kApFec)) == (kDemod | kApFec);
+    }
+    unsigned long long m = __ballot(cand);
+    if (lane == 0)
+      while (m) {
+        const int i = __builtin_ctzll(m);
+        m &= m - 1;
+        walk(base + i);
+      }
   }
 }
 

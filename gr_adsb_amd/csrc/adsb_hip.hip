@@ -209,6 +209,8 @@ struct Slot {
   bool ev1_valid = false;
   bool h2d_pending = false;      // host-fed submission: the upload's event has to be waited for by the k_detect stream
   int seq = 0;                   // direct passes: the number the kernel stores into h_sum->pad_ when everything is out
+  unsigned long long air_pass = 0;   // ADSB_FLAG_AIRCRAFT_TABLE: this pass's number << 32, kept when the pass is re-run
+  bool air_keep = false;             // ... set while finish() re-runs the pass
   bool polled = false;           // ... and finish() polls for instead of waiting for an event
   Plan plan{};
   DetectArgs args{};
@@ -354,6 +356,11 @@ struct adsb_ctx {
   static constexpr int kHist = 4096;
   std::vector<float> det_hist;
   uint64_t det_hist_n = 0;
+  // ADSB_FLAG_AIRCRAFT_TABLE: 2^24 first-announcement keys, the step state, and the event behind the last table step queued
+  unsigned long long* d_air = nullptr;
+  AirState* d_air_st = nullptr;
+  hipEvent_t air_ev = nullptr;
+  unsigned long long air_next = 0;    // number of the next published pass (table keys: number << 32 | position)
   char err[256] = {0};
 };
 
@@ -564,6 +571,49 @@ void launch_fec(hipStream_t st, const Slot& s, Rec* out, const Summary* sum) {
                      (Rec*)(s.host_cap > 0 ? s.h_out : nullptr), s.host_cap);
 }
 
+// opt-in aircraft table (ADSB_FLAG_AIRCRAFT_TABLE): the table step of one published pass (list: out / mirror / sum; slices:
+// bits14 / ok, n = ntags), in stream order behind every earlier pass's step: the three slots run on their own streams, so
+// the step waits for the event recorded behind the previous one (pass n's verdict needs every announcement of passes < n)
+int launch_air(adsb_ctx* c, hipStream_t st, AirArgs a, long long tot) {
+  HIPCHK(c, hipStreamWaitEvent(st, c->air_ev, 0));
+  long long g = (tot + kThreads - 1) / kThreads;
+  if (g > 2048) g = 2048;
+  if (g < 1) g = 1;
+  a.table = c->d_air; a.st = c->d_air_st; a.fec = (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) ? 1 : 0;
+  hipLaunchKernelGGL(k_air_announce, dim3((unsigned)g), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(k_air_verdict, dim3((unsigned)g), dim3(kThreads), 0, st, a, 0);
+  hipLaunchKernelGGL(k_air_cond, dim3(1), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(k_air_verdict, dim3((unsigned)g), dim3(kThreads), 0, st, a, 1);
+  HIPCHK(c, hipEventRecord(c->air_ev, st));
+  return 0;
+}
+
+int launch_air_pass(adsb_ctx* c, Slot& s, hipStream_t st, Rec* out, int force = 0) {
+  AirArgs a{};
+  a.out = out; a.mirror = (out != (Rec*)s.h_out && s.host_cap > 0) ? (Rec*)s.h_out : nullptr;
+  a.mirror_cap = a.mirror ? s.host_cap : 0;
+  a.sum = &((Misc*)s.d_misc.p)->sum; a.cap = (int)s.tot; a.host_sum = s.h_sum; a.pass = s.air_pass; a.force = force;
+  return launch_air(c, st, a, s.tot);
+}
+
+// the step state's `broken` word cleared behind every table step queued so far (before a pass that overflowed is re-run)
+int air_unbreak(adsb_ctx* c, hipStream_t st) {
+  HIPCHK(c, hipStreamWaitEvent(st, c->air_ev, 0));
+  HIPCHK(c, hipMemsetAsync(&c->d_air_st->broken, 0, sizeof(int), st));
+  HIPCHK(c, hipEventRecord(c->air_ev, st));
+  return 0;
+}
+
+// an empty table (every key all ones) and a fresh step state, behind every table step queued so far; pass numbers restart
+int air_clear(adsb_ctx* c) {
+  if (c->air_next > 0) HIPCHK(c, hipStreamWaitEvent(c->stream, c->air_ev, 0));
+  HIPCHK(c, hipMemsetAsync(c->d_air, 0xFF, ((size_t)1 << 24) * sizeof(unsigned long long), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_air_st, 0, sizeof(AirState), c->stream));
+  HIPCHK(c, hipEventRecord(c->air_ev, c->stream));
+  c->air_next = 0;
+  return 0;
+}
+
 // adsb_wait_for_event: the caller's pending events are waited for by `st`, the stream the next call's first operation runs on
 int apply_ext(adsb_ctx* c, hipStream_t st) {
   for (int i = 0; i < c->n_ext; ++i) HIPCHK(c, hipStreamWaitEvent(st, c->ext_ev[i], 0));
@@ -575,6 +625,8 @@ int apply_ext(adsb_ctx* c, hipStream_t st) {
 int enqueue_tail(adsb_ctx* c, Slot& s) {
   const DetectArgs& a = s.args;
   const Plan& pl = s.plan;
+  if (pl.air && !s.air_keep) s.air_pass = (c->air_next++) << 32;   // publication order = the order passes are queued in
+  s.air_keep = false;
   Misc* misc = (Misc*)s.d_misc.p;
   hipStream_t ts = s.cs;
   if (s.direct) {
@@ -594,9 +646,11 @@ int enqueue_tail(adsb_ctx* c, Slot& s) {
     t.seq = s.seq;
     if (s.fused) launch_pass_small(ts, a, t);
     else ADSB_BY_MODE(pl.mode, launch_tail_small, ts, a, t);
-    if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) {
-      // the repair follows the published pass number: the host waits for the event behind it instead of polling
-      launch_fec(ts, s, (Rec*)s.h_out, &misc->sum);
+    if (c->flags & (ADSB_FLAG_FEC_CONSERVATIVE | ADSB_FLAG_AIRCRAFT_TABLE)) {
+      // the repair / the table step follow the published pass number: the host waits for the event behind them instead
+      // of polling
+      if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) launch_fec(ts, s, (Rec*)s.h_out, &misc->sum);
+      if (pl.air) { int r_ = launch_air_pass(c, s, ts, (Rec*)s.h_out); if (r_) return r_; }
       HIPCHK(c, hipEventRecord(s.done, ts));
       return 0;
     }
@@ -642,6 +696,7 @@ int enqueue_tail(adsb_ctx* c, Slot& s) {
                      &misc->sum, (const int*)s.d_seg.p, fmask, fwant, pl.head_n, (Rec*)(s.direct ? s.h_out : s.d_out.p), (int)s.tot,
                      a.long_count, a.long_lastp, &misc->acc, s.h_sum, (Rec*)(s.host_cap > 0 ? s.h_out : nullptr), s.host_cap);
   if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) launch_fec(ts, s, (Rec*)s.d_out.p, &misc->sum);
+  if (pl.air) { int r_ = launch_air_pass(c, s, ts, (Rec*)s.d_out.p); if (r_) return r_; }
   HIPCHK(c, hipEventRecord(s.done, ts));
   return 0;
 }
@@ -776,6 +831,49 @@ int enqueue(adsb_ctx* c, Slot& s, const Plan& pl, bool submitted) {
 
 // Wait for a queued call; handle the two rare outcomes that need a second pass (pulses longer than the
 // LDS window; per-workgroup list overflow); bring the records to pinned host memory.
+// ADSB_FLAG_AIRCRAFT_TABLE after a centre-list overflow: the overflowed pass skipped its table step and set `broken`, so
+// every step queued behind it skipped too (kAirSkipped in its summary).  Every pass in flight is settled, in publication
+// order: an overflowed one is re-run under its own number (behind a cleared `broken`), a skipped step is re-run.  Nothing
+// is submitted meanwhile, so each verdict again sees exactly the announcements of the passes before it.
+int air_settle_all(adsb_ctx* c) {
+  Slot* order[ADSB_MAX_IN_FLIGHT];
+  int n = 0;
+  for (Slot& sl : c->slot)
+    if (sl.busy && sl.plan.air) {
+      int k = n++;
+      for (; k > 0 && order[k - 1]->air_pass > sl.air_pass; --k) order[k] = order[k - 1];
+      order[k] = &sl;
+    }
+  for (int i = 0; i < n; ++i) {
+    Slot& s = *order[i];
+    for (int attempt = 0;; ++attempt) {
+      if (attempt == 16) return fail(c, -EIO, "centre list capacity did not converge");
+      HIPCHK(c, hipEventSynchronize(s.done));
+      HIPCHK(c, hipGetLastError());
+      const hipStream_t ts = s.direct ? s.ds : s.cs;
+      int r;
+      if (s.h_sum->overflow) {
+        if ((long long)s.rec_cap >= s.chunk / 2 + 8) return fail(c, -EIO, "centre list overflow at maximum size");
+        c->rec_cap_shift++;
+        c->stats.retries++;
+        if ((r = air_unbreak(c, ts))) return r;
+        s.air_keep = true;
+        if ((r = enqueue(c, s, s.plan, s.submitted))) return r;
+        c->stats.calls--;
+        continue;
+      }
+      if (s.h_sum->flags & kAirSkipped) {
+        s.h_sum->flags &= ~kAirSkipped;
+        if ((r = launch_air_pass(c, s, ts, (Rec*)(s.direct ? s.h_out : s.d_out.p), 1))) return r;
+        HIPCHK(c, hipEventRecord(s.done, ts));
+        continue;
+      }
+      break;
+    }
+  }
+  return 0;
+}
+
 int finish(adsb_ctx* c, Slot& s, Summary* sum, int32_t* n_res) {
   // every error exit releases the slot: a failed call must not leave its ticket busy for good
 #define FINCHK(call)                                                           \
@@ -810,6 +908,10 @@ int finish(adsb_ctx* c, Slot& s, Summary* sum, int32_t* n_res) {
     } else {
       FINCHK(hipEventSynchronize(s.done));
       FINCHK(hipGetLastError());
+      if (s.plan.air && (s.h_sum->overflow || (s.h_sum->flags & kAirSkipped))) {
+        int r_ = air_settle_all(c);
+        if (r_) { s.busy = false; return r_; }
+      }
     }
     if (timing) {
       float ms = 0;
@@ -917,6 +1019,7 @@ int canonical(adsb_ctx* c, int mode, const void* d_data, int64_t n, int64_t abs_
   if (((uintptr_t)d_data & 15u) != 0) return fail(c, -EINVAL, "device pointer must be 16-byte aligned");
   Plan pl = plan_canonical(mode, d_data, n, abs_offset, c->sps);
   pl.long_aware = (c->flags & ADSB_FLAG_LONG_AWARE_GATE) != 0;
+  pl.air = (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) != 0;
   Summary s;
   int32_t nres = 0;
   if (n == 0) { c->slot[c->last_slot].nres = 0; if (n_out) *n_out = 0; return 0; }
@@ -1059,16 +1162,32 @@ static uint32_t host_parity_flags(const uint8_t b[14]) {
   return f;
 }
 
-uint32_t adsb_mode_s_fec(const uint8_t in[14], uint8_t out[14], int32_t* first_bit, int32_t* nflip) {
-  // decoder.py:304-323: for burst lengths 1, 2 and every position, key = compute_crc_2 of the pattern; :738-763: the payload's
-  // key looked up, the pattern applied.  compute_crc_2(bits[0:L]) (:716-736) is the L-bit message mod x*G(x) -- 25 bits
+// decoder.py:304-323: for burst lengths 1, 2 and every position, key = compute_crc_2 of the pattern; :738-763: the payload's
+// key looked up.  compute_crc_2(bits[0:L]) (:716-736) is the L-bit message mod x*G(x) -- 25 bits.  Returns whether a pattern
+// matches; *first / *len = the pattern, e = the payload with it applied.
+static bool host_fec_find(const uint8_t b[14], int L, int32_t* first, int32_t* len, uint8_t e[14]) {
   static constexpr CrcTab tab = make_crc_tab();
-  auto key = [](const uint8_t* b, int L) {        // sum over set bits i of x^(L-1-i) mod x*G = x * (x^(L-2-i) mod G), or 1
+  auto key = [](const uint8_t* v, int n) {        // sum over set bits i of x^(n-1-i) mod x*G = x * (x^(n-2-i) mod G), or 1
     uint32_t k = 0;
-    for (int i = 0; i < L; ++i)
-      if ((b[i >> 3] >> (7 - (i & 7))) & 1) k ^= (i == L - 1) ? 1u : (tab.r[L - 2 - i] << 1);
+    for (int i = 0; i < n; ++i)
+      if ((v[i >> 3] >> (7 - (i & 7))) & 1) k ^= (i == n - 1) ? 1u : (tab.r[n - 2 - i] << 1);
     return k;
   };
+  const uint32_t k = key(b, L);
+  for (int w = 1; w <= 2; ++w)
+    for (int i = 0; i + w <= L; ++i) {
+      uint8_t p[14] = {0};
+      for (int q = i; q < i + w; ++q) p[q >> 3] |= (uint8_t)(0x80u >> (q & 7));
+      if (key(p, L) != k) continue;
+      *first = i;
+      *len = w;
+      for (int q = 0; q < 14; ++q) e[q] = (uint8_t)(p[q] ^ b[q]);
+      return true;
+    }
+  return false;
+}
+
+uint32_t adsb_mode_s_fec(const uint8_t in[14], uint8_t out[14], int32_t* first_bit, int32_t* nflip) {
   uint8_t b[14];
   memcpy(b, in, 14);
   if (first_bit) *first_bit = -1;
@@ -1078,24 +1197,63 @@ uint32_t adsb_mode_s_fec(const uint8_t in[14], uint8_t out[14], int32_t* first_b
   if (out) memcpy(out, b, 14);
   if (!((1u << df) & kDfPiSet) || (flags & ADSB_BURST_PARITY_OK)) return flags;
   const int L = (flags & ADSB_BURST_LONG) ? 112 : 56;
-  const uint32_t k = key(b, L);
-  for (int len = 1; len <= 2; ++len)
-    for (int i = 0; i + len <= L; ++i) {
-      uint8_t e[14] = {0};
-      for (int q = i; q < i + len; ++q) e[q >> 3] |= (uint8_t)(0x80u >> (q & 7));
-      if (key(e, L) != k) continue;
-      if (first_bit) *first_bit = i;
-      if (nflip) *nflip = len;
-      for (int q = 0; q < 14; ++q) e[q] ^= b[q];
-      const uint32_t f2 = host_parity_flags(e);
-      const unsigned df2 = e[0] >> 3;
-      if (((1u << df2) & kDfPiSet) && ((f2 & ADSB_BURST_LONG) == (flags & ADSB_BURST_LONG))) {
-        if (out) memcpy(out, e, 14);
-        return f2 | ADSB_BURST_FEC_FIXED;
-      }
-      return flags | ADSB_BURST_FEC_DF;
+  int32_t i = 0, len = 0;
+  uint8_t e[14];
+  if (!host_fec_find(b, L, &i, &len, e)) return flags;
+  if (first_bit) *first_bit = i;
+  if (nflip) *nflip = len;
+  const uint32_t f2 = host_parity_flags(e);
+  const unsigned df2 = e[0] >> 3;
+  if (((1u << df2) & kDfPiSet) && ((f2 & ADSB_BURST_LONG) == (flags & ADSB_BURST_LONG))) {
+    if (out) memcpy(out, e, 14);
+    return f2 | ADSB_BURST_FEC_FIXED;
+  }
+  return flags | ADSB_BURST_FEC_DF;
+}
+
+// decode_message / decode_me (decoder.py:883-947,1065-1232) as far as they reach update_plane for a reply that passed:
+// the address it announces, or -1
+static int32_t host_announce(const uint8_t b[14]) {
+  auto field = [&](int lo, int n) {
+    uint32_t v = 0;
+    for (int i = lo; i < lo + n; ++i) v = (v << 1) | ((b[i >> 3] >> (7 - (i & 7))) & 1u);
+    return v;
+  };
+  const uint32_t df = field(0, 5), sub = field(5, 3), tc = field(32, 5), st = field(37, 3);
+  const int32_t aa = (int32_t)field(8, 24);
+  if (df == 11) return aa;                                                     // :883-893
+  if (df == 17 || (df == 18 && (sub == 0 || sub == 1 || sub == 6)) || (df == 19 && sub == 0)) {   // :896-947 -> decode_me
+    if ((tc >= 1 && tc <= 4) || (tc >= 9 && tc <= 18)) return aa;            // :1075-1088, :1100-1112
+    if (tc == 19 && (st == 1 || st == 2)) return aa;                           // :1141-1232
+  }
+  return -1;
+}
+
+uint32_t adsb_mode_s_aircraft(const uint8_t bits[14], int32_t fec, int32_t* aa_out, int32_t* announce, int32_t* fec_announce) {
+  int32_t aa = -1, ann = -1, fann = -1;
+  uint32_t ret = 0;
+  int32_t df = 0, nbits = 0;
+  const uint32_t syn = adsb_mode_s_syndrome(bits, &df, &nbits);
+  const uint32_t ap_set = (1u << 0) | (1u << 4) | (1u << 5) | (1u << 16) | (1u << 20) | (1u << 21) | (1u << 24);
+  int32_t i = 0, len = 0;
+  uint8_t e[14];
+  if ((1u << df) & ap_set) {
+    // check_parity (:576-601, :636-665): AA = crc ^ AP = the syndrome; unknown: correct_burst_errors on the raw reply,
+    // keyed by (AA, last bit); decode_message then runs on the repaired bits with self.aa_str of check_parity
+    aa = (int32_t)syn;
+    if (fec && host_fec_find(bits, nbits, &i, &len, e)) {
+      ret = ADSB_BURST_AP_FEC;
+      const uint32_t df2 = e[0] >> 3;
+      fann = (((1u << df2) & ap_set) && df2 != 24) ? aa : host_announce(e);
     }
-  return flags;
+  } else if ((1u << df) & kDfPiSet) {
+    if (syn == 0) ann = host_announce(bits);
+    else if (fec && host_fec_find(bits, nbits, &i, &len, e)) ann = host_announce(e);   // the decoder's own repair
+  }
+  if (aa_out) *aa_out = aa;
+  if (announce) *announce = ann;
+  if (fec_announce) *fec_announce = fann;
+  return ret;
 }
 
 float adsb_snr_db(float peak, float median) {
@@ -1155,6 +1313,11 @@ int adsb_create(double fs, float threshold, int device, uint32_t flags, adsb_ctx
   }
   c->stream = c->slot[0].stream;         // blocking calls always run in slot 0 (run_pipeline)
   if (hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking) != hipSuccess) { adsb_destroy(c); return -EIO; }
+  if (flags & ADSB_FLAG_AIRCRAFT_TABLE) {
+    if (hipMalloc((void**)&c->d_air, ((size_t)1 << 24) * sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc((void**)&c->d_air_st, sizeof(AirState)) != hipSuccess) { (void)hipGetLastError(); adsb_destroy(c); return -ENOMEM; }
+    if (hipEventCreateWithFlags(&c->air_ev, hipEventDisableTiming) != hipSuccess || air_clear(c) != 0) { adsb_destroy(c); return -EIO; }
+  }
   *out = c;
   return 0;
 }
@@ -1184,6 +1347,10 @@ void adsb_destroy(adsb_ctx* c) {
     if (sl.det_done) (void)hipEventDestroy(sl.det_done);
     if (sl.stream) (void)hipStreamDestroy(sl.stream);
   }
+  if (c->air_ev) (void)hipEventSynchronize(c->air_ev);
+  if (c->d_air) (void)hipFree(c->d_air);
+  if (c->d_air_st) (void)hipFree(c->d_air_st);
+  if (c->air_ev) (void)hipEventDestroy(c->air_ev);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->h_dm) (void)hipHostFree(c->h_dm);
   for (void* r : c->h_ring) if (r) (void)hipHostFree(r);
@@ -1269,6 +1436,12 @@ int adsb_clear_pending_events(adsb_ctx* c) {
 
 int adsb_reset(adsb_ctx* c) {
   if (!c) return -EINVAL;
+  if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) {
+    for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = air_clear(c);
+    if (r) return r;
+  }
   c->st = FramerState();
   c->n_ext = 0;           // a fresh stream starts without remembered producers
   return 0;
@@ -1363,6 +1536,7 @@ static int submit_canonical(adsb_ctx* c, int mode, const void* d_data, int64_t n
   if (s.busy) return fail(c, -EBUSY, "every pipeline slot is in flight (adsb_wait first)");
   Plan pl = plan_canonical(mode, d_data, n, abs_offset, c->sps);
   pl.long_aware = (c->flags & ADSB_FLAG_LONG_AWARE_GATE) != 0;
+  pl.air = (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) != 0;
   int r = enqueue(c, s, pl, true);
   if (r) { s.busy = false; return r; }
   s.is_shard = false;
@@ -1488,6 +1662,8 @@ int adsb_demod_work(adsb_ctx* c, const float* in0, int64_t n, int64_t nitems_rea
                     int32_t ntags, uint8_t* bits112, uint8_t* ok, float* ratio) {
   if (!c || n < 0 || ntags < 0 || (n > 0 && !in0) || (ntags > 0 && (!tag_offsets || !bits112 || !ok))) return -EINVAL;
   if (ntags == 0) return 0;
+  if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE)      // (the table steps of passes in flight may still be settled: finish)
+    for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
   HIPCHK(c, hipSetDevice(c->device));
   // (independent of submitted calls still in flight: own buffers, ordered behind them on the compute stream)
   // Tag positions, packed bits, ok flags and ratios live in the context's pinned, device-visible scratch (layout: tag
@@ -1515,6 +1691,13 @@ int adsb_demod_work(adsb_ctx* c, const float* in0, int64_t n, int64_t nitems_rea
     const int fb = (int)((nt + kThreads - 1) / kThreads < 2048 ? (nt + kThreads - 1) / kThreads : 2048);
     hipLaunchKernelGGL(k_fec_slices, dim3(fb), dim3(kThreads), 0, c->stream, (unsigned char*)(h + o_bits),
                        (unsigned char*)(h + o_ok), (int)ntags);
+  }
+  if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) {
+    // the slices with ok != 0 are this call's published PDUs, in tag order
+    AirArgs aa{};
+    aa.bits14 = (unsigned char*)(h + o_bits); aa.ok = (unsigned char*)(h + o_ok); aa.cap = (int)ntags;
+    aa.pass = (c->air_next++) << 32;
+    if ((rc = launch_air(c, c->stream, aa, (long long)ntags))) { (void)hipStreamSynchronize(c->stream); return rc; }
   }
   hipError_t he = hipStreamSynchronize(c->stream);            // always: nothing stays queued behind an error return
   if (he == hipSuccess) he = hipGetLastError();
@@ -1566,6 +1749,7 @@ static int shard_post(adsb_ctx* c, Slot& s, const Summary& sum, int32_t* nres_io
 static int shard_plan_checked(adsb_ctx* c, int fmt, const void* d_data, int64_t n, int64_t origin, int64_t own_lo,
                               int64_t own_hi, int64_t stream_len, int32_t head_cands, Plan* pl) {
   if (!c || n < 0 || fmt < 0 || fmt >= ADSB_FMT_COUNT || head_cands < 0) return -EINVAL;
+  if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) return fail(c, -EINVAL, "sharded calls are not for ADSB_FLAG_AIRCRAFT_TABLE contexts");
   if (((uintptr_t)d_data & 15u) != 0) return fail(c, -EINVAL, "device pointer must be 16-byte aligned");
   *pl = plan_shard(fmt, d_data, n, origin, own_lo, own_hi, stream_len, c->sps, head_cands);
   pl->long_aware = (c->flags & ADSB_FLAG_LONG_AWARE_GATE) != 0;
@@ -1591,6 +1775,7 @@ int adsb_shard_host(adsb_ctx* c, int fmt, const void* host, int64_t n, int64_t o
                     int64_t stream_len, int32_t head_cands, uint32_t shard_flags, adsb_burst* out, int32_t cap,
                     int32_t* n_out) {
   if (!c || fmt < 0 || fmt >= ADSB_FMT_COUNT || n < 1 || !host) return -EINVAL;
+  if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) return fail(c, -EINVAL, "sharded calls are not for ADSB_FLAG_AIRCRAFT_TABLE contexts");
   HIPCHK(c, hipSetDevice(c->device));
   void* d = nullptr;
   int rc = upload(c, host, (size_t)n * (size_t)mode_bytes(fmt), &d);
@@ -1660,6 +1845,7 @@ static int32_t gate_from(adsb_burst* recs, int32_t n, int sps, long long* eob_io
 int adsb_process_sharded_device(adsb_ctx* c, int fmt, const void* d_data, int64_t n, int64_t abs_offset, int32_t shards,
                                 adsb_burst* out, int32_t cap, int32_t* n_out) {
   if (!c || fmt < 0 || fmt >= ADSB_FMT_COUNT || n < 0 || shards < 1 || cap < 0 || (cap > 0 && !out) || !n_out) return -EINVAL;
+  if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) return fail(c, -EINVAL, "sharded calls are not for ADSB_FLAG_AIRCRAFT_TABLE contexts");
   if (((uintptr_t)d_data & 15u) != 0) return fail(c, -EINVAL, "device pointer must be 16-byte aligned");
   for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
   // the rows of adsb_last_confidence belong to the records of ONE pass in the order that pass delivered them; this driver
@@ -1818,6 +2004,7 @@ int adsb_process_sharded_multi(adsb_ctx* const* ctxs, int32_t n_ctx, int fmt, co
     adsb_ctx* c = ctxs[k];
     if (!c) return -EINVAL;
     for (int j = 0; j < k; ++j) if (ctxs[j] == c) return fail(c0, -EINVAL, "adsb_process_sharded_multi: a context listed twice");
+    if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) return fail(c0, -EINVAL, "sharded calls are not for ADSB_FLAG_AIRCRAFT_TABLE contexts");
     // one stream, one set of rules: every context must have been created with the same rate, threshold, gate and scale
     if (c->sps != c0->sps || !(c->thr == c0->thr) || ((c->flags ^ c0->flags) & (ADSB_FLAG_LONG_AWARE_GATE | ADSB_FLAG_FEC_CONSERVATIVE)) ||
         !(c->scale[fmt] == c0->scale[fmt]))

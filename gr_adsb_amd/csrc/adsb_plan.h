@@ -23,6 +23,7 @@ struct Plan {
   bool gate;                // apply framer.py:121-123 on the device
   int head_n = 0;           // shard mode: deliver the first head_n centres whether gated or not
   bool long_aware = false;  // opt-in length-aware gate (never in GNU Radio emulation): set by the caller from the context
+  bool air = false;         // ADSB_FLAG_AIRCRAFT_TABLE: the pass is published, its records get the table step (canonical calls)
 };
 
 // How a pass over `ntiles` tiles (1024 samples each) is cut into chunks, one per wavefront, for a device that keeps

@@ -95,6 +95,19 @@ extern "C" {
  * every entry point that returns records applies it, and adsb_demod_work applies it to its slices.  Without the flag nothing
  * is launched and no byte changes.  Confidence ratios stay those of the raw slice (demod.py:101). */
 #define ADSB_FLAG_FEC_CONSERVATIVE 128u
+/* Opt-in: the decoder's aircraft table (plane_dict, decoder.py:576-665) on the device, so that address/parity (AP) replies --
+ * DF 0/4/5/16/20/21/24, accepted by the decoder only when AA = crc(bits[0:L-24]) ^ bits[L-24:L] is an address it has heard --
+ * get a verdict too.  The table models one decoder (msg_filter="All Messages", error_corr "None", or "Conservative" with
+ * ADSB_FLAG_FEC_CONSERVATIVE) that consumes the context's published PDUs in publication order: call order, adsb_submit_*
+ * in submission order (not wait order), within a call the delivered records with ADSB_BURST_DEMOD (adsb_demod_work: the
+ * slices with ok != 0) in order.  Every such record that the decoder would accept and that reaches update_plane announces
+ * its address (adsb_mode_s_aircraft states the per-PDU rule); an AP reply is flagged ADSB_BURST_AP_KNOWN when its AA was
+ * announced earlier.  The table lives as long as the context (128 MiB of device memory, allocated only with the flag):
+ * adsb_reset clears it; addresses never time out, as in the decoder.  Applies to adsb_process_*, adsb_submit_* and
+ * adsb_demod_work; adsb_framer_work ignores it (its records are not what is published); the sharded entry points
+ * (adsb_shard_*, adsb_submit_shard_device, adsb_process_sharded_*) return -EINVAL: their stitch decides publication after
+ * the device has run.  Without the flag nothing is allocated or launched and no byte changes. */
+#define ADSB_FLAG_AIRCRAFT_TABLE 256u
 
 /* adsb_burst.flags */
 #define ADSB_BURST_DEMOD 1u /* eob inside the demod input: bits[] valid, a PDU is published (demod.py:82) */
@@ -104,7 +117,8 @@ extern "C" {
  * what the decoder's first two steps (decoder.py:550-556 decode_header, :560-688 check_parity) will find,
  * so a consumer can drop garbage PDUs before they reach the (scalar, per-message) decoder.  Advisory: the
  * bits and every other field are unchanged, and the reference-compatible blocks publish all PDUs. */
-#define ADSB_BURST_PARITY_OK 32u /* DF 11/17/18/19 and crc(bits[0:L-24]) == bits[L-24:L] (decoder.py:625,679) */
+#define ADSB_BURST_PARITY_OK 32u /* DF 11/17/18/19 and crc(bits[0:L-24]) == bits[L-24:L] (decoder.py:625,679); the
+                                    address/parity formats' verdict needs an aircraft table: ADSB_FLAG_AIRCRAFT_TABLE */
 #define ADSB_BURST_LONG 64u      /* DF 16-21/24: 112-bit reply (decoder.py:636,669); else the 56-bit reading */
 #define ADSB_BURST_KNOWN_DF 128u /* DF is one check_parity() handles: 0,4,5,11,16,17,18,19,20,21,24 */
 #define ADSB_BURST_DF_SHIFT 8    /* (flags >> 8) & 31 = downlink format (decoder.py:551) */
@@ -113,6 +127,10 @@ extern "C" {
 /* ADSB_FLAG_FEC_CONSERVATIVE contexts only (kDemod records of DF 11/17/18/19 that failed parity): */
 #define ADSB_BURST_FEC_FIXED 0x4000u /* a 1-bit / 2-adjacent-bit error was repaired: bits[] and the pre-filter bits are the repaired reply's */
 #define ADSB_BURST_FEC_DF 0x8000u    /* the decoder's repair would change the DF (or its length): bits[] left raw */
+/* ADSB_FLAG_AIRCRAFT_TABLE contexts only (ADSB_BURST_DEMOD records of DF 0/4/5/16/20/21/24); the two values are never
+ * set on a delivered record otherwise.  adsb_demod_work's ok[]: bit 3 (8) = AP_KNOWN, bit 4 (16) = AP_FEC. */
+#define ADSB_BURST_AP_FEC 0x0004u    /* with ADSB_FLAG_FEC_CONSERVATIVE: AA unknown, but the decoder's repair accepts the reply (bits[] stay raw) */
+#define ADSB_BURST_AP_KNOWN 0x0008u  /* AA was announced by an earlier published reply: the decoder accepts it */
 
 typedef struct adsb_ctx adsb_ctx;
 
@@ -281,7 +299,9 @@ int adsb_framer_work_passthrough(adsb_ctx* ctx, const float* in0, int64_t n_in0,
  * nitems_read+n).  bits112: ntags*112 bytes of 0/1 (the u8vector the PDU carries); ok[t] != 0 when the
  * burst was demodulated, 0 when it straddles the end of the chunk and is dropped (demod.py:82,130-133);
  * a non-zero ok[t] is ADSB_BURST_DEMOD | the pre-filter bits ADSB_BURST_PARITY_OK / _LONG / _KNOWN_DF, and on an
- * ADSB_FLAG_FEC_CONSERVATIVE context ADSB_BURST_FEC_FIXED >> 13 (2) / ADSB_BURST_FEC_DF >> 13 (4), with bits112 repaired.
+ * ADSB_FLAG_FEC_CONSERVATIVE context ADSB_BURST_FEC_FIXED >> 13 (2) / ADSB_BURST_FEC_DF >> 13 (4), with bits112 repaired; on an
+ * ADSB_FLAG_AIRCRAFT_TABLE context ADSB_BURST_AP_KNOWN (8) / ADSB_BURST_AP_FEC << 2 (16), the slices with ok != 0 being
+ * the call's published PDUs, in tag order.
  * ratio (optional, may be NULL): ntags*112 floats bit1_amp/bit0_amp; 10*log10 of it is
  * demod.bit_confidence (demod.py:101). */
 int adsb_demod_work(adsb_ctx* ctx, const float* in0, int64_t n, int64_t nitems_read,
@@ -390,6 +410,16 @@ uint32_t adsb_mode_s_syndrome(const uint8_t bits[14], int32_t* df, int32_t* nbit
  * payload when FEC_FIXED, else a copy of in (in and out may be the same array).  *first_bit / *nflip = the table's pattern
  * (bits first_bit .. first_bit+nflip-1) on a hit, FEC_DF included; -1 / 0 without one.  Out pointers may be NULL. */
 uint32_t adsb_mode_s_fec(const uint8_t in[14], uint8_t out[14], int32_t* first_bit, int32_t* nflip);
+
+/* The per-PDU rule of ADSB_FLAG_AIRCRAFT_TABLE for one 14-byte payload of a demodulated burst, as plain host arithmetic
+ * (fec != 0: the context also has ADSB_FLAG_FEC_CONSERVATIVE).  *aa = the AA of an AP-format reply, else -1.  *announce = the
+ * address the reply announces whatever the table holds (DF 11, and DF 17 / 18 with CF 0,1,6 / 19 with AF 0 of TC 1-4, 9-18
+ * or 19 with ST 1,2, after the parity check and, with fec, the decoder's repair), else -1.  Returns ADSB_BURST_AP_FEC when
+ * fec and an AP reply whose AA is unknown would be accepted by the decoder's repair (its (AA, last bit) is one of the error
+ * patterns); *fec_announce = what that reply then announces -- the pre-repair AA when the repaired DF is 0/4/5/16/20/21,
+ * the repaired reply's address by the rule above when it became DF 11/17/18/19, -1 otherwise (or without the repair).
+ * Out pointers may be NULL. */
+uint32_t adsb_mode_s_aircraft(const uint8_t bits[14], int32_t fec, int32_t* aa, int32_t* announce, int32_t* fec_announce);
 
 /* How one call over n_samples is cut on a device that keeps `resident_wavefronts` wavefronts of the streaming kernel
  * resident (adsb_stats.detect_grid / blocks_per_cu tell what a context uses: CUs x blocks_per_cu x 4, or x 1 for the 8-bit formats): *units chunks of
