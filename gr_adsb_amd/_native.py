@@ -24,6 +24,16 @@ FLAG_NO_NUMA_BINDING = 64 # host side not placed on the GPU's NUMA node (default
 FLAG_LOW_LATENCY = 16     # the tail of a pass runs beside the next pass's k_detect: results a pass earlier, 1-2 % less throughput
 FLAG_FEC_CONSERVATIVE = 128  # opt-in: the decoder's "Conservative" 1-2-bit burst repair on the device (decoder.py:738-780)
 FLAG_AIRCRAFT_TABLE = 256    # opt-in: the decoder's aircraft table on the device: verdicts for address/parity replies
+FLAG_DECODE = 512            # opt-in (with FLAG_AIRCRAFT_TABLE): the decoder's message decoding and plane fields on the device
+# include/adsb_hip.h adsb_decoded: one row per delivered record of a FLAG_DECODE context
+DECODED_DTYPE = np.dtype([("port", "u1"), ("df", "u1"), ("present", "u1"), ("pad0", "u1"), ("icao", "<i4"), ("bits", "u1", (14,)),
+                          ("callsign", "S8"), ("pad1", "u1", (2,)), ("altitude", "<i4"), ("velocity_we", "<i4"),
+                          ("velocity_sn", "<i4"), ("vertical_rate", "<i4"), ("latitude", "<f8"), ("longitude", "<f8"),
+                          ("num_msgs", "<u4"), ("pad2", "<u4")])
+assert DECODED_DTYPE.itemsize == 72
+DEC_NONE, DEC_DECODED, DEC_UNKNOWN, DEC_RAISED = 0, 1, 2, 3
+DEC_HAS_PLANE, DEC_HAS_CALLSIGN, DEC_HAS_ALTITUDE, DEC_HAS_VELOCITY = 1, 2, 4, 8
+DEC_MSG_FILTERS = {"All Messages": 0, "Extended Squitter Only": 1}
 ABI_VERSION = 5
 # input sample formats (include/adsb_hip.h ADSB_FMT_*): numpy dtype of the flat host array, items per sample
 FMT_FC32, FMT_MAG2, FMT_SC16, FMT_SC8, FMT_CU8 = 0, 1, 2, 3, 4
@@ -49,7 +59,7 @@ EXPORTS = [
     "adsb_submit_iq_device", "adsb_submit_mag2_device", "adsb_submit_iq16_device", "adsb_submit_shard_device", "adsb_wait",
     "adsb_set_iq16_scale", "adsb_process_iq16", "adsb_process_iq16_device",
     "adsb_set_format_scale", "adsb_process_format", "adsb_process_format_device", "adsb_submit_format_device",
-    "adsb_submit_format_host", "adsb_last_confidence",
+    "adsb_submit_format_host", "adsb_last_confidence", "adsb_set_decoder", "adsb_last_decoded", "adsb_decode_pdus",
     "adsb_framer_work", "adsb_framer_work_passthrough", "adsb_demod_work", "adsb_shard_bounds", "adsb_process_sharded_device", "adsb_shard_device", "adsb_shard_host", "adsb_shard_fixup", "adsb_stitch", "adsb_snr_db", "adsb_mode_s_syndrome", "adsb_mode_s_fec", "adsb_mode_s_aircraft", "adsb_plan_chunks", "adsb_get_stats",
     "adsb_process_sharded_multi", "adsb_device_alloc", "adsb_device_free", "adsb_device_upload", "adsb_clear_pending_events",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
@@ -125,6 +135,9 @@ def load():
     lib.adsb_submit_format_device.argtypes = [vp, c.c_int, vp, i64, i64, c.POINTER(i32)]
     lib.adsb_submit_format_host.argtypes = [vp, c.c_int, vp, i64, i64, c.POINTER(i32)]
     lib.adsb_last_confidence.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
+    lib.adsb_set_decoder.argtypes = [vp, i32, c.c_double]
+    lib.adsb_last_decoded.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
+    lib.adsb_decode_pdus.argtypes = [vp, vp, vp, i32, vp]
     lib.adsb_last_result.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
     lib.adsb_submit_iq_device.argtypes = [vp, vp, i64, i64, c.POINTER(i32)]
     lib.adsb_submit_mag2_device.argtypes = [vp, vp, i64, i64, c.POINTER(i32)]
@@ -241,6 +254,32 @@ class Context:
         buf = (ctypes.c_char * (n.value * 112 * 4)).from_address(p.value)
         v = np.frombuffer(buf, dtype=np.float32).reshape(n.value, 112)
         return v.copy() if copy else v
+
+    def set_decoder(self, msg_filter="All Messages", start_timestamp=0.0):
+        """FLAG_DECODE contexts: the decoder's msg_filter and the start timestamp of the records' PDUs (adsb_set_decoder)."""
+        self._chk(self.lib.adsb_set_decoder(self._h, DEC_MSG_FILTERS[msg_filter], float(start_timestamp)))
+
+    def last_decoded(self, copy=True):
+        """FLAG_DECODE contexts: DECODED_DTYPE rows of the last finished call's records (adsb_last_decoded)."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int32(0)
+        self._chk(self.lib.adsb_last_decoded(self._h, ctypes.byref(p), ctypes.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=DECODED_DTYPE)
+        buf = (ctypes.c_char * (n.value * DECODED_DTYPE.itemsize)).from_address(p.value)
+        v = np.frombuffer(buf, dtype=DECODED_DTYPE)
+        return v.copy() if copy else v
+
+    def decode_pdus(self, bits14, timestamps):
+        """FLAG_DECODE contexts: decode already-published PDUs (n x 14 packed bytes, n float64 timestamps) through the context's
+        decoder state, in one device call (adsb_decode_pdus) -> DECODED_DTYPE rows."""
+        b = np.ascontiguousarray(bits14, dtype=np.uint8).reshape(-1, 14)
+        t = np.ascontiguousarray(timestamps, dtype=np.float64).reshape(-1)
+        assert len(b) == len(t)
+        rows = np.zeros(len(b), dtype=DECODED_DTYPE)
+        self._chk(self.lib.adsb_decode_pdus(self._h, b.ctypes.data_as(ctypes.c_void_p), t.ctypes.data_as(ctypes.c_void_p),
+                                            len(b), rows.ctypes.data_as(ctypes.c_void_p)))
+        return rows
 
     def submit_format_host(self, fmt, data, abs_offset=0):
         """Host-fed pipelined submission (adsb_submit_format_host): data = host array in the format's layout; a
@@ -726,3 +765,39 @@ def snr_db(peak, median):
         p = np.asarray(peak, dtype=np.float32)
         m = np.asarray(median, dtype=np.float32)
         return (np.float32(10.0) * np.log10(p / m) + np.float32(1.6)).astype(np.float32)
+
+
+def decoded_pdu(row, meta):
+    """One adsb_decoded row plus the incoming PDU's meta ({"timestamp", "snr", ...}) -> what the reference decoder publishes
+    for it: ("decoded" | "unknown", (meta dict, u8vector of 112 bits)), or None when it publishes nothing (a raising PDU
+    included).  Fields, types and key order as decoder.py:512-538 builds them: speed and heading from the integer velocity
+    components with NumPy's sqrt and arctan2 (:1190-1191), NaN where the plane has no value, datetime from the timestamp."""
+    import datetime
+    port = int(row["port"])
+    if port not in (DEC_DECODED, DEC_UNKNOWN):
+        return None
+    ts = meta["timestamp"]
+    dt = datetime.datetime.utcfromtimestamp(ts).strftime("%Y-%m-%d %H:%M:%S.%f UTC")
+    vec = unpack_bits(np.asarray(row["bits"], dtype=np.uint8)).reshape(112)
+    if port == DEC_UNKNOWN:
+        return "unknown", ({"timestamp": ts, "datetime": dt, "df": int(row["df"]), "snr": meta["snr"]}, vec)
+    pr = int(row["present"])
+    nan = float("nan")
+    d = {"callsign": bytes(row["callsign"]).rstrip(b"\0").decode() if pr & DEC_HAS_CALLSIGN else None,
+         "altitude": int(row["altitude"]) if pr & DEC_HAS_ALTITUDE else nan}
+    if pr & DEC_HAS_VELOCITY:
+        vwe, vsn = int(row["velocity_we"]), int(row["velocity_sn"])
+        d["speed"] = np.sqrt(vsn**2 + vwe**2)
+        d["heading"] = np.arctan2(vsn, vwe) * 360.0 / (2.0 * np.pi)
+        d["vertical_rate"] = int(row["vertical_rate"])
+    else:
+        d["speed"] = d["heading"] = d["vertical_rate"] = nan
+    d["latitude"] = float(row["latitude"])
+    d["longitude"] = float(row["longitude"])
+    d["num_msgs"] = int(row["num_msgs"])
+    d["timestamp"] = ts
+    d["datetime"] = dt
+    d["icao"] = "{:06x}".format(int(row["icao"]))
+    d["df"] = int(row["df"])
+    d["snr"] = meta["snr"]
+    return "decoded", (d, vec)

@@ -587,3 +587,63 @@ class demod(gr.sync_block):
             self._carry_pos = keep_from
         else:
             self._carry = np.zeros(0, dtype=np.float32)
+
+
+class decoder(gr.sync_block):
+    """The reference decoder's block surface (python/adsb/decoder.py: name "ADS-B Decoder", message input "demodulated",
+    outputs "decoded" and "unknown") over the device step of FLAG_DECODE: parity, Conservative repair, the aircraft table,
+    callsigns, altitudes, velocities and the CPR global decode run on the GPU; each row is turned into the reference's PDU
+    on the host (_native.decoded_pdu: speed and heading with NumPy, the dict's types and key order).  The decoder's clock
+    is the PDU's own timestamp (now = int(meta["timestamp"]), include/adsb_hip.h ADSB_FLAG_DECODE): the reference reads
+    int(time.time()), the same when it decodes in real time with zero latency.
+
+    A PDU on which the reference raises (DF 18 CF 2/3/5, TC 19 ST 0/5/6/7: decode_packet raises before it publishes) is
+    counted in `self.raised` and publishes nothing.  print_level: any value is accepted, nothing is printed (the curses
+    table and the log lines are not reproduced).  error_corr "Brute Force" behaves as "None", like the reference's branch."""
+
+    def __init__(self, msg_filter, error_corr, print_level="None", device=0):
+        if error_corr not in _ERROR_CORR:
+            raise ValueError("error_corr must be one of %s, not %r" % (", ".join(_ERROR_CORR), error_corr))
+        if msg_filter not in _MSG_FILTER:
+            raise ValueError("msg_filter must be one of %s, not %r" % (", ".join(_MSG_FILTER), msg_filter))
+        gr.sync_block.__init__(self, name="ADS-B Decoder", in_sig=None, out_sig=None)
+        self.msg_filter, self.error_corr, self.print_level = msg_filter, error_corr, print_level
+        self.raised = 0
+        fl = _native.FLAG_AIRCRAFT_TABLE | _native.FLAG_DECODE
+        if error_corr == "Conservative":
+            fl |= _native.FLAG_FEC_CONSERVATIVE
+        # any valid rate: the context only decodes PDUs that were published already (adsb_decode_pdus)
+        self._ctx = _native.Context(2e6, 0.0, device=device, flags=fl)
+        self._ctx.set_decoder(msg_filter, 0.0)
+        self._in, self._dec, self._unk = pmt.to_pmt("demodulated"), pmt.to_pmt("decoded"), pmt.to_pmt("unknown")
+        self.message_port_register_in(self._in)
+        self.message_port_register_out(self._dec)
+        self.message_port_register_out(self._unk)
+        self.set_msg_handler(self._in, self.decode_packet)
+
+    def decode_packet(self, pdu):
+        self.decode_pdus([pdu])
+
+    def decode_pdus(self, pdus):
+        """Several PDUs (meta . u8vector of 112 bits) in one device call, published in order."""
+        if not pdus:
+            return
+        metas = [pmt.to_python(pmt.car(p)) for p in pdus]
+        bits = np.array([np.packbits(np.asarray(pmt.to_python(pmt.cdr(p)), dtype=np.uint8)[:112]) for p in pdus], dtype=np.uint8)
+        rows = self._ctx.decode_pdus(bits, np.array([m["timestamp"] for m in metas], dtype=np.float64))
+        for row, meta in zip(rows, metas):
+            if row["port"] == _native.DEC_RAISED:
+                self.raised += 1
+                continue
+            out = _native.decoded_pdu(row, meta)
+            if out is not None:
+                port, (d, vec) = out
+                self.message_port_pub(self._dec if port == "decoded" else self._unk, pmt.cons(pmt.to_pmt(d), pmt.to_pmt(vec)))
+
+    def reset(self):
+        """Forget every plane (adsb_reset)."""
+        self._ctx.reset()
+
+    def stop(self):
+        self._ctx.close()
+        return True

@@ -2394,4 +2394,294 @@ __global__ void __launch_bounds__(64) k_air_cond(AirArgs a) {
   }
 }
 
+// ---- opt-in decode (ADSB_FLAG_DECODE): the decoder's message decoding and plane_dict fields -----------------------------
+// The rest of decode_packet for the PDUs the table step has just judged, in publication order: decode_message / decode_me
+// (decoder.py:883-1301), update_plane (:413-440) and the CPR global decode (:1309-1512), one decoder (msg_filter of the
+// context, error_corr "Conservative" iff ADSB_FLAG_FEC_CONSERVATIVE) whose clock is the PDU's own timestamp:
+// now = (long long)timestamp, Python's int() (include/adsb_hip.h ADSB_FLAG_DECODE).  Three stages behind k_air_verdict, with
+// its skip rules: k_dec_classify (one thread per record: its row at once when it touches no plane, else a key address << 32 |
+// position), a sort of the keys (adsb_hip.hip: rocPRIM; the emulator sorts on the host), k_dec_fold (one lane per address
+// segment, in list order).
+constexpr unsigned kDecNone = 0, kDecDecoded = 1, kDecUnknown = 2, kDecRaised = 3;     // adsb_decoded.port
+constexpr unsigned kHasPlane = 1, kHasCallsign = 2, kHasAltitude = 4, kHasVelocity = 8;  // adsb_decoded.present
+constexpr unsigned kHasEven = 16, kHasOdd = 32;                                           // Plane.present only
+constexpr unsigned long long kDecNoKey = ~0ull;   // sorts last: its bits 32..59 exceed every address
+// one row per delivered record: include/adsb_hip.h adsb_decoded, byte for byte
+struct DecRow {
+  unsigned char port, df, present, pad0;
+  int icao;
+  unsigned char bits[14];
+  char callsign[8];
+  unsigned char pad1[2];
+  int altitude, velocity_we, velocity_sn, vertical_rate;
+  double latitude, longitude;
+  unsigned num_msgs, pad2;
+};
+static_assert(sizeof(DecRow) == 72, "adsb_decoded is 72 bytes");
+// plane_dict[address] without last_seen (never read back): one dense entry per 24-bit address, valid iff epoch matches
+// (named fields, no arrays: the fold keeps an entry in registers)
+struct Plane {
+  unsigned epoch, num_msgs, present;
+  int altitude;
+  unsigned long long callsign;   // 8 characters, the first in the low byte, NUL padded
+  int vwe, vsn, vr;
+  int cpr_lat0, cpr_lon0, cpr_lat1, cpr_lon1;   // the even (0) and the odd (1) frame
+  int pad;
+  long long cpr_t0, cpr_t1;
+  double lat, lon;
+};
+static_assert(sizeof(Plane) == 88, "88 bytes per address");
+struct DecArgs {
+  AirArgs air;               // the records, n and the skip rules of the table step
+  const double* ts;          // slices: the PDUs' timestamps; null: start + offset / fs (blocks.make_pdu)
+  double start, fs;
+  Plane* planes;             // 2^24 entries
+  unsigned epoch;
+  int all;                   // msg_filter "All Messages" (else "Extended Squitter Only")
+  unsigned long long* keys;  // [cap]: address << 32 | position, kDecNoKey
+  const unsigned long long* sorted;
+  DecRow* rows;              // [cap]
+};
+
+__device__ __forceinline__ unsigned dec_field(unsigned long long a, unsigned long long b, int lo, int n) {
+  // bits lo .. lo+n-1 (n <= 24) of the reply whose bytes are a (0..7) and b (8..13)
+  unsigned v = 0;
+  for (int i = lo; i < lo + n; ++i) {
+    const unsigned long long w = i < 64 ? a : b;
+    const int k = i < 64 ? i : i - 64;
+    v = (v << 1) | (unsigned)((w >> (8 * (k >> 3) + 7 - (k & 7))) & 1u);
+  }
+  return v;
+}
+__device__ __forceinline__ int dec_ac13(unsigned v) {                     // decoder.py:1016-1060
+  if (v == 0 || ((v >> 6) & 1u) || !((v >> 4) & 1u)) return -1;
+  return (int)(((v >> 7) << 5) | (((v >> 5) & 1u) << 4) | (v & 0xFu)) * 25 - 1000;
+}
+__device__ __forceinline__ int dec_ac12(unsigned v) {                     // decoder.py:1006-1013
+  if (!((v >> 4) & 1u)) return -1;
+  return (int)(((v >> 5) << 4) | (v & 0xFu)) * 25 - 1000;
+}
+__device__ __forceinline__ int dec_nl(double lat) {                       // decoder.py:1362-1512
+  static constexpr double e[58] = {
+      10.47047130, 14.82817437, 18.18626357, 21.02939493, 23.54504487, 25.82924707, 27.93898710, 29.91135686, 31.77209708,
+      33.53993436, 35.22899598, 36.85025108, 38.41241892, 39.92256684, 41.38651832, 42.80914012, 44.19454951, 45.54626723,
+      46.86733252, 48.16039128, 49.42776439, 50.67150166, 51.89342469, 53.09516153, 54.27817472, 55.44378444, 56.59318756,
+      57.72747354, 58.84763776, 59.95459277, 61.04917774, 62.13216659, 63.20427479, 64.26616523, 65.31845310, 66.36171008,
+      67.39646774, 68.42322022, 69.44242631, 70.45451075, 71.45986473, 72.45884545, 73.45177442, 74.43893416, 75.42056257,
+      76.39684391, 77.36789461, 78.33374083, 79.29428225, 80.24923213, 81.19801349, 82.13956981, 83.07199445, 83.99173563,
+      84.89166191, 85.75541621, 86.53536998, 87.00000000};
+  if (lat < 0) lat = -lat;
+  int k = 0;
+  while (k < 58 && !(lat < e[k])) ++k;
+  return 59 - k;
+}
+__device__ __forceinline__ long long dec_pymod(long long a, long long m) { const long long r = a % m; return r < 0 ? r + m : r; }
+// calculate_lat_lon (decoder.py:1309-1350) once both frames are younger than 30 s: false when the zones differ.  Every
+// operation is one IEEE float64 operation in the reference's order (-ffp-contract=off, no fast-math).
+__device__ __forceinline__ bool dec_cpr(const Plane& p, double& lat, double& lon) {
+  const double le = (double)p.cpr_lat0 / 131072, lo_e = (double)p.cpr_lon0 / 131072;
+  const double lo = (double)p.cpr_lat1 / 131072, lo_o = (double)p.cpr_lon1 / 131072;
+  const double x = 59 * le, y = 60 * lo;
+  const long long j = (long long)__builtin_floor((x - y) + 0.5);
+  double lat_even = (360.0 / 60) * ((double)dec_pymod(j, 60) + le);
+  if (lat_even >= 270) lat_even -= 360;
+  double lat_odd = (360.0 / 59) * ((double)dec_pymod(j, 59) + lo);
+  if (lat_odd >= 270) lat_odd -= 360;
+  if (dec_nl(lat_even) != dec_nl(lat_odd)) return false;
+  const bool even = (p.cpr_t0 - p.cpr_t1) > 0;
+  lat = even ? lat_even : lat_odd;
+  const int nl = dec_nl(lat);
+  const int ni = nl - (even ? 0 : 1) > 1 ? nl - (even ? 0 : 1) : 1;
+  const double u = lo_e * (double)(nl - 1), v = lo_o * (double)nl;
+  const long long m = (long long)__builtin_floor((u - v) + 0.5);
+  lon = (360.0 / (double)ni) * ((double)dec_pymod(m, ni) + (even ? lo_e : lo_o));
+  if (lon >= 180.0) lon -= 360.0;
+  return true;
+}
+
+// Events of an accepted PDU on its plane
+enum DecEvent : int { kEvSnap = 0, kEvCount, kEvAlt13, kEvIdent, kEvPos, kEvVel };
+struct DecClass {
+  unsigned long long a, b;   // the decoder's bits after the PDU (its repair applied)
+  int addr;                  // the address the PDU is filed under (self.aa_str), -1 for ""
+  int ev;                    // DecEvent, -1: not accepted
+  unsigned port;
+  bool fold;                 // its row needs the plane: the fold writes it
+};
+// decode_packet's path for one delivered record (w2 / w3 after k_fec and the table step's verdicts)
+__device__ __forceinline__ DecClass dec_classify(unsigned long long w2, unsigned long long w3, bool all, bool fec) {
+  DecClass c;
+  c.a = w2; c.b = w3 & 0xFFFFFFFFFFFFull; c.addr = -1; c.ev = -1; c.port = kDecNone; c.fold = false;
+  const unsigned fl = (unsigned)(w3 >> 48);
+  if (!(fl & kDemod)) return c;
+  const unsigned dfb = 1u << ((unsigned)(w2 & 0xFFu) >> 3);
+  const bool lng = (dfb & kDfLongSet) != 0;
+  unsigned long long ra, rb;
+  bool ok = false;
+  if (dfb & kDfApSet) {
+    if (!all) return c;                                                   // check_parity: only under "All Messages"
+    c.addr = (int)syndrome_of(w2, w3, lng ? 14 : 7);                      // self.aa_str of check_parity
+    if (fl & kApKnown) ok = true;
+    else if ((fl & kApFec) && fec_repair(w2, w3, lng, (unsigned)c.addr, ra, rb)) { c.a = ra; c.b = rb; ok = true; }
+  } else if ((dfb & kDfPiSet) && (all || (dfb & ~(1u << 11)))) {
+    if (fl & kParityOk) ok = true;                                        // kFecFixed: already repaired
+    else if ((fl & kFecDf) && fec_repair(w2, w3, lng, syndrome_of(w2, w3, lng ? 14 : 7), ra, rb)) { c.a = ra; c.b = rb; ok = true; }
+  }
+  if (!ok) return c;
+  // decode_message (decoder.py:883-947) on the repaired reply, decode_me (:1065-1301)
+  const unsigned df = (unsigned)(c.a & 0xFFu) >> 3;
+  c.ev = kEvSnap;
+  if (all && (df == 0 || df == 16 || df == 4 || df == 20 || df == 5 || df == 21)) {
+    if (c.addr >= 0) c.ev = (df == 5 || df == 21) ? kEvCount : kEvAlt13;
+  } else if (all && df == 11) {
+    c.addr = (int)dec_field(c.a, c.b, 8, 24);
+    c.ev = kEvCount;
+  } else if (df >= 17 && df <= 19) {
+    c.addr = (int)dec_field(c.a, c.b, 8, 24);
+    const unsigned sub = dec_field(c.a, c.b, 5, 3), tc = dec_field(c.a, c.b, 32, 5), st = dec_field(c.a, c.b, 37, 3);
+    if (df == 18 && (sub == 2 || sub == 3 || sub == 5)) c.port = kDecRaised;          // decode_tisb_me's log call
+    else if ((df == 18 && sub != 0 && sub != 1 && sub != 6) || (df == 19 && sub != 0)) {}
+    else if (tc == 0) {}
+    else if (tc <= 4) { c.ev = kEvIdent; c.port = kDecDecoded; }
+    else if (tc <= 8 || tc >= 20) c.port = kDecUnknown;
+    else if (tc <= 18) c.ev = kEvPos;
+    else if (st == 1 || st == 2) { c.ev = kEvVel; c.port = kDecDecoded; }
+    else if (st != 3 && st != 4) c.port = kDecRaised;                                  // self.st
+  }
+  c.fold = c.addr >= 0;
+  return c;
+}
+
+__device__ __forceinline__ void dec_load(const DecArgs& d, int t, unsigned long long& w2, unsigned long long& w3, double& ts) {
+  air_load(d.air, t, w2, w3);
+  if (d.ts) ts = d.ts[t];
+  else ts = d.start + (double)(long long)d.air.out[t].w[0] / d.fs;
+}
+__device__ __forceinline__ void dec_row(DecRow* r, const DecClass& c, unsigned port, const Plane* p) {
+  r->port = (unsigned char)port;
+  r->df = (unsigned char)((unsigned)(c.a & 0xFFu) >> 3);
+  r->present = 0; r->pad0 = 0;
+  r->icao = c.addr;
+  for (int k = 0; k < 8; ++k) r->bits[k] = (unsigned char)(c.a >> (8 * k));
+  for (int k = 0; k < 6; ++k) r->bits[8 + k] = (unsigned char)(c.b >> (8 * k));
+  r->pad1[0] = r->pad1[1] = 0;
+  r->pad2 = 0;
+  if (!p) {
+    for (int k = 0; k < 8; ++k) r->callsign[k] = 0;
+    r->altitude = r->velocity_we = r->velocity_sn = r->vertical_rate = 0;
+    r->latitude = r->longitude = __builtin_nan("");
+    r->num_msgs = 0;
+    return;
+  }
+  r->present = (unsigned char)(p->present & (kHasPlane | kHasCallsign | kHasAltitude | kHasVelocity));
+  for (int k = 0; k < 8; ++k) r->callsign[k] = (char)(p->callsign >> (8 * k));
+  r->altitude = p->altitude; r->velocity_we = p->vwe; r->velocity_sn = p->vsn; r->vertical_rate = p->vr;
+  r->latitude = p->lat; r->longitude = p->lon;
+  r->num_msgs = p->num_msgs;
+}
+__device__ __forceinline__ bool dec_skip(const DecArgs& d) { return air_skip(d.air); }
+
+// Stage 1, one thread per record of the list's capacity: the sort key, or the row at once
+__global__ void __launch_bounds__(kThreads) k_dec_classify(DecArgs d) {
+  if (dec_skip(d)) return;
+  const int n = air_n(d.air);
+  for (int t = (int)(blockIdx.x * kThreads + threadIdx.x); t < d.air.cap; t += (int)(gridDim.x * kThreads)) {
+    unsigned long long key = kDecNoKey;
+    if (t < n) {
+      unsigned long long w2, w3;
+      air_load(d.air, t, w2, w3);
+      const DecClass c = dec_classify(w2, w3, d.all != 0, d.air.fec != 0);
+      if (c.fold && c.ev >= 0) key = ((unsigned long long)(unsigned)c.addr << 32) | (unsigned)t;
+      else dec_row(&d.rows[t], c, c.port, nullptr);      // rejected (an unknown AA included) or filed under ""
+    }
+    d.keys[t] = key;
+  }
+}
+
+// Stage 3, one lane per address segment of the sorted keys: the plane's events in list order, a row after each
+__global__ void __launch_bounds__(kThreads) k_dec_fold(DecArgs d) {
+  if (dec_skip(d)) return;
+  for (int i = (int)(blockIdx.x * kThreads + threadIdx.x); i < d.air.cap; i += (int)(gridDim.x * kThreads)) {
+    const unsigned long long k0 = d.sorted[i];
+    if (k0 == kDecNoKey) continue;
+    const unsigned addr = (unsigned)(k0 >> 32);
+    if (i > 0 && (unsigned)(d.sorted[i - 1] >> 32) == addr) continue;
+    Plane p = d.planes[addr];
+    if (p.epoch != d.epoch) p.present = 0;
+    bool dirty = false;
+    for (int j = i; j < d.air.cap; ++j) {
+      const unsigned long long k = d.sorted[j];
+      if (k == kDecNoKey || (unsigned)(k >> 32) != addr) break;
+      const int t = (int)(unsigned)k;
+      unsigned long long w2, w3;
+      double ts;
+      dec_load(d, t, w2, w3, ts);
+      const DecClass c = dec_classify(w2, w3, d.all != 0, d.air.fec != 0);
+      unsigned port = c.port;
+      if (c.ev > kEvSnap) {
+        dirty = true;
+        if (!(p.present & kHasPlane)) {                                  // update_plane: a new entry (reset_plane_altimetry)
+          p.epoch = d.epoch; p.present = kHasPlane; p.num_msgs = 0; p.altitude = 0;
+          p.callsign = 0;
+          p.vwe = p.vsn = p.vr = 0;
+          p.lat = p.lon = __builtin_nan("");
+          p.cpr_lat0 = p.cpr_lat1 = p.cpr_lon0 = p.cpr_lon1 = 0; p.pad = 0;
+          p.cpr_t0 = p.cpr_t1 = 0;
+        }
+        p.num_msgs += 1;
+        if (c.ev == kEvAlt13) {
+          const int alt = dec_ac13(dec_field(c.a, c.b, 19, 13));
+          if (alt != -1) { p.altitude = alt; p.present |= kHasAltitude; }
+        } else if (c.ev == kEvIdent) {
+          static constexpr char lut[65] = "_ABCDEFGHIJKLMNOPQRSTUVWXYZ_____ _______________0123456789______";
+          unsigned long long cs = 0;
+          int q = 0;
+          for (int s = 0; s < 8; ++s) {
+            const char ch = lut[dec_field(c.a, c.b, 40 + 6 * s, 6)];
+            if (ch != '_') cs |= (unsigned long long)(unsigned char)ch << (8 * q++);
+          }
+          p.callsign = cs;
+          p.present |= kHasCallsign;
+        } else if (c.ev == kEvPos) {
+          const long long now = (long long)ts;
+          const int odd = (int)dec_field(c.a, c.b, 53, 1);
+          const int clat = (int)dec_field(c.a, c.b, 54, 17), clon = (int)dec_field(c.a, c.b, 71, 17);
+          if (odd) { p.cpr_lat1 = clat; p.cpr_lon1 = clon; p.cpr_t1 = now; p.present |= kHasOdd; }
+          else { p.cpr_lat0 = clat; p.cpr_lon0 = clon; p.cpr_t0 = now; p.present |= kHasEven; }
+          double lat = __builtin_nan(""), lon = lat;
+          if ((p.present & kHasEven) && (p.present & kHasOdd) && now - p.cpr_t0 < 30 && now - p.cpr_t1 < 30) {
+            double a_, b_;
+            if (dec_cpr(p, a_, b_)) { lat = a_; lon = b_; }
+          }
+          if ((lat - p.lat) < 0.1) port = kDecDecoded;                    // NaN on either side: not published
+          p.altitude = dec_ac12(dec_field(c.a, c.b, 40, 12));
+          p.present |= kHasAltitude;
+          if (lat == lat && lon == lon) { p.lat = lat; p.lon = lon; }
+        } else if (c.ev == kEvVel) {
+          int vwe = (int)dec_field(c.a, c.b, 46, 10) - 1, vsn = (int)dec_field(c.a, c.b, 57, 10) - 1;
+          int vr = ((int)dec_field(c.a, c.b, 69, 9) - 1) * 64;
+          if (dec_field(c.a, c.b, 45, 1)) vwe = -vwe;
+          if (dec_field(c.a, c.b, 56, 1)) vsn = -vsn;
+          if (dec_field(c.a, c.b, 68, 1)) vr = -vr;
+          p.vwe = vwe; p.vsn = vsn; p.vr = vr;
+          p.present |= kHasVelocity;
+        }
+      }
+      dec_row(&d.rows[t], c, port, (p.present & kHasPlane) ? &p : nullptr);
+    }
+    if (dirty) d.planes[addr] = p;
+  }
+}
+
+// adsb_decode_pdus: the ok[] bytes of already-published PDUs (kDemod | the parity pre-filter bits), as k_slice sets them
+__global__ void __launch_bounds__(kThreads) k_dec_pdu_flags(const unsigned char* bits14, unsigned char* ok, int n) {
+  for (int t = (int)(blockIdx.x * kThreads + threadIdx.x); t < n; t += (int)(gridDim.x * kThreads)) {
+    const unsigned char* p = bits14 + (long long)t * 14;
+    unsigned long long w2 = 0, w3 = 0;
+    for (int k = 0; k < 8; ++k) w2 |= (unsigned long long)p[k] << (8 * k);
+    for (int k = 0; k < 6; ++k) w3 |= (unsigned long long)p[8 + k] << (8 * k);
+    ok[t] = (unsigned char)(kDemod | (parity_flags_of(w2, w3) & 0xE0u));
+  }
+}
+
 }  // namespace adsb

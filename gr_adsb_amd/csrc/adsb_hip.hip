@@ -165,6 +165,8 @@ __device__ __forceinline__ adsb_cold_ptr adsb_cold(const adsb::DetectArgs&) {
 using namespace adsb;
 
 static_assert(sizeof(adsb_burst) == 32 && sizeof(Rec) == 32, "record layout");
+static_assert(sizeof(adsb_decoded) == sizeof(DecRow) && offsetof(adsb_decoded, latitude) == offsetof(DecRow, latitude) &&
+              offsetof(adsb_decoded, num_msgs) == offsetof(DecRow, num_msgs), "decoded row layout");
 
 namespace {
 
@@ -211,6 +213,8 @@ struct Slot {
   int seq = 0;                   // direct passes: the number the kernel stores into h_sum->pad_ when everything is out
   unsigned long long air_pass = 0;   // ADSB_FLAG_AIRCRAFT_TABLE: this pass's number << 32, kept when the pass is re-run
   bool air_keep = false;             // ... set while finish() re-runs the pass
+  void* h_dec = nullptr;             // ADSB_FLAG_DECODE: pinned rows of the pass's delivered records (adsb_last_decoded)
+  size_t h_dec_cap = 0;
   bool polled = false;           // ... and finish() polls for instead of waiting for an event
   Plan plan{};
   DetectArgs args{};
@@ -361,6 +365,15 @@ struct adsb_ctx {
   AirState* d_air_st = nullptr;
   hipEvent_t air_ev = nullptr;
   unsigned long long air_next = 0;    // number of the next published pass (table keys: number << 32 | position)
+  // ADSB_FLAG_DECODE: the plane state of every address, the epoch that marks an entry valid, the decoder's settings, and
+  // the sort's buffers (one decode step runs at a time: the table step's event chain orders them)
+  Plane* d_planes = nullptr;
+  unsigned dec_epoch = 1;
+  int dec_all = 1;
+  double dec_start = 0;
+  DevBuf d_dec_keys, d_dec_sorted, d_dec_tmp;
+  void* h_pdu = nullptr;              // adsb_decode_pdus' staging (pinned, device-visible)
+  size_t h_pdu_cap = 0;
   char err[256] = {0};
 };
 
@@ -574,7 +587,111 @@ void launch_fec(hipStream_t st, const Slot& s, Rec* out, const Summary* sum) {
 // opt-in aircraft table (ADSB_FLAG_AIRCRAFT_TABLE): the table step of one published pass (list: out / mirror / sum; slices:
 // bits14 / ok, n = ntags), in stream order behind every earlier pass's step: the three slots run on their own streams, so
 // the step waits for the event recorded behind the previous one (pass n's verdict needs every announcement of passes < n)
-int launch_air(adsb_ctx* c, hipStream_t st, AirArgs a, long long tot) {
+// ADSB_FLAG_DECODE's group stage: a stable LSD radix sort of the keys (address << 32 | position, written in list order) by
+// bits 32..59 -- the address and the "no key" marker; stability keeps list order inside an address.  Seven passes of four
+// bits, each a block histogram, one scan, a stable scatter.  Small on purpose: 4096 keys per workgroup, 272 bytes of LDS,
+// so that every stage fits beside the next pass's k_detect.
+constexpr int kSortItems = 16, kSortTile = kThreads * kSortItems;
+__global__ void __launch_bounds__(kThreads) k_dec_sort_hist(const unsigned long long* in, int n, int shift, unsigned* hist) {
+  __shared__ unsigned cnt[16];
+  if (threadIdx.x < 16) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const int base = (int)blockIdx.x * kSortTile;
+  for (int r = 0; r < kSortItems; ++r) {
+    const int i = base + r * kThreads + (int)threadIdx.x;
+    if (i < n) atomicAdd(&cnt[(unsigned)(in[i] >> shift) & 15u], 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x < 16) hist[threadIdx.x * gridDim.x + blockIdx.x] = cnt[threadIdx.x];
+}
+// exclusive scan of hist[16 * nblk] (digit-major), one workgroup
+__global__ void __launch_bounds__(kThreads) k_dec_sort_scan(unsigned* hist, int total) {
+  __shared__ unsigned wsum[kWaves];
+  __shared__ unsigned carry;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  for (int base = 0; base < total; base += kThreads) {
+    const int i = base + (int)threadIdx.x;
+    const unsigned v = i < total ? hist[i] : 0u;
+    unsigned x = v;
+    for (int o = 1; o < 64; o <<= 1) { const unsigned y = __shfl_up(x, o); if (lane >= o) x += y; }
+    if (lane == 63) wsum[wave] = x;
+    __syncthreads();
+    unsigned pre = carry;
+    for (int w = 0; w < wave; ++w) pre += wsum[w];
+    if (i < total) hist[i] = pre + x - v;
+    __syncthreads();
+    if (threadIdx.x == kThreads - 1) carry = pre + x;
+    __syncthreads();
+  }
+}
+__global__ void __launch_bounds__(kThreads) k_dec_sort_scatter(const unsigned long long* in, unsigned long long* out, int n,
+                                                               int shift, const unsigned* hist) {
+  __shared__ unsigned off[16];
+  __shared__ unsigned wcnt[kWaves][16];
+  if (threadIdx.x < 16) off[threadIdx.x] = hist[threadIdx.x * gridDim.x + blockIdx.x];
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const int base = (int)blockIdx.x * kSortTile;
+  for (int r = 0; r < kSortItems; ++r) {
+    const int i = base + r * kThreads + (int)threadIdx.x;
+    const bool live = i < n;
+    const unsigned long long k = live ? in[i] : 0ull;
+    const unsigned d = (unsigned)(k >> shift) & 15u;
+    unsigned rank = 0;
+    for (unsigned q = 0; q < 16; ++q) {
+      const unsigned long long m = __ballot(live && d == q);
+      if (lane == 0) wcnt[wave][q] = (unsigned)__popcll(m);
+      if (live && d == q) rank = (unsigned)__popcll(m & lt);
+    }
+    __syncthreads();
+    if (live) {
+      unsigned pos = off[d] + rank;
+      for (int w = 0; w < wave; ++w) pos += wcnt[w][d];
+      out[pos] = k;
+    }
+    __syncthreads();
+    if (threadIdx.x < 16) {
+      unsigned t = 0;
+      for (int w = 0; w < kWaves; ++w) t += wcnt[w][threadIdx.x];
+      off[threadIdx.x] += t;
+    }
+    __syncthreads();
+  }
+}
+
+// ADSB_FLAG_DECODE: the decode step of the same records, behind the last verdict (rows: cap rows; ts: the slices'
+// timestamps, null for a pass's list).  The sort's buffers are the context's: every decode step waits for the one before.
+int launch_dec(adsb_ctx* c, hipStream_t st, const AirArgs& a, long long g, DecRow* rows, const double* ts) {
+  const size_t n = (size_t)a.cap;
+  if (n == 0) return 0;
+  const int nblk = (int)((n + kSortTile - 1) / kSortTile);
+  const size_t tmp = (size_t)nblk * 16 * sizeof(unsigned);
+  if (n * 8 > c->d_dec_keys.cap || n * 8 > c->d_dec_sorted.cap || tmp > c->d_dec_tmp.cap) {
+    HIPCHK(c, hipEventSynchronize(c->air_ev));            // (the buffers may still be read by the step queued before)
+    int r;
+    if ((r = ensure(c, c->d_dec_keys, n * 8)) || (r = ensure(c, c->d_dec_sorted, n * 8)) || (r = ensure(c, c->d_dec_tmp, tmp))) return r;
+  }
+  DecArgs d{};
+  d.air = a; d.ts = ts; d.start = c->dec_start; d.fs = c->fs; d.planes = c->d_planes; d.epoch = c->dec_epoch; d.all = c->dec_all;
+  d.keys = (unsigned long long*)c->d_dec_keys.p; d.sorted = (const unsigned long long*)c->d_dec_sorted.p; d.rows = rows;
+  hipLaunchKernelGGL(k_dec_classify, dim3((unsigned)g), dim3(kThreads), 0, st, d);
+  unsigned long long* in = (unsigned long long*)c->d_dec_keys.p;
+  unsigned long long* out = (unsigned long long*)c->d_dec_sorted.p;
+  for (int shift = 32; shift < 60; shift += 4) {          // seven passes: the result ends in d_dec_sorted
+    hipLaunchKernelGGL(k_dec_sort_hist, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, (int)n, shift,
+                       (unsigned*)c->d_dec_tmp.p);
+    hipLaunchKernelGGL(k_dec_sort_scan, dim3(1), dim3(kThreads), 0, st, (unsigned*)c->d_dec_tmp.p, nblk * 16);
+    hipLaunchKernelGGL(k_dec_sort_scatter, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, out, (int)n, shift,
+                       (const unsigned*)c->d_dec_tmp.p);
+    unsigned long long* x = in; in = out; out = x;
+  }
+  hipLaunchKernelGGL(k_dec_fold, dim3((unsigned)g), dim3(kThreads), 0, st, d);
+  return 0;
+}
+
+int launch_air(adsb_ctx* c, hipStream_t st, AirArgs a, long long tot, DecRow* rows = nullptr, const double* ts = nullptr) {
   HIPCHK(c, hipStreamWaitEvent(st, c->air_ev, 0));
   long long g = (tot + kThreads - 1) / kThreads;
   if (g > 2048) g = 2048;
@@ -584,6 +701,7 @@ int launch_air(adsb_ctx* c, hipStream_t st, AirArgs a, long long tot) {
   hipLaunchKernelGGL(k_air_verdict, dim3((unsigned)g), dim3(kThreads), 0, st, a, 0);
   hipLaunchKernelGGL(k_air_cond, dim3(1), dim3(64), 0, st, a);
   hipLaunchKernelGGL(k_air_verdict, dim3((unsigned)g), dim3(kThreads), 0, st, a, 1);
+  if (c->flags & ADSB_FLAG_DECODE) { int r = launch_dec(c, st, a, g, rows, ts); if (r) return r; }
   HIPCHK(c, hipEventRecord(c->air_ev, st));
   return 0;
 }
@@ -593,7 +711,11 @@ int launch_air_pass(adsb_ctx* c, Slot& s, hipStream_t st, Rec* out, int force = 
   a.out = out; a.mirror = (out != (Rec*)s.h_out && s.host_cap > 0) ? (Rec*)s.h_out : nullptr;
   a.mirror_cap = a.mirror ? s.host_cap : 0;
   a.sum = &((Misc*)s.d_misc.p)->sum; a.cap = (int)s.tot; a.host_sum = s.h_sum; a.pass = s.air_pass; a.force = force;
-  return launch_air(c, st, a, s.tot);
+  if (c->flags & ADSB_FLAG_DECODE) {
+    int r = ensure_pinned(c, s.h_dec, s.h_dec_cap, (size_t)s.tot * sizeof(DecRow));
+    if (r) return r;
+  }
+  return launch_air(c, st, a, s.tot, (DecRow*)s.h_dec, nullptr);
 }
 
 // the step state's `broken` word cleared behind every table step queued so far (before a pass that overflowed is re-run)
@@ -1266,6 +1388,7 @@ float adsb_snr_db(float peak, float median) {
 }
 
 int adsb_create(double fs, float threshold, int device, uint32_t flags, adsb_ctx** out) {
+  if ((flags & ADSB_FLAG_DECODE) && !(flags & ADSB_FLAG_AIRCRAFT_TABLE)) return -EINVAL;   // the decode step follows the table's
   if (!out) return -EINVAL;
   *out = nullptr;
   if (!(fs > 0) || fmod(fs, 1e6) != 0.0) return -EINVAL;        // framer.py:44, demod.py:42
@@ -1313,6 +1436,12 @@ int adsb_create(double fs, float threshold, int device, uint32_t flags, adsb_ctx
   }
   c->stream = c->slot[0].stream;         // blocking calls always run in slot 0 (run_pipeline)
   if (hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking) != hipSuccess) { adsb_destroy(c); return -EIO; }
+  if (flags & ADSB_FLAG_DECODE) {
+    // every entry's epoch 0: no plane; adsb_reset moves the epoch on
+    const size_t pb = ((size_t)1 << 24) * sizeof(Plane);
+    if (hipMalloc((void**)&c->d_planes, pb) != hipSuccess) { (void)hipGetLastError(); adsb_destroy(c); return -ENOMEM; }
+    if (hipMemsetAsync(c->d_planes, 0, pb, c->stream) != hipSuccess) { adsb_destroy(c); return -EIO; }
+  }
   if (flags & ADSB_FLAG_AIRCRAFT_TABLE) {
     if (hipMalloc((void**)&c->d_air, ((size_t)1 << 24) * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc((void**)&c->d_air_st, sizeof(AirState)) != hipSuccess) { (void)hipGetLastError(); adsb_destroy(c); return -ENOMEM; }
@@ -1350,6 +1479,10 @@ void adsb_destroy(adsb_ctx* c) {
   if (c->air_ev) (void)hipEventSynchronize(c->air_ev);
   if (c->d_air) (void)hipFree(c->d_air);
   if (c->d_air_st) (void)hipFree(c->d_air_st);
+  if (c->d_planes) (void)hipFree(c->d_planes);
+  for (DevBuf* b : {&c->d_dec_keys, &c->d_dec_sorted, &c->d_dec_tmp}) if (b->p) (void)hipFree(b->p);
+  if (c->h_pdu) (void)hipHostFree(c->h_pdu);
+  for (Slot& sl : c->slot) if (sl.h_dec) (void)hipHostFree(sl.h_dec);
   if (c->air_ev) (void)hipEventDestroy(c->air_ev);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->h_dm) (void)hipHostFree(c->h_dm);
@@ -1439,6 +1572,11 @@ int adsb_reset(adsb_ctx* c) {
   if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) {
     for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
     HIPCHK(c, hipSetDevice(c->device));
+    if ((c->flags & ADSB_FLAG_DECODE) && ++c->dec_epoch == 0) {   // (2^32 resets: every entry cleared once more, behind
+      HIPCHK(c, hipStreamWaitEvent(c->stream, c->air_ev, 0));    //  every step queued so far and before air_clear's event)
+      HIPCHK(c, hipMemsetAsync(c->d_planes, 0, ((size_t)1 << 24) * sizeof(Plane), c->stream));
+      c->dec_epoch = 1;
+    }
     int r = air_clear(c);
     if (r) return r;
   }
@@ -1581,6 +1719,59 @@ int adsb_last_confidence(adsb_ctx* c, const float** ratio, int32_t* n) {
   return 0;
 }
 
+int adsb_set_decoder(adsb_ctx* c, int32_t msg_filter, double start_timestamp) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_DECODE");
+  if (msg_filter != ADSB_DEC_ALL_MESSAGES && msg_filter != ADSB_DEC_EXTENDED_SQUITTER_ONLY) return fail(c, -EINVAL, "msg_filter");
+  for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
+  c->dec_all = msg_filter == ADSB_DEC_ALL_MESSAGES;
+  c->dec_start = start_timestamp;
+  return 0;
+}
+
+int adsb_last_decoded(adsb_ctx* c, const adsb_decoded** rows, int32_t* n) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_DECODE");
+  const Slot& s = c->slot[c->last_slot];
+  if (rows) *rows = s.nres > 0 ? (const adsb_decoded*)s.h_dec : nullptr;
+  if (n) *n = s.nres;
+  return 0;
+}
+
+int adsb_decode_pdus(adsb_ctx* c, const uint8_t* bits14, const double* timestamps, int32_t n, adsb_decoded* rows) {
+  if (!c || n < 0 || (n > 0 && (!bits14 || !timestamps || !rows))) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_DECODE");
+  for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
+  if (n == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  // staging in pinned, device-visible memory: rows (72 B) | timestamps (8 B) | bits (14 B) | ok (1 B) per PDU
+  const size_t nt = (size_t)n, o_ts = nt * sizeof(adsb_decoded), o_bits = o_ts + nt * 8, o_ok = o_bits + nt * 14;
+  int rc;
+  if ((rc = ensure_pinned(c, c->h_pdu, c->h_pdu_cap, o_ok + nt))) return rc;
+  char* h = (char*)c->h_pdu;
+  memcpy(h + o_ts, timestamps, nt * 8);
+  memcpy(h + o_bits, bits14, nt * 14);
+  if ((rc = apply_ext(c, c->stream))) return rc;
+  const int g = (int)((nt + kThreads - 1) / kThreads < 2048 ? (nt + kThreads - 1) / kThreads : 2048);
+  hipLaunchKernelGGL(k_dec_pdu_flags, dim3(g), dim3(kThreads), 0, c->stream, (const unsigned char*)(h + o_bits),
+                     (unsigned char*)(h + o_ok), (int)n);
+  if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE)
+    hipLaunchKernelGGL(k_fec_slices, dim3(g), dim3(kThreads), 0, c->stream, (unsigned char*)(h + o_bits),
+                       (unsigned char*)(h + o_ok), (int)n);
+  AirArgs aa{};
+  aa.bits14 = (unsigned char*)(h + o_bits); aa.ok = (unsigned char*)(h + o_ok); aa.cap = (int)n;
+  aa.pass = (c->air_next++) << 32;
+  if ((rc = launch_air(c, c->stream, aa, (long long)n, (DecRow*)h, (const double*)(h + o_ts)))) {
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+  }
+  hipError_t he = hipStreamSynchronize(c->stream);
+  if (he == hipSuccess) he = hipGetLastError();
+  if (he != hipSuccess) return fail(c, -EIO, "decode step", he);
+  memcpy(rows, h, nt * sizeof(adsb_decoded));
+  return 0;
+}
+
 int adsb_submit_format_device(adsb_ctx* c, int format, const void* d_data, int64_t n, int64_t abs_offset, int32_t* ticket) {
   if (!c || format < 0 || format >= ADSB_FMT_COUNT) return -EINVAL;
   return submit_canonical(c, format, d_data, n, abs_offset, ticket);
@@ -1626,6 +1817,7 @@ int adsb_framer_work(adsb_ctx* c, const float* in0, int64_t n_in0, int64_t N, in
 int adsb_framer_work_passthrough(adsb_ctx* c, const float* in0, int64_t n_in0, int64_t N, int64_t nitems_written, float* out0,
                                  adsb_burst* tags, int32_t cap, int32_t* n_out) {
   if (!c || !in0 || N < 1) return -EINVAL;
+  if (c->flags & ADSB_FLAG_DECODE) return fail(c, -EINVAL, "adsb_framer_work is not for ADSB_FLAG_DECODE contexts");
   const long long H = 8ll * c->sps;
   if (n_in0 != N + H - 1) return fail(c, -EINVAL, "framer input must hold N + 8*sps - 1 items");
   HIPCHK(c, hipSetDevice(c->device));
@@ -1661,6 +1853,7 @@ int adsb_framer_work_passthrough(adsb_ctx* c, const float* in0, int64_t n_in0, i
 int adsb_demod_work(adsb_ctx* c, const float* in0, int64_t n, int64_t nitems_read, const int64_t* tag_offsets,
                     int32_t ntags, uint8_t* bits112, uint8_t* ok, float* ratio) {
   if (!c || n < 0 || ntags < 0 || (n > 0 && !in0) || (ntags > 0 && (!tag_offsets || !bits112 || !ok))) return -EINVAL;
+  if (c->flags & ADSB_FLAG_DECODE) return fail(c, -EINVAL, "adsb_demod_work is not for ADSB_FLAG_DECODE contexts (adsb_decode_pdus)");
   if (ntags == 0) return 0;
   if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE)      // (the table steps of passes in flight may still be settled: finish)
     for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");

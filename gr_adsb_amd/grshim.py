@@ -71,6 +71,12 @@ class sync_block:
     def message_port_register_out(self, name):
         self._ports.append(name)
 
+    def message_port_register_in(self, name):
+        self._ports_in = getattr(self, "_ports_in", []) + [name]
+
+    def set_msg_handler(self, name, fn):
+        self._handlers = dict(getattr(self, "_handlers", {}), **{name: fn})
+
     def message_port_pub(self, port, msg):
         self.messages.append((port, msg))
 

@@ -108,6 +108,21 @@ extern "C" {
  * (adsb_shard_*, adsb_submit_shard_device, adsb_process_sharded_*) return -EINVAL: their stitch decides publication after
  * the device has run.  Without the flag nothing is allocated or launched and no byte changes. */
 #define ADSB_FLAG_AIRCRAFT_TABLE 256u
+/* Opt-in, requires ADSB_FLAG_AIRCRAFT_TABLE (adsb_create: -EINVAL without it): the rest of the decoder on the device --
+ * decode_message / decode_me (decoder.py:883-1301: callsigns, AC13 / AC12 altitudes, velocities, the CPR global decode of
+ * :1309-1512), update_plane and the published ports (:413-440, :512-538) -- for the same PDUs, in the same publication order
+ * as the table, as one decoder with msg_filter set by adsb_set_decoder (default "All Messages") and error_corr
+ * "Conservative" iff ADSB_FLAG_FEC_CONSERVATIVE, else "None".  Every delivered record gets an adsb_decoded row
+ * (adsb_last_decoded); adsb_decode_pdus decodes already-published PDUs through the same state.
+ * The decoder's clock is the PDU's own timestamp: now = int(timestamp) (Python truncation), the timestamp of a record
+ * being start_timestamp + offset / fs in float64 (blocks.make_pdu) -- what the reference computes with int(time.time()) when it
+ * decodes in real time with zero latency.  CPR frames age out after 30 s of that clock; nothing else times out.
+ * State: one 88-byte entry per 24-bit address (2^24 entries, 1.375 GiB of device memory, allocated only with the flag),
+ * valid when its epoch is the context's: adsb_reset clears every plane in O(1).  The key "" that the decoder files a few
+ * PDUs under (a reply whose repair made it an address/parity format) is not an address: such PDUs touch no plane.
+ * adsb_framer_work, adsb_demod_work and the sharded entry points return -EINVAL.  Without the flag nothing is allocated or
+ * launched. */
+#define ADSB_FLAG_DECODE 512u
 
 /* adsb_burst.flags */
 #define ADSB_BURST_DEMOD 1u /* eob inside the demod input: bits[] valid, a PDU is published (demod.py:82) */
@@ -143,6 +158,36 @@ typedef struct adsb_burst {
   uint8_t bits[14]; /* 112 hard bits, first bit = MSB of bits[0] (demod.py:94-95) */
   uint16_t flags;
 } adsb_burst;
+
+/* ADSB_FLAG_DECODE: what the decoder made of one delivered record (adsb_last_decoded, adsb_decode_pdus).  72 bytes. */
+#define ADSB_DEC_NONE 0u      /* nothing published */
+#define ADSB_DEC_DECODED 1u   /* published on "decoded" (decoder.py:512-526): the plane's fields below */
+#define ADSB_DEC_UNKNOWN 2u   /* published on "unknown" (:529-538) */
+#define ADSB_DEC_RAISED 3u    /* decode_packet raises before it publishes: DF 18 CF 2/3/5, TC 19 ST 0/5/6/7 */
+#define ADSB_DEC_HAS_PLANE 1u     /* plane_dict[icao] exists after the PDU: the fields below are its snapshot */
+#define ADSB_DEC_HAS_CALLSIGN 2u  /* callsign is not None */
+#define ADSB_DEC_HAS_ALTITUDE 4u  /* altitude is not NaN */
+#define ADSB_DEC_HAS_VELOCITY 8u  /* speed, heading and vertical_rate are not NaN */
+#define ADSB_DEC_ALL_MESSAGES 0          /* adsb_set_decoder msg_filter values */
+#define ADSB_DEC_EXTENDED_SQUITTER_ONLY 1
+typedef struct adsb_decoded {
+  uint8_t port;          /* ADSB_DEC_* */
+  uint8_t df;            /* self.df after the PDU (the repaired reply's when the decoder repaired it) */
+  uint8_t present;       /* ADSB_DEC_HAS_* */
+  uint8_t pad0;
+  int32_t icao;          /* the address the PDU is filed under (self.aa_str), -1 for "" */
+  uint8_t bits[14];      /* the decoder's bits after the PDU: what a published PDU carries (packed, MSB first) */
+  char callsign[8];      /* NUL padded, "_" removed */
+  uint8_t pad1[2];
+  int32_t altitude;
+  int32_t velocity_we;   /* speed = sqrt(velocity_sn^2 + velocity_we^2), heading = arctan2(velocity_sn, velocity_we)*360/(2 pi) */
+  int32_t velocity_sn;
+  int32_t vertical_rate;
+  double latitude;       /* NaN until a fix */
+  double longitude;
+  uint32_t num_msgs;
+  uint32_t pad2;
+} adsb_decoded;
 
 typedef struct adsb_stats {
   uint64_t detect_launches;  /* k_detect launches timed */
@@ -260,6 +305,17 @@ int adsb_last_result(adsb_ctx* ctx, const adsb_burst** bursts, int32_t* n);
  * reference has them); rows of bursts without ADSB_BURST_DEMOD are zero.  Valid until the same pipeline slot is
  * used again.  -EINVAL on a context created without the flag. */
 int adsb_last_confidence(adsb_ctx* ctx, const float** ratio, int32_t* n);
+/* ADSB_FLAG_DECODE contexts: the decoder's msg_filter (ADSB_DEC_ALL_MESSAGES / _EXTENDED_SQUITTER_ONLY) and the
+ * start_timestamp of the records' PDU timestamps (start + offset / fs), for the calls that follow.  -EBUSY while a submitted
+ * call is pending. */
+int adsb_set_decoder(adsb_ctx* ctx, int32_t msg_filter, double start_timestamp);
+/* ADSB_FLAG_DECODE contexts: *rows -> n adsb_decoded in the context's pinned memory, row t for record t of the last finished
+ * adsb_process_* call or waited ticket.  Valid until the same pipeline slot is used again. */
+int adsb_last_decoded(adsb_ctx* ctx, const adsb_decoded** rows, int32_t* n);
+/* ADSB_FLAG_DECODE contexts: decode n already-published PDUs (bits14: n x 14 packed bytes; timestamps: n float64) in one
+ * device call, through the context's decoder state, in call order with its other calls: parity flags, the Conservative
+ * repair (with ADSB_FLAG_FEC_CONSERVATIVE), the table step and the decode step.  rows: n adsb_decoded. */
+int adsb_decode_pdus(adsb_ctx* ctx, const uint8_t* bits14, const double* timestamps, int32_t n, adsb_decoded* rows);
 
 /* Asynchronous form of adsb_process_*_device: submit queues the whole device pipeline on the context's
  * streams and returns a ticket (0 .. ADSB_MAX_IN_FLIGHT-1) at once; adsb_wait blocks for that call, copies
