@@ -52,6 +52,10 @@ BURST_FEC_DF = 0x8000    # FLAG_FEC_CONSERVATIVE: the decoder's repair would cha
 BURST_AP_FEC = 0x0004    # FLAG_AIRCRAFT_TABLE + FLAG_FEC_CONSERVATIVE: AA unknown, the decoder's repair accepts the reply
 BURST_AP_KNOWN = 0x0008  # FLAG_AIRCRAFT_TABLE: the AA of this address/parity reply was announced by an earlier PDU
 MAX_IN_FLIGHT = 3
+# one item of adsb_process_batch* (include/adsb_hip.h: adsb_batch_item): pointer, samples, stream offset, threshold
+BATCH_ITEM_DTYPE = np.dtype([("data", "<u8"), ("n", "<i8"), ("abs_offset", "<i8"), ("threshold", "<f4"), ("reserved", "<u4")])
+assert BATCH_ITEM_DTYPE.itemsize == 32
+BATCH_ITEM_MAX = 1 << 22     # ADSB_BATCH_ITEM_MAX: longer items take the ordinary pass inside the call
 
 EXPORTS = [
     "adsb_abi_version", "adsb_create", "adsb_destroy", "adsb_set_threshold", "adsb_set_stream", "adsb_set_copy_threads", "adsb_host_copy", "adsb_wait_for_event", "adsb_reset", "adsb_framer_state",
@@ -62,6 +66,7 @@ EXPORTS = [
     "adsb_submit_format_host", "adsb_last_confidence", "adsb_set_decoder", "adsb_last_decoded", "adsb_decode_pdus",
     "adsb_framer_work", "adsb_framer_work_passthrough", "adsb_demod_work", "adsb_shard_bounds", "adsb_process_sharded_device", "adsb_shard_device", "adsb_shard_host", "adsb_shard_fixup", "adsb_stitch", "adsb_snr_db", "adsb_mode_s_syndrome", "adsb_mode_s_fec", "adsb_mode_s_aircraft", "adsb_plan_chunks", "adsb_get_stats",
     "adsb_process_sharded_multi", "adsb_device_alloc", "adsb_device_free", "adsb_device_upload", "adsb_clear_pending_events",
+    "adsb_process_batch_device", "adsb_process_batch",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
 ]
 
@@ -153,6 +158,8 @@ def load():
     lib.adsb_shard_bounds.restype = c.c_int32
     lib.adsb_process_sharded_device.argtypes = [vp, c.c_int, vp, i64, i64, i32, vp, i32, c.POINTER(i32)]
     lib.adsb_process_sharded_multi.argtypes = [c.POINTER(vp), i32, c.c_int, vp, i64, i64, i32, vp, i32, c.POINTER(i32), c.POINTER(MultiStats)]
+    for name in ("adsb_process_batch_device", "adsb_process_batch"):
+        getattr(lib, name).argtypes = [vp, c.c_int, vp, i32, vp, i32, vp, c.POINTER(i32), c.POINTER(i32)]
     lib.adsb_device_alloc.argtypes = [vp, c.POINTER(vp), c.c_size_t]
     lib.adsb_device_free.argtypes = [vp, vp]
     lib.adsb_device_upload.argtypes = [vp, vp, vp, c.c_size_t]
@@ -191,6 +198,8 @@ class Context:
         self.fs = float(fs)
         self.sps = int(fs // 1e6)
         self._h = ctypes.c_void_p()
+        self._thr = np.float32(threshold)
+        self.last_batch_fallbacks = 0
         rc = self.lib.adsb_create(float(fs), float(np.float32(threshold)), int(device), int(flags), ctypes.byref(self._h))
         if rc != 0:
             self._h = ctypes.c_void_p()
@@ -219,6 +228,7 @@ class Context:
     def set_threshold(self, thr):
         self._chk(self.lib.adsb_set_threshold(self._h, float(np.float32(thr))))
         self._thr_cached = thr
+        self._thr = np.float32(thr)
 
     def set_stream(self, stream_handle):
         self._chk(self.lib.adsb_set_stream(self._h, ctypes.c_void_p(int(stream_handle))))
@@ -318,6 +328,50 @@ class Context:
         self._chk(self.lib.adsb_process_format_device(self._h, int(fmt), ctypes.c_void_p(int(dev_ptr)), int(n), int(abs_offset),
                                                       None, 0, ctypes.byref(n_out)))
         return self.last_result() if fetch else n_out.value
+
+    def _batch(self, fn, fmt, ptrs, ns, thresholds, abs_offsets):
+        k = len(ptrs)
+        items = np.zeros(k, dtype=BATCH_ITEM_DTYPE)
+        items["data"] = np.asarray(ptrs, dtype=np.uint64)
+        items["n"] = np.asarray(ns, dtype=np.int64)
+        items["abs_offset"] = 0 if abs_offsets is None else np.asarray(abs_offsets, dtype=np.int64)
+        items["threshold"] = self._thr if thresholds is None else np.asarray(thresholds, dtype=np.float32)
+        first = np.zeros(k + 1, dtype=np.int32)
+        n_out, n_fb = ctypes.c_int32(0), ctypes.c_int32(0)
+        cap = getattr(self, "_batch_cap", 1 << 16)
+        while True:
+            out = np.empty(cap, dtype=BURST_DTYPE)
+            rc = fn(self._h, int(fmt), ctypes.c_void_p(items.ctypes.data), k, ctypes.c_void_p(out.ctypes.data), cap,
+                    ctypes.c_void_p(first.ctypes.data), ctypes.byref(n_out), ctypes.byref(n_fb))
+            if rc == -28 and n_out.value > cap:          # -ENOSPC: *n_out = the number needed
+                cap = self._batch_cap = n_out.value + n_out.value // 4
+                continue
+            self._chk(rc)
+            break
+        self.last_batch_fallbacks = n_fb.value
+        return out[:n_out.value].copy(), first
+
+    def process_batch_device(self, fmt, ptrs, ns, thresholds=None, abs_offsets=None):
+        """Many independent streams in one device pass (adsb_process_batch_device): ptrs[i] = 16-byte aligned device pointer
+        of item i, ns[i] its samples; thresholds[i] its framer threshold (None: the context's for every item); abs_offsets[i]
+        the stream offset of its sample 0 (None: 0).  Returns (records, item_first): item i's records -- exactly those of
+        process_format_device over the item alone -- are records[item_first[i]:item_first[i+1]].  last_batch_fallbacks =
+        items that took the ordinary pass inside the call (longer than BATCH_ITEM_MAX, or a list overflow)."""
+        return self._batch(self.lib.adsb_process_batch_device, fmt, [int(p) for p in ptrs], ns, thresholds, abs_offsets)
+
+    def process_batch(self, fmt, arrays, thresholds=None, abs_offsets=None):
+        """The same for host arrays in the format's layout (adsb_process_batch): pageable numpy arrays, or page-locked ones
+        (PinnedArray.array, torch pin_memory), which are DMA'd where they lie.  Every array must start on a 16-byte boundary."""
+        dt, per = FMT_LAYOUT[int(fmt)]
+        arrays = [np.ascontiguousarray(a, dtype=dt) for a in arrays]
+        for k, a in enumerate(arrays):
+            if a.ctypes.data & 15:                       # a view into a larger array: the library wants 16-byte aligned items
+                buf = np.empty(a.nbytes + 16, dtype=np.uint8)
+                o = (-buf.ctypes.data) & 15
+                arrays[k] = buf[o:o + a.nbytes].view(dt)
+                arrays[k][...] = a
+        return self._batch(self.lib.adsb_process_batch, fmt, [a.ctypes.data for a in arrays], [len(a) // per for a in arrays],
+                           thresholds, abs_offsets)
 
     def submit_format_device(self, fmt, dev_ptr, n, abs_offset=0):
         t = ctypes.c_int32(-1)

@@ -56,6 +56,12 @@
 #define ADSB_AIR_STORE(p, v) ((void)(*(p) = (v)))
 #endif
 #endif
+// ADSB_COLD_AT(e): the argument block *e of a device TABLE (const DetectArgs* e, not written during the launch) as the pointer
+// type adsb_cold() returns.  The product maps it to the constant address space behind an empty asm statement; a host build
+// (the SIMT emulator) reads the entry where it lies.
+#ifndef ADSB_COLD_AT
+#define ADSB_COLD_AT(e) (e)
+#endif
 
 namespace adsb {
 
@@ -1124,8 +1130,19 @@ __device__ __forceinline__ bool chips_match(const float* tp, int half_rt) {
 
 // HALF = samples per chip (sps/2) when it is one of the instantiated rates (2, 4, 8, 20 Msps), else 0 = run-time value.
 // WPB = wavefronts per workgroup of the kernel this is the body of: 1 for k_detect, kWaves for k_pass_small.
-template <int MODE, int HALF, int WPB = kWaves>
-__device__ __forceinline__ void detect_body(const DetectArgs& a, const int block) {
+// COLD: where the body finds the argument block "as it lies in memory" (cold() below).  ColdKernarg: the kernel's own
+// argument segment -- right while DetectArgs is the kernel's first by-value parameter (k_detect, k_pass_small).  ColdTable:
+// an entry of a device table of argument blocks (k_batch: one entry per workgroup); the includer's ADSB_COLD_AT turns the
+// entry's address into the pointer type adsb_cold returns, opaque to the optimiser in the same way.
+struct ColdKernarg {
+  __device__ __forceinline__ auto operator()(const DetectArgs& a) const { return adsb_cold(a); }
+};
+struct ColdTable {
+  const DetectArgs* e;
+  __device__ __forceinline__ auto operator()(const DetectArgs&) const { return ADSB_COLD_AT(e); }
+};
+template <int MODE, int HALF, int WPB = kWaves, class COLD = ColdKernarg>
+__device__ __forceinline__ void detect_body(const DetectArgs& a, const int block, const COLD cold_src = COLD{}) {
   __shared__ __attribute__((aligned(16))) float s_xa[WPB][kBack + kWWin];
   __shared__ __attribute__((aligned(16))) unsigned s_ma[WPB][kMaskDwords];
   __shared__ __attribute__((aligned(4))) unsigned short s_risea[WPB][kWTile / 2];
@@ -1147,7 +1164,7 @@ __device__ __forceinline__ void detect_body(const DetectArgs& a, const int block
   // Those are read through cold() -- the same block as it lies in (kernarg) memory, one scalar load where it is used --
   // instead of living in registers across the tile loop (every k_detect instance spilled 60-90 SGPRs into vector lanes,
   // 8-15 v_readlane reloads per tile).  Hot fields (thr, scale, sps, origin, rec_cap, long_aware) stay by-value.
-  auto cold = [&]() { return adsb_cold(a); };
+  auto cold = [&]() { return cold_src(a); };
   const long long unit = (long long)block * WPB + wave;
   const long long c0 = unit * cold()->chunk;
   long long c1 = c0 + cold()->chunk;
@@ -2012,6 +2029,13 @@ struct TailArgs {
   int gate_on, head_n; long long gate, gate_long, prev_eob;
   int seq;               // this pass's number: stored LAST, into host_sum->pad_ -- the host polls it (adsb_hip.hip: finish)
 };
+// The small per-item words of a batch item's scratch (k_batch): the four lists' counts, offsets, flags and last centres, the
+// long-pulse list's two words, the item's Summary.  One block per item, zeroed in front of every batch.
+struct alignas(64) BatchFixed {
+  int blk_count[kWaves]; int blk_off[kWaves]; unsigned blk_flags[kWaves]; long long blk_lastp[kWaves];
+  int long_count; int pad; unsigned long long long_lastp;
+  Summary sum;
+};
 // End of a one-workgroup pass: the summary into the caller-visible (pinned, mapped) host copy, then -- behind a system-scope
 // fence, so that the records compact_body stored straight into pinned host memory and the summary's fields are visible
 // first -- the pass number.  The host does not wait for the kernel's completion signal (end-of-kernel cache maintenance,
@@ -2084,6 +2108,87 @@ __global__ void __launch_bounds__(kThreads) k_pass_small(DetectArgs a, TailArgs 
                t.long_lastp);
   __syncthreads();
   publish_small(t);
+}
+
+// ---- k_batch: many INDEPENDENT streams ("items") in one launch, one workgroup per item (adsb_process_batch*) ---------------
+// Workgroup b runs the whole pass of item b as k_pass_small runs its one stream -- detect_body over four chunks, then the
+// one-workgroup tail on the item's own scratch -- with its argument blocks taken from two device tables (da[b], ta[b]) instead
+// of the kernel's parameters: every item has its own data pointer, length, stream offset and threshold.  Any input format.
+// The item's gated records stay in device memory (ta[b].out), its Summary in ta[b].sum; kept[b] = the number of records, or -1
+// when the host has to run the item through the ordinary pass (a list overflowed; the host marks items it runs itself --
+// longer than ADSB_BATCH_ITEM_MAX -- with n < 0).  n == 0: no records.
+// detect_body reads its rarely needed fields from the table entry (ColdTable): the kernel-argument segment holds three pointers
+// here, not a DetectArgs.
+template <int MODE, int HALF>
+__global__ void __launch_bounds__(kThreads) k_batch(const DetectArgs* __restrict__ da, const TailArgs* __restrict__ ta,
+                                                    int* __restrict__ kept) {
+  const int b = (int)blockIdx.x;
+  const DetectArgs* const e = da + b;
+  const DetectArgs a = *e;
+  if (a.n <= 0) {                                              // workgroup-uniform
+    if (threadIdx.x == 0) kept[b] = a.n == 0 ? 0 : -1;
+    return;
+  }
+  detect_body<MODE, HALF, kWaves, ColdTable>(a, 0, ColdTable{e});
+  __syncthreads();
+  longrun_body<MODE>(0, 1, a);
+  __syncthreads();
+  const TailArgs t = ta[b];                                    // (behind the tile loop: its 21 fields are not live across it)
+  __shared__ int s_scan_cnt[kScanRound];
+  scan_body<kScanRound>(t.blk_count, t.blk_lastp, t.blk_flags, t.nblk, t.rec_cap, t.long_count, t.long_lastp, t.blk_off, t.sum, s_scan_cnt);
+  __syncthreads();
+  gather_body(0, 1, t.cands, t.blk_count, t.blk_off, t.nblk, t.rec_cap, t.sorted, t.sorted_src);
+  __syncthreads();
+  unsigned fmask = 0u, fwant = 0u;
+  if (t.gate_on) {
+    resolve_body(0, 1, t.sorted, t.sum, t.gate, t.gate_long, t.prev_eob);
+    fmask = kKept; fwant = kKept;
+    __syncthreads();
+  }
+  count_body(0, 1, t.sorted, t.sum, fmask, fwant, t.head_n, t.seg_count);
+  __syncthreads();
+  compact_body(0, 1, t.sorted, t.recs, t.sorted_src, t.sum, t.seg_count, fmask, fwant, t.head_n, t.out, t.out_cap, t.long_count,
+               t.long_lastp);
+  __syncthreads();
+  if (threadIdx.x == 0) {                                      // (thread 0 wrote every field it reads here)
+    const Summary* s = t.sum;
+    kept[b] = (s->overflow || s->long_count > a.long_cap || s->n_kept > t.out_cap) ? -1 : s->n_kept;
+  }
+}
+
+// ---- k_batch_pack: the items' records -> one dense list in item order ---------------------------------------------------
+// Workgroup b = item b: the exclusive prefix of the counts in front of it (a coalesced pass over kept[0 .. b): a few KB, L2
+// resident), then its records to packed[first .. first + count).  first[0 .. n_items] and a copy of kept[] go to the host
+// (pinned, mapped: visible when the stream has drained), and so do the first host_cap records of the dense list -- a batch
+// that delivers no more than that needs no device -> host copy.  tot->n_kept = the number of records (k_fec's bound).
+__global__ void __launch_bounds__(kThreads) k_batch_pack(const TailArgs* __restrict__ ta, const int* __restrict__ kept, int n_items,
+                                                         Rec* __restrict__ packed, int packed_cap, int* __restrict__ first,
+                                                         int* __restrict__ host_kept, Summary* __restrict__ tot,
+                                                         Rec* __restrict__ host_out, int host_cap) {
+  __shared__ int s_part[kWaves];
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int pre = 0;
+  for (int j = tid; j < b; j += kThreads) { const int k = kept[j]; pre += k > 0 ? k : 0; }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) pre += __shfl_xor(pre, d);
+  if (lane == 0) s_part[wave] = pre;
+  __syncthreads();
+  pre = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+  const int kb = kept[b], cnt = kb > 0 ? kb : 0;
+  if (tid == 0) {
+    first[b] = pre;
+    host_kept[b] = kb;
+    if (b == n_items - 1) { first[n_items] = pre + cnt; tot->n_kept = pre + cnt; }
+  }
+  typedef unsigned long long u64x2 __attribute__((vector_size(16)));
+  const u64x2* src = reinterpret_cast<const u64x2*>(ta[b].out);
+  for (int i = tid; i < 2 * cnt; i += kThreads) {              // 16-byte halves: consecutive lanes, consecutive addresses
+    const int r = pre + (i >> 1);
+    if (r >= packed_cap) break;
+    const u64x2 v = src[i];
+    reinterpret_cast<u64x2*>(packed + r)[i & 1] = v;
+    if (r < host_cap) reinterpret_cast<u64x2*>(host_out + r)[i & 1] = v;
+  }
 }
 
 // ---- k_slice: PPM slice (+ optional confidence ratio) for a caller-supplied tag list ---------------

@@ -157,6 +157,15 @@ __device__ __forceinline__ adsb_cold_ptr adsb_cold(const adsb::DetectArgs&) {
   asm volatile("" : "+s"(p));
   return (adsb_cold_ptr)p;
 }
+// The same for an argument block that lies in a device TABLE (k_batch: one entry per workgroup, the entry's address is
+// wave-uniform).  The table is not written while the kernel runs, so its entries may be read through the constant address
+// space like the kernel-argument segment: scalar loads where a field is used, and cold() keeps its type.
+__device__ __forceinline__ adsb_cold_ptr adsb_cold_at(const adsb::DetectArgs* e) {
+  unsigned long long p = (unsigned long long)e;
+  asm volatile("" : "+s"(p));
+  return (adsb_cold_ptr)p;
+}
+#define ADSB_COLD_AT(e) adsb_cold_at(e)
 
 #include "adsb_device.h"
 #include "adsb_plan.h"
@@ -221,6 +230,22 @@ struct Slot {
   int grid = 0, nlists = 0, rec_cap = 0;
   long long tot = 0, ntiles = 0, chunk = 0, span = 0;
   int32_t nres = 0;
+};
+
+// adsb_process_batch*: the context's buffers: they grow on demand like a slot's and are PER ITEM (an item's records have to outlive
+// its workgroup: k_batch_pack gathers them), so their size follows the batch, not the device -- see run_batch
+struct BatchBufs {
+  DevBuf d_scratch;              // per item: cands, sorted, recs, out, sorted_src, seg_count, long-pulse list
+  DevBuf d_fixed;                // BatchFixed[n_items]
+  DevBuf d_da, d_ta, d_kept;     // the two argument tables and k_batch's verdict per item
+  DevBuf d_packed, d_tot;        // the dense record list and its Summary (n_kept = number of records: k_fec's bound)
+  DevBuf d_in;                   // adsb_process_batch: the device copy of every item
+  void* h_tab = nullptr;         // pinned: the tables as the host builds them
+  size_t h_tab_cap = 0;
+  void* h_first = nullptr;       // pinned, device-visible: first[n_items + 1], then kept[n_items]
+  size_t h_first_cap = 0;
+  void* h_out = nullptr;         // pinned, device-visible: the dense list (its head straight from k_batch_pack)
+  size_t h_out_cap = 0;
 };
 
 }  // namespace
@@ -374,6 +399,7 @@ struct adsb_ctx {
   DevBuf d_dec_keys, d_dec_sorted, d_dec_tmp;
   void* h_pdu = nullptr;              // adsb_decode_pdus' staging (pinned, device-visible)
   size_t h_pdu_cap = 0;
+  BatchBufs bt;                       // adsb_process_batch*
   char err[256] = {0};
 };
 
@@ -1245,6 +1271,241 @@ int upload(adsb_ctx* c, const void* host, size_t bytes, void** d_out) {
   return 0;
 }
 
+// ---- adsb_process_batch*: many independent streams, one workgroup each (k_batch), one dense result (k_batch_pack) ----------
+// k_batch is instantiated per input format for 2 Msps (the rate of the receivers that come in fleets: RTL-SDR, HackRF) and
+// with the run-time tap stride for every other rate: ten instances, not twenty-five -- each is a detect_body plus a tail, and
+// the library's build time is its kernels'.  The 8-bit formats run the generic-scale conversion whatever the scale is (the
+// power-of-two instances of k_detect are bit-identical to it: tests/test_conversion_exact.py).
+template <int MODE>
+void launch_batch(hipStream_t st, int sps, int n_items, const DetectArgs* da, const TailArgs* ta, int* kept) {
+  if (sps == 2) hipLaunchKernelGGL((k_batch<MODE, 1>), dim3(n_items), dim3(kThreads), 0, st, da, ta, kept);
+  else hipLaunchKernelGGL((k_batch<MODE, 0>), dim3(n_items), dim3(kThreads), 0, st, da, ta, kept);
+}
+
+int check_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_items, adsb_burst* out, int32_t cap,
+                int32_t* item_first, int32_t* n_out) {
+  if (!c) return -EINVAL;
+  if (fmt < 0 || fmt >= ADSB_FMT_COUNT) return fail(c, -EINVAL, "adsb_process_batch: bad format");
+  if (n_items < 0 || (n_items > 0 && !items) || cap < 0 || (cap > 0 && !out) || !item_first || !n_out)
+    return fail(c, -EINVAL, "adsb_process_batch: bad argument");
+  if (c->flags & (ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE | ADSB_FLAG_CONFIDENCE))
+    return fail(c, -EINVAL, "adsb_process_batch: not for ADSB_FLAG_AIRCRAFT_TABLE / _DECODE / _CONFIDENCE contexts (one receiver each)");
+  for (int32_t i = 0; i < n_items; ++i) {
+    if (items[i].reserved != 0u) return fail(c, -EINVAL, "adsb_process_batch: item.reserved must be 0");
+    if (items[i].n < 0) return fail(c, -EINVAL, "adsb_process_batch: item.n < 0");
+    if (items[i].n > 0 && !items[i].data) return fail(c, -EINVAL, "adsb_process_batch: item.data is NULL");
+    if (((uintptr_t)items[i].data & 15u) != 0) return fail(c, -EINVAL, "adsb_process_batch: item.data must be 16-byte aligned");
+  }
+  for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
+  return 0;
+}
+
+// the dense list and item_first are 32-bit: a batch whose lists have 2^31 slots or more is refused
+int batch_slots_ok(adsb_ctx* c, const adsb_batch_item* items, int32_t n_items) {
+  long long slots = 0;
+  for (int32_t i = 0; i < n_items; ++i)
+    if (items[i].n > 0 && items[i].n <= kBatchItemMax) slots += (long long)kWaves * plan_batch_item(items[i].n, c->sps, kWaves, kWTile).rec_cap;
+  if (slots >= (1ll << 31)) return fail(c, -EINVAL, "adsb_process_batch: batch too large for one call (list slots >= 2^31)");
+  return 0;
+}
+
+// items[i].data: memory the device can read.  Arguments have been checked (check_batch).
+int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_items, adsb_burst* out, int32_t cap,
+              int32_t* item_first, int32_t* n_out, int32_t* n_fallback) {
+  *n_out = 0;
+  item_first[0] = 0;
+  if (n_fallback) *n_fallback = 0;
+  if (n_items == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  BatchBufs& B = c->bt;
+  const hipStream_t st = c->stream;
+  int r;
+  // Scratch PER ITEM, laid out one item after the other (adsb_plan.h: plan_batch_layout)
+  std::vector<BatchLay> lay((size_t)n_items);
+  size_t total = 0;
+  long long packed_cap = 0;
+  for (int32_t i = 0; i < n_items; ++i) {
+    BatchLay& L = lay[(size_t)i];
+    L.slots = 0;
+    if (items[i].n == 0 || items[i].n > kBatchItemMax) continue;
+    L = plan_batch_layout(total, plan_batch_item(items[i].n, c->sps, kWaves, kWTile), kWaves, kThreads, sizeof(Rec), sizeof(LongRise));
+    total = L.end;
+    packed_cap += L.slots;
+  }
+  if ((r = batch_slots_ok(c, items, n_items))) return r;
+  const long long kHostRecs = 32768;
+  const size_t tab_bytes = (size_t)n_items * (sizeof(DetectArgs) + sizeof(TailArgs));
+  if ((r = ensure(c, B.d_scratch, total + 128))) return r;
+  if ((r = ensure(c, B.d_fixed, (size_t)n_items * sizeof(BatchFixed)))) return r;
+  if ((r = ensure(c, B.d_da, (size_t)n_items * sizeof(DetectArgs)))) return r;
+  if ((r = ensure(c, B.d_ta, (size_t)n_items * sizeof(TailArgs)))) return r;
+  if ((r = ensure(c, B.d_kept, (size_t)n_items * sizeof(int)))) return r;
+  if ((r = ensure(c, B.d_packed, (size_t)(packed_cap + 1) * sizeof(Rec)))) return r;
+  if ((r = ensure(c, B.d_tot, sizeof(Summary)))) return r;
+  if ((r = ensure_pinned(c, B.h_tab, B.h_tab_cap, tab_bytes))) return r;
+  if ((r = ensure_pinned(c, B.h_first, B.h_first_cap, (size_t)(2 * (size_t)n_items + 1) * sizeof(int), true))) return r;
+  if ((r = ensure_pinned(c, B.h_out, B.h_out_cap, (size_t)kHostRecs * sizeof(Rec), true))) return r;
+  long long host_cap = (long long)(B.h_out_cap / sizeof(Rec));
+  if (host_cap > kHostRecs) host_cap = kHostRecs;
+
+  DetectArgs* hda = (DetectArgs*)B.h_tab;
+  TailArgs* hta = (TailArgs*)((char*)B.h_tab + (size_t)n_items * sizeof(DetectArgs));
+  memset(B.h_tab, 0, tab_bytes);
+  char* const sc = (char*)B.d_scratch.p;
+  BatchFixed* const fx = (BatchFixed*)B.d_fixed.p;
+  const bool long_aware = (c->flags & ADSB_FLAG_LONG_AWARE_GATE) != 0;
+  for (int32_t i = 0; i < n_items; ++i) {
+    const BatchLay& L = lay[(size_t)i];
+    if (L.slots == 0) { hda[i].n = items[i].n == 0 ? 0 : -1; continue; }     // empty, or the host's own (too long)
+    fill_batch_item(hda[i], hta[i], plan_canonical(fmt, items[i].data, items[i].n, items[i].abs_offset, c->sps), L, sc, fx[i],
+                    items[i].threshold, c->scale[fmt], c->sps, long_aware, kWaves);
+  }
+  if ((r = apply_ext(c, st))) return r;
+  HIPCHK(c, hipMemcpyAsync(B.d_da.p, hda, (size_t)n_items * sizeof(DetectArgs), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(B.d_ta.p, hta, (size_t)n_items * sizeof(TailArgs), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(B.d_fixed.p, 0, (size_t)n_items * sizeof(BatchFixed), st));
+  int* const h_first = (int*)B.h_first;
+  int* const h_kept = h_first + n_items + 1;
+  ADSB_BY_MODE(fmt, launch_batch, st, c->sps, (int)n_items, (const DetectArgs*)B.d_da.p, (const TailArgs*)B.d_ta.p, (int*)B.d_kept.p);
+  hipLaunchKernelGGL(k_batch_pack, dim3(n_items), dim3(kThreads), 0, st, (const TailArgs*)B.d_ta.p, (const int*)B.d_kept.p,
+                     (int)n_items, (Rec*)B.d_packed.p, (int)packed_cap, h_first, h_kept, (Summary*)B.d_tot.p, (Rec*)B.h_out,
+                     (int)host_cap);
+  if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) {
+    long long g = (packed_cap + kThreads - 1) / kThreads;
+    if (g > 2048) g = 2048;
+    if (g < 1) g = 1;
+    hipLaunchKernelGGL(k_fec, dim3((unsigned)g), dim3(kThreads), 0, st, (Rec*)B.d_packed.p, (const Summary*)B.d_tot.p,
+                       (int)packed_cap, (Rec*)B.h_out, (int)host_cap);
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(st));
+  std::atomic_thread_fence(std::memory_order_acquire);
+  c->stats.calls++;
+  const long long nb = h_first[n_items];
+  if (nb < 0 || nb > packed_cap) return fail(c, -EIO, "adsb_process_batch: the pack step returned nonsense");
+  if (nb > host_cap) {
+    if ((r = ensure_pinned(c, B.h_out, B.h_out_cap, (size_t)nb * sizeof(Rec), true))) return r;
+    HIPCHK(c, hipMemcpyAsync(B.h_out, B.d_packed.p, (size_t)nb * sizeof(Rec), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+  }
+  const adsb_burst* const packed = (const adsb_burst*)B.h_out;
+  int32_t nfb = 0;
+  for (int32_t i = 0; i < n_items; ++i) nfb += h_kept[i] < 0 ? 1 : 0;
+  if (n_fallback) *n_fallback = nfb;
+  if (nfb == 0) {
+    *n_out = (int32_t)nb;
+    for (int32_t i = 0; i <= n_items; ++i) item_first[i] = h_first[i];
+    if (nb > cap) return fail(c, -ENOSPC, "output array too small");
+    if (nb > 0) memcpy(out, packed, (size_t)nb * sizeof(adsb_burst));
+    return 0;
+  }
+  // The items k_batch could not finish (or was not given): each through the ordinary pass, as a blocking canonical pass with
+  // the item's threshold -- enqueue / finish regrow the list capacity themselves -- and its records take the item's place.
+  // The pass runs in a pipeline slot OTHER than the one adsb_last_result refers to (no slot is busy: check_batch), so the
+  // previous call's records, their count and any view the caller holds into that slot's pinned buffer stay as they are; the
+  // context's threshold and its list-capacity multiplier are put back afterwards (an item's density says nothing about the
+  // caller's other streams).  stats.calls / stats.retries do count these passes.
+  std::vector<std::vector<adsb_burst>> fb((size_t)nfb);
+  std::vector<int32_t> fb_of((size_t)n_items, -1);
+  const float thr_saved = c->thr;
+  const int shift_saved = c->rec_cap_shift;
+  Slot& fs = c->slot[(c->last_slot + 1) % ADSB_MAX_IN_FLIGHT];
+  int32_t k = 0;
+  int rc = 0;
+  for (int32_t i = 0; i < n_items && rc == 0; ++i) {
+    if (h_kept[i] >= 0) continue;
+    Plan pl = plan_canonical(fmt, items[i].data, items[i].n, items[i].abs_offset, c->sps);
+    pl.long_aware = long_aware;
+    Summary s;
+    int32_t nres = 0;
+    c->thr = items[i].threshold;
+    rc = enqueue(c, fs, pl, false);
+    if (rc) fs.busy = false;
+    else rc = finish(c, fs, &s, &nres);
+    if (rc == 0 && nres > 0) {
+      const adsb_burst* src = (const adsb_burst*)fs.h_out;
+      fb[(size_t)k].assign(src, src + nres);
+    }
+    fb_of[(size_t)i] = k++;
+  }
+  c->thr = thr_saved;
+  c->rec_cap_shift = shift_saved;
+  if (rc) return rc;
+  long long tot = 0;
+  for (int32_t i = 0; i < n_items; ++i) {
+    item_first[i] = (int32_t)tot;
+    tot += fb_of[(size_t)i] >= 0 ? (long long)fb[(size_t)fb_of[(size_t)i]].size() : (long long)(h_first[i + 1] - h_first[i]);
+    if (tot >= (1ll << 31)) return fail(c, -EINVAL, "adsb_process_batch: more than 2^31 records");
+  }
+  item_first[n_items] = (int32_t)tot;
+  *n_out = (int32_t)tot;
+  if (tot > cap) return fail(c, -ENOSPC, "output array too small");
+  for (int32_t i = 0; i < n_items; ++i) {
+    const int32_t cnt = item_first[i + 1] - item_first[i];
+    if (cnt == 0) continue;
+    const adsb_burst* src = fb_of[(size_t)i] >= 0 ? fb[(size_t)fb_of[(size_t)i]].data() : packed + h_first[i];
+    memcpy(out + item_first[i], src, (size_t)cnt * sizeof(adsb_burst));
+  }
+  return 0;
+}
+
+// adsb_process_batch: every item into ONE device buffer of the context (each on a 256-byte boundary).  Page-locked sources are
+// DMA'd where they lie; pageable ones go through the staging ring, consecutive items gathered into one ring chunk (by the
+// context's copy threads, like staged_copy) and sent with one DMA (an item larger than a chunk: staged_copy, in pieces).
+int upload_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_items, std::vector<adsb_batch_item>* dev) {
+  constexpr size_t kRingChunk = (size_t)16 << 20;
+  const size_t bps = (size_t)mode_bytes(fmt);
+  std::vector<size_t> off((size_t)n_items + 1);
+  size_t total = 0;
+  for (int32_t i = 0; i < n_items; ++i) { off[(size_t)i] = total; total += ((size_t)items[i].n * bps + 255) & ~(size_t)255; }
+  off[(size_t)n_items] = total;
+  int rc;
+  if ((rc = ensure(c, c->bt.d_in, total + 256))) return rc;
+  if ((rc = ensure_pool(c))) return rc;
+  const hipStream_t st = c->stream;
+  if ((rc = apply_ext(c, st))) return rc;
+  char* const d = (char*)c->bt.d_in.p;
+  int cur = -1;                 // ring chunk being filled, or -1
+  size_t cur_lo = 0, cur_hi = 0;   // ... with the device range [cur_lo, cur_hi)
+  auto flush = [&]() -> int {
+    if (cur < 0) return 0;
+    if (cur_hi > cur_lo) {
+      HIPCHK(c, hipMemcpyAsync(d + cur_lo, c->h_ring[cur], cur_hi - cur_lo, hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipEventRecord(c->ring_done[cur], st));
+      c->ring_used[cur] = true;
+    }
+    cur = -1;
+    return 0;
+  };
+  for (int32_t i = 0; i < n_items; ++i) {
+    const size_t bytes = (size_t)items[i].n * bps, o = off[(size_t)i];
+    (*dev)[(size_t)i] = items[i];
+    (*dev)[(size_t)i].data = d + o;
+    if (bytes == 0) continue;
+    if (is_pinned_host(items[i].data)) {
+      if ((rc = flush())) return rc;
+      HIPCHK(c, hipMemcpyAsync(d + o, items[i].data, bytes, hipMemcpyHostToDevice, st));
+      continue;
+    }
+    if (bytes > kRingChunk) {
+      if ((rc = flush())) return rc;
+      if ((rc = staged_copy(c, d + o, items[i].data, bytes, st))) return rc;
+      continue;
+    }
+    if (cur >= 0 && o + bytes - cur_lo > kRingChunk) { if ((rc = flush())) return rc; }
+    if (cur < 0) {
+      for (void*& rg : c->h_ring)
+        if (!rg) HIPCHK(c, host_alloc_near(c, &rg, kRingChunk));
+      cur = (int)(c->ring_k++ % (unsigned)adsb_ctx::kRing);
+      if (c->ring_used[cur]) HIPCHK(c, hipEventSynchronize(c->ring_done[cur]));     // the chunk's previous DMA has read it
+      cur_lo = o;
+    }
+    c->pool->copy((char*)c->h_ring[cur] + (o - cur_lo), (const char*)items[i].data, bytes);     // (the context's copy threads)
+    cur_hi = o + bytes;
+  }
+  return flush();
+}
+
 }  // namespace
 
 extern "C" {
@@ -1482,6 +1743,10 @@ void adsb_destroy(adsb_ctx* c) {
   if (c->d_planes) (void)hipFree(c->d_planes);
   for (DevBuf* b : {&c->d_dec_keys, &c->d_dec_sorted, &c->d_dec_tmp}) if (b->p) (void)hipFree(b->p);
   if (c->h_pdu) (void)hipHostFree(c->h_pdu);
+  for (DevBuf* b : {&c->bt.d_scratch, &c->bt.d_fixed, &c->bt.d_da, &c->bt.d_ta, &c->bt.d_kept, &c->bt.d_packed, &c->bt.d_tot,
+                    &c->bt.d_in})
+    if (b->p) (void)hipFree(b->p);
+  for (void* p : {c->bt.h_tab, c->bt.h_first, c->bt.h_out}) if (p) (void)hipHostFree(p);
   for (Slot& sl : c->slot) if (sl.h_dec) (void)hipHostFree(sl.h_dec);
   if (c->air_ev) (void)hipEventDestroy(c->air_ev);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -1620,6 +1885,34 @@ int adsb_process_format(adsb_ctx* c, int format, const void* host, int64_t n, in
   int rc = upload(c, host, (size_t)n * (size_t)mode_bytes(format), &d);
   if (rc) return rc;
   return canonical(c, format, d, n, abs_offset, out, cap, n_out);
+}
+
+static_assert(sizeof(adsb_batch_item) == 32 && offsetof(adsb_batch_item, threshold) == 24, "adsb_batch_item layout");
+static_assert(ADSB_BATCH_ITEM_MAX == kBatchItemMax, "adsb_plan.h and the header agree on the longest batch-path item");
+
+int adsb_process_batch_device(adsb_ctx* c, int format, const adsb_batch_item* items, int32_t n_items, adsb_burst* out,
+                              int32_t cap, int32_t* item_first, int32_t* n_out, int32_t* n_fallback) {
+  int rc = check_batch(c, format, items, n_items, out, cap, item_first, n_out);
+  if (rc) return rc;
+  return run_batch(c, format, items, n_items, out, cap, item_first, n_out, n_fallback);
+}
+
+int adsb_process_batch(adsb_ctx* c, int format, const adsb_batch_item* items, int32_t n_items, adsb_burst* out, int32_t cap,
+                       int32_t* item_first, int32_t* n_out, int32_t* n_fallback) {
+  int rc = check_batch(c, format, items, n_items, out, cap, item_first, n_out);
+  if (rc) return rc;
+  std::vector<adsb_batch_item> dev((size_t)n_items);
+  if (n_items > 0) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = batch_slots_ok(c, items, n_items))) return rc;       // (before any upload is queued)
+    rc = upload_batch(c, format, items, n_items, &dev);
+    if (rc == 0) rc = run_batch(c, format, dev.data(), n_items, out, cap, item_first, n_out, n_fallback);
+    // an error exit (an allocation that failed, ...) may leave uploads queued that read the CALLER's page-locked buffers:
+    // they have finished when this call returns (a successful call and -ENOSPC have synchronised already)
+    if (rc != 0 && rc != -ENOSPC) (void)hipStreamSynchronize(c->stream);
+    return rc;
+  }
+  return run_batch(c, format, dev.data(), n_items, out, cap, item_first, n_out, n_fallback);
 }
 
 int adsb_process_iq16_device(adsb_ctx* c, const void* d_iq16, int64_t n, int64_t abs_offset, adsb_burst* out,

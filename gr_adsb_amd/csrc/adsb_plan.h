@@ -68,6 +68,68 @@ inline Plan plan_canonical(int mode, const void* d, long long n, long long abs_o
   return p;
 }
 
+// One item of a batch (adsb_process_batch*: k_batch, one four-wavefront workgroup per item): the item is a canonical call cut
+// into four chunks of whole tiles, as the one-launch small pass cuts its input, with the ordinary pass's first list capacity
+// (chunk/256 + 64 slots per list, never more than there can be rises; whole 128-byte lines).  An item whose lists overflow is
+// run again through the ordinary pass by the host, which regrows its capacity itself.
+constexpr long long kBatchItemMax = 1ll << 22;      // ADSB_BATCH_ITEM_MAX
+struct BatchGeom { long long ntiles, chunk; int rec_cap, long_cap; };
+inline BatchGeom plan_batch_item(long long n, int sps, int lists = 4, int tile = 1024) {
+  const long long span = n - (8ll * sps - 1);             // plan_canonical: scan_hi
+  long long ntiles = span > 0 ? (span + tile - 1) / tile : 0;
+  if (ntiles < 1) ntiles = 1;
+  const long long tiles_per = (ntiles + lists - 1) / lists;
+  BatchGeom g;
+  g.ntiles = ntiles; g.chunk = tiles_per * tile;
+  long long rc = g.chunk / 256 + 64;
+  if (rc > g.chunk / 2 + 8) rc = g.chunk / 2 + 8;
+  g.rec_cap = (int)((rc + 15) & ~15ll);
+  g.long_cap = (int)(ntiles + 1);                         // at most one long pulse per tile, plus the virtual rise
+  return g;
+}
+
+// Scratch of ONE batch item inside one buffer, as byte offsets from `base` (every array on a 128-byte line): the four lists'
+// words and records, the ordered list and its sources, the item's gated records, the segment counts, the long-pulse list.
+// Per list slot that is 8 + 32 + 8 + 4 + 32 = 84 bytes: ~0.33 bytes per sample plus ~22 KB per item.
+struct BatchLay { size_t cands, sorted, recs, out, src, seg, lng, end; long long slots; BatchGeom g; };
+inline BatchLay plan_batch_layout(size_t base, const BatchGeom& g, int lists, int threads, size_t rec_bytes, size_t long_bytes) {
+  auto up = [](size_t v) { return (v + 127) & ~(size_t)127; };
+  BatchLay L;
+  L.g = g; L.slots = (long long)lists * g.rec_cap;
+  const size_t s = (size_t)L.slots;
+  size_t o = base;
+  L.cands = o; o += up(s * 8);
+  L.sorted = o; o += up(s * 8);
+  L.recs = o; o += up(s * rec_bytes);
+  L.out = o; o += up(s * rec_bytes);
+  L.src = o; o += up(s * 4);
+  L.seg = o; o += up((s / (size_t)threads + 2) * 4);
+  L.lng = o; o += up((size_t)g.long_cap * long_bytes);
+  L.end = o;
+  return L;
+}
+// The two argument blocks of one batch item (DA = DetectArgs, TA = TailArgs, FX = BatchFixed of adsb_device.h): a canonical
+// plan with the item's own threshold, its scratch at `sc` + L.*, its small words in fx.  One definition for the library and
+// the emulator driver of the tests.
+template <class DA, class TA, class FX>
+inline void fill_batch_item(DA& a, TA& t, const Plan& pl, const BatchLay& L, char* sc, FX& fx, float thr, float scale, int sps,
+                            bool long_aware, int lists) {
+  a.data = pl.d_data; a.n = pl.n; a.in0_base = pl.in0_base; a.scan_lo = pl.scan_lo; a.scan_hi = pl.scan_hi;
+  a.fall_hi = pl.fall_hi; a.dem_hi = pl.dem_hi; a.origin = pl.origin; a.chunk = L.g.chunk; a.thr = thr;
+  a.prev_in0 = pl.prev_in0; a.scale = scale; a.sps = sps; a.end_is_call_end = pl.end_is_call_end;
+  a.long_aware = long_aware ? 1 : 0; a.rec_cap = L.g.rec_cap; a.long_cap = L.g.long_cap;
+  a.cands = (decltype(a.cands))(sc + L.cands); a.recs = (decltype(a.recs))(sc + L.recs); a.blk_count = fx.blk_count;
+  a.blk_lastp = fx.blk_lastp; a.blk_flags = fx.blk_flags; a.longlist = (decltype(a.longlist))(sc + L.lng);
+  a.long_count = &fx.long_count; a.long_lastp = &fx.long_lastp;
+  t.cands = a.cands; t.recs = a.recs; t.blk_count = a.blk_count; t.blk_lastp = a.blk_lastp; t.blk_flags = a.blk_flags;
+  t.blk_off = fx.blk_off; t.nblk = lists; t.rec_cap = L.g.rec_cap; t.long_count = a.long_count; t.long_lastp = a.long_lastp;
+  t.sorted = (decltype(t.sorted))(sc + L.sorted); t.sorted_src = (decltype(t.sorted_src))(sc + L.src);
+  t.seg_count = (decltype(t.seg_count))(sc + L.seg); t.sum = &fx.sum; t.host_sum = nullptr;
+  t.out = (decltype(t.out))(sc + L.out); t.out_cap = (int)L.slots;
+  t.gate_on = pl.gate ? 1 : 0; t.head_n = 0; t.gate = 63ll * sps; t.gate_long = (long long)(long_aware ? 119 : 63) * sps;
+  t.prev_eob = pl.prev_eob_stream - pl.origin; t.seq = 0;
+}
+
 // framer.work() as GNU Radio calls it: the buffer IS in0 (N + 8*sps - 1 floats, history first).
 inline Plan plan_framer_work(const void* d_in0, long long n_in0, long long N, long long nitems_written, int sps,
                              const FramerState& st) {

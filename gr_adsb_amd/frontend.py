@@ -128,6 +128,27 @@ class FrontEnd:
     def wait(self, ticket, fetch=True, copy=True):
         return self.ctx.wait(ticket, fetch=fetch, copy=copy)
 
+    # -- many receivers, one GPU: a batch of independent streams in one device pass -------------------
+    def process_batch(self, fmt, arrays, thresholds=None, abs_offsets=None):
+        """arrays[i]: host array of item i in the format's layout -> (records, item_first); item i's records, those of
+        process_format(fmt, arrays[i]) at thresholds[i], are records[item_first[i]:item_first[i+1]] (Context.process_batch)."""
+        return self.ctx.process_batch(fmt, arrays, thresholds, abs_offsets)
+
+    def process_batch_tensors(self, fmt, tensors, thresholds=None, abs_offsets=None):
+        """The same for contiguous CUDA tensors (first dimension = samples; views into one allocation are fine as long as each
+        starts on a 16-byte boundary).  One event for the call: the tensors are all on torch's current stream."""
+        tensors = list(tensors)
+        if tensors:
+            for t in tensors:
+                assert t.is_cuda and t.is_contiguous()
+            _after_torch(self.ctx, tensors[0])
+        return self.ctx.process_batch_device(fmt, [t.data_ptr() for t in tensors], [t.shape[0] for t in tensors],
+                                             thresholds, abs_offsets)
+
+    @property
+    def last_batch_fallbacks(self):
+        return self.ctx.last_batch_fallbacks
+
     def shard_tensor(self, t, origin, own_lo, own_hi, stream_len, fmt=0, head_cands=0):
         _after_torch(self.ctx, t)
         return self.ctx.shard_device(fmt, t.data_ptr(), t.shape[0], origin, own_lo, own_hi, stream_len, head_cands)

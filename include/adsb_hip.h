@@ -433,6 +433,37 @@ typedef struct adsb_multi_stats {
 int adsb_process_sharded_multi(adsb_ctx* const* ctxs, int32_t n_ctx, int format, const void* host, int64_t n,
                                int64_t abs_offset, int32_t shards_per_ctx, adsb_burst* out, int32_t cap, int32_t* n_out,
                                adsb_multi_stats* stats);
+/* MANY receivers, ONE device pass: a batch of n_items INDEPENDENT streams ("items") of one format on one context (one fs).
+ * Every item is a fresh stream of its own -- its own zero history, noise-window clamp, prev_eob_idx = -1 and end-of-call
+ * rules (framer.py:54-57,102-108, demod.py:82) -- with its own stream offset and threshold: item i's records are exactly
+ * those adsb_process_format_device(ctx, format, data, n, abs_offset, ...) returns on a context whose threshold is
+ * items[i].threshold -- same records, same order, same bytes -- concatenated in item order: out[item_first[i] ..
+ * item_first[i+1]) belong to item i, *n_out = item_first[n_items] (item_first holds n_items + 1 entries).  One launch runs one
+ * workgroup per item (k_batch) and a second packs the items' records (k_batch_pack): N receivers cost one pass, not N.
+ * The format scale, fs, ADSB_FLAG_LONG_AWARE_GATE and ADSB_FLAG_FEC_CONSERVATIVE come from the context and apply to every item.
+ * Items longer than ADSB_BATCH_ITEM_MAX samples, and items whose centre lists overflow the batch kernel's capacity, are run
+ * through the ordinary pass inside the call and their records take the item's place (*n_fallback counts them; may be NULL):
+ * the result never depends on the batch kernel's capacity.  Few LONG items are better served by adsb_submit_format_device.
+ * -ENOSPC with *n_out = the number needed when cap is too small; -EBUSY while submitted tickets are pending; -EINVAL for a
+ * bad format, a pointer that is not 16-byte aligned, reserved != 0, n < 0, and on contexts with ADSB_FLAG_AIRCRAFT_TABLE,
+ * ADSB_FLAG_DECODE or ADSB_FLAG_CONFIDENCE (one table, one row set, one ratio list model ONE receiver).  n_items == 0 succeeds.
+ * The framer state of adsb_framer_work and the result of adsb_last_result are left alone, with or without fallback items (a
+ * fallback pass runs in a pipeline slot other than the one adsb_last_result refers to; adsb_get_stats counts it in calls / retries).  Pending adsb_wait_for_event events
+ * are consumed by the call's first GPU operation.  No reference counterpart: the reference is one receiver per process. */
+typedef struct adsb_batch_item {
+  const void* data;   /* 16-byte aligned; memory the device can read (adsb_process_batch_device) or host memory (adsb_process_batch) */
+  int64_t n;          /* samples; 0 is legal and yields no records */
+  int64_t abs_offset; /* stream offset of the item's sample 0 */
+  float threshold;    /* this item's framer threshold: any float, <= 0 and NaN included (the reference accepts them) */
+  uint32_t reserved;  /* must be 0 */
+} adsb_batch_item;    /* 32 bytes */
+#define ADSB_BATCH_ITEM_MAX (1ll << 22) /* longer items are legal; they take the ordinary pass inside the call */
+int adsb_process_batch_device(adsb_ctx* ctx, int format, const adsb_batch_item* items, int32_t n_items, adsb_burst* out,
+                              int32_t cap, int32_t* item_first, int32_t* n_out, int32_t* n_fallback);
+/* The same for items in HOST memory: all items are uploaded into one device buffer of the context (page-locked sources DMA'd
+ * where they lie, pageable ones through the staging ring), then run as above. */
+int adsb_process_batch(adsb_ctx* ctx, int format, const adsb_batch_item* items, int32_t n_items, adsb_burst* out, int32_t cap,
+                       int32_t* item_first, int32_t* n_out, int32_t* n_fallback);
 /* Device memory on the context's device for callers that do not link HIP (a C or ctypes client of the *_device entry
  * points): hipMalloc / hipFree / a blocking hipMemcpy host -> device.  16-byte alignment is guaranteed.  No reference
  * counterpart (the reference never leaves host memory). */
