@@ -236,10 +236,27 @@ class Context:
     def reset(self):
         self._chk(self.lib.adsb_reset(self._h))
 
-    def _run(self, fn, ptr, n, abs_offset):
+    # The three calls every input format has (FMT_LAYOUT: dtype and items per sample of the flat host array); the methods
+    # named after one format below are these with that format.
+    def _host(self, fmt, data, abs_offset):
+        dt, per = FMT_LAYOUT[fmt]
+        data = np.ascontiguousarray(data, dtype=dt)
         n_out = ctypes.c_int32(0)
-        self._chk(fn(self._h, ctypes.c_void_p(ptr), int(n), int(abs_offset), None, 0, ctypes.byref(n_out)))
+        self._chk(self.lib.adsb_process_format(self._h, fmt, ctypes.c_void_p(data.ctypes.data), len(data) // per,
+                                               int(abs_offset), None, 0, ctypes.byref(n_out)))
         return self.last_result()
+
+    def _device(self, fmt, dev_ptr, n, abs_offset, fetch):
+        n_out = ctypes.c_int32(0)
+        self._chk(self.lib.adsb_process_format_device(self._h, fmt, ctypes.c_void_p(int(dev_ptr)), int(n), int(abs_offset),
+                                                      None, 0, ctypes.byref(n_out)))
+        return self.last_result() if fetch else n_out.value
+
+    def _submit(self, fmt, dev_ptr, n, abs_offset):
+        t = ctypes.c_int32(-1)
+        self._chk(self.lib.adsb_submit_format_device(self._h, fmt, ctypes.c_void_p(int(dev_ptr)), int(n), int(abs_offset),
+                                                     ctypes.byref(t)))
+        return t.value
 
     def last_result(self, copy=True):
         """Bursts of the last finished call.  copy=False returns a writable view of the context's pinned
@@ -304,30 +321,20 @@ class Context:
         return t.value
 
     def process_iq(self, iq, abs_offset=0):
-        iq = np.ascontiguousarray(iq, dtype=np.complex64)
-        return self._run(self.lib.adsb_process_iq, iq.ctypes.data, len(iq), abs_offset)
+        return self._host(FMT_FC32, iq, abs_offset)
 
     def process_mag2(self, x, abs_offset=0):
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        return self._run(self.lib.adsb_process_mag2, x.ctypes.data, len(x), abs_offset)
+        return self._host(FMT_MAG2, x, abs_offset)
 
     def set_format_scale(self, fmt, scale):
         self._chk(self.lib.adsb_set_format_scale(self._h, int(fmt), float(np.float32(scale))))
 
     def process_format(self, fmt, data, abs_offset=0):
         """Host array in any ADSB_FMT_* layout (integer IQ: flat interleaved I,Q array of 2n items)."""
-        dt, per = FMT_LAYOUT[int(fmt)]
-        data = np.ascontiguousarray(data, dtype=dt)
-        n_out = ctypes.c_int32(0)
-        self._chk(self.lib.adsb_process_format(self._h, int(fmt), ctypes.c_void_p(data.ctypes.data), len(data) // per,
-                                               int(abs_offset), None, 0, ctypes.byref(n_out)))
-        return self.last_result()
+        return self._host(int(fmt), data, abs_offset)
 
     def process_format_device(self, fmt, dev_ptr, n, abs_offset=0, fetch=True):
-        n_out = ctypes.c_int32(0)
-        self._chk(self.lib.adsb_process_format_device(self._h, int(fmt), ctypes.c_void_p(int(dev_ptr)), int(n), int(abs_offset),
-                                                      None, 0, ctypes.byref(n_out)))
-        return self.last_result() if fetch else n_out.value
+        return self._device(int(fmt), dev_ptr, n, abs_offset, fetch)
 
     def _batch(self, fn, fmt, ptrs, ns, thresholds, abs_offsets):
         k = len(ptrs)
@@ -374,51 +381,32 @@ class Context:
                            thresholds, abs_offsets)
 
     def submit_format_device(self, fmt, dev_ptr, n, abs_offset=0):
-        t = ctypes.c_int32(-1)
-        self._chk(self.lib.adsb_submit_format_device(self._h, int(fmt), ctypes.c_void_p(int(dev_ptr)), int(n), int(abs_offset),
-                                                     ctypes.byref(t)))
-        return t.value
+        return self._submit(int(fmt), dev_ptr, n, abs_offset)
 
     def set_iq16_scale(self, scale):
-        self._chk(self.lib.adsb_set_iq16_scale(self._h, float(np.float32(scale))))
+        self.set_format_scale(FMT_SC16, scale)
 
     def process_iq16(self, iq16, abs_offset=0):
         """iq16: int16 array of interleaved I,Q (2n shorts)."""
-        iq16 = np.ascontiguousarray(iq16, dtype=np.int16)
-        return self._run(self.lib.adsb_process_iq16, iq16.ctypes.data, len(iq16) // 2, abs_offset)
+        return self._host(FMT_SC16, iq16, abs_offset)
 
     def process_iq16_device(self, dev_ptr, n, abs_offset=0, fetch=True):
-        n_out = ctypes.c_int32(0)
-        self._chk(self.lib.adsb_process_iq16_device(self._h, ctypes.c_void_p(int(dev_ptr)), int(n), int(abs_offset), None, 0,
-                                                    ctypes.byref(n_out)))
-        return self.last_result() if fetch else n_out.value
+        return self._device(FMT_SC16, dev_ptr, n, abs_offset, fetch)
 
     def submit_iq16_device(self, dev_ptr, n, abs_offset=0):
-        t = ctypes.c_int32(-1)
-        self._chk(self.lib.adsb_submit_iq16_device(self._h, ctypes.c_void_p(int(dev_ptr)), int(n), int(abs_offset), ctypes.byref(t)))
-        return t.value
+        return self._submit(FMT_SC16, dev_ptr, n, abs_offset)
 
     def process_iq_device(self, dev_ptr, n, abs_offset=0, fetch=True):
-        n_out = ctypes.c_int32(0)
-        self._chk(self.lib.adsb_process_iq_device(self._h, ctypes.c_void_p(int(dev_ptr)), int(n), int(abs_offset), None, 0,
-                                                  ctypes.byref(n_out)))
-        return self.last_result() if fetch else n_out.value
+        return self._device(FMT_FC32, dev_ptr, n, abs_offset, fetch)
 
     def process_mag2_device(self, dev_ptr, n, abs_offset=0, fetch=True):
-        n_out = ctypes.c_int32(0)
-        self._chk(self.lib.adsb_process_mag2_device(self._h, ctypes.c_void_p(int(dev_ptr)), int(n), int(abs_offset), None, 0,
-                                                    ctypes.byref(n_out)))
-        return self.last_result() if fetch else n_out.value
+        return self._device(FMT_MAG2, dev_ptr, n, abs_offset, fetch)
 
     def submit_iq_device(self, dev_ptr, n, abs_offset=0):
-        t = ctypes.c_int32(-1)
-        self._chk(self.lib.adsb_submit_iq_device(self._h, ctypes.c_void_p(int(dev_ptr)), int(n), int(abs_offset), ctypes.byref(t)))
-        return t.value
+        return self._submit(FMT_FC32, dev_ptr, n, abs_offset)
 
     def submit_mag2_device(self, dev_ptr, n, abs_offset=0):
-        t = ctypes.c_int32(-1)
-        self._chk(self.lib.adsb_submit_mag2_device(self._h, ctypes.c_void_p(int(dev_ptr)), int(n), int(abs_offset), ctypes.byref(t)))
-        return t.value
+        return self._submit(FMT_MAG2, dev_ptr, n, abs_offset)
 
     def submit_shard_device(self, fmt, dev_ptr, n, origin, own_lo, own_hi, stream_len, head_cands=0):
         t = ctypes.c_int32(-1)

@@ -12,6 +12,7 @@
 #include <sys/syscall.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -20,6 +21,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -179,10 +181,35 @@ static_assert(sizeof(adsb_decoded) == sizeof(DecRow) && offsetof(adsb_decoded, l
 
 namespace {
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
+// Owners: whatever a context creates -- device memory, page-locked memory, streams, events -- is held by a member that
+// releases it when the context is deleted (adsb_destroy synchronises, then `delete c`): a new member needs no line anywhere
+// else.  Move-only; no allocation and no HIP call outside create / grow / release; `.p` is a plain pointer read.
+template <class P, auto Release>
+struct Owned {
+  P p = nullptr;
+  Owned() = default;
+  Owned(Owned&& o) noexcept : p(o.p) { o.p = nullptr; }
+  ~Owned() { (void)release(); }
+  hipError_t release() {
+    const hipError_t e = p ? Release(p) : hipSuccess;
+    p = nullptr;
+    return e;
+  }
+  operator P() const { return p; }
+  P operator->() const { return p; }
 };
+template <class T> using DevPtr = Owned<T*, hipFree>;         // device memory of a fixed size
+template <class T> using PinnedPtr = Owned<T*, hipHostFree>;  // page-locked host memory of a fixed size
+using Stream = Owned<hipStream_t, hipStreamDestroy>;          // a queue the context created (never a caller's: adsb_set_stream)
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+// ... and memory that grows on demand (ensure / ensure_pinned)
+template <auto Release>
+struct Buf : Owned<void*, Release> {
+  size_t cap = 0;
+  hipError_t release() { cap = 0; return Owned<void*, Release>::release(); }
+};
+using DevBuf = Buf<hipFree>;
+using PinnedBuf = Buf<hipHostFree>;
 
 // d_misc layout: [0] int long_count, [8] u64 long_lastp, [16] OrderAcc (k_order's accumulator), [64] Summary
 struct Misc {
@@ -202,13 +229,11 @@ struct Slot {
   DevBuf d_cands, d_recs, d_sorted, d_sorted_src, d_out, d_seg, d_blk_count, d_blk_lastp, d_blk_flags, d_blk_off, d_long, d_misc;
   DevBuf d_in;                   // host-fed submissions: this call's samples (adsb_submit_format_host)
   DevBuf d_ratio;                // ADSB_FLAG_CONFIDENCE: [n_kept][112] bit1/bit0 ratios
-  Summary* h_sum = nullptr;      // pinned
-  void* h_out = nullptr;         // pinned burst records of the finished call
-  size_t h_out_cap = 0;
-  void* h_ratio = nullptr;       // pinned confidence ratios of the finished call
-  size_t h_ratio_cap = 0;
-  hipEvent_t done = nullptr, ev0 = nullptr, ev1 = nullptr, det_done = nullptr, h2d_done = nullptr;
-  hipStream_t stream = nullptr;  // this slot's own in-order queue: a SUBMITTED pass runs on it from k_detect to k_compact (see enqueue)
+  PinnedPtr<Summary> h_sum;
+  PinnedBuf h_out;               // burst records of the finished call
+  PinnedBuf h_ratio;             // confidence ratios of the finished call
+  Event done, ev0, ev1, det_done, h2d_done;
+  Stream stream;                 // this slot's own in-order queue: a SUBMITTED pass runs on it from k_detect to k_compact (see enqueue)
   hipStream_t ds = nullptr;      // the stream this pass's k_detect was queued on ...
   hipStream_t cs = nullptr;      // ... and the one its tail, its summary and its record copy run on (the same, or behind an event)
   bool busy = false;
@@ -222,8 +247,7 @@ struct Slot {
   int seq = 0;                   // direct passes: the number the kernel stores into h_sum->pad_ when everything is out
   unsigned long long air_pass = 0;   // ADSB_FLAG_AIRCRAFT_TABLE: this pass's number << 32, kept when the pass is re-run
   bool air_keep = false;             // ... set while finish() re-runs the pass
-  void* h_dec = nullptr;             // ADSB_FLAG_DECODE: pinned rows of the pass's delivered records (adsb_last_decoded)
-  size_t h_dec_cap = 0;
+  PinnedBuf h_dec;                   // ADSB_FLAG_DECODE: rows of the pass's delivered records (adsb_last_decoded)
   bool polled = false;           // ... and finish() polls for instead of waiting for an event
   Plan plan{};
   DetectArgs args{};
@@ -240,12 +264,9 @@ struct BatchBufs {
   DevBuf d_da, d_ta, d_kept;     // the two argument tables and k_batch's verdict per item
   DevBuf d_packed, d_tot;        // the dense record list and its Summary (n_kept = number of records: k_fec's bound)
   DevBuf d_in;                   // adsb_process_batch: the device copy of every item
-  void* h_tab = nullptr;         // pinned: the tables as the host builds them
-  size_t h_tab_cap = 0;
-  void* h_first = nullptr;       // pinned, device-visible: first[n_items + 1], then kept[n_items]
-  size_t h_first_cap = 0;
-  void* h_out = nullptr;         // pinned, device-visible: the dense list (its head straight from k_batch_pack)
-  size_t h_out_cap = 0;
+  PinnedBuf h_tab;               // the tables as the host builds them
+  PinnedBuf h_first;             // device-visible: first[n_items + 1], then kept[n_items]
+  PinnedBuf h_out;               // device-visible: the dense list (its head straight from k_batch_pack)
 };
 
 }  // namespace
@@ -318,6 +339,13 @@ struct CopyPool {
   }
 };
 
+// One context.  Four rules of its host side are each kept in one place:
+//   * what it creates it releases: every buffer, stream and event is an owner member (DevBuf, PinnedBuf, DevPtr, PinnedPtr,
+//     Stream, Event, the copy pool); adsb_destroy only synchronises and deletes;
+//   * a call that fails releases its pipeline slot: enqueue() and finish() do, no caller does;
+//   * nothing runs while a submitted call is pending: require_idle();
+//   * a per-record step gets step_grid(n, per) workgroups.
+// claim_and_enqueue() hands the next slot to a submitted pass, requeue_grown() re-runs a pass whose lists overflowed.
 struct adsb_ctx {
   int device = 0;
   double fs = 0;
@@ -335,14 +363,14 @@ struct adsb_ctx {
   // one serialise.  A context of its own uses three (the slots') plus the upload stream of host-fed submissions;
   // the record copy of a finished pass goes onto that pass's own -- by then idle -- stream.
   hipStream_t stream = nullptr;       // compute stream of the blocking entry points: slot 0's stream, or the caller's (adsb_set_stream)
-  hipStream_t copy_stream = nullptr;  // caller-owned compute stream only: device -> pinned host result copies
-  hipStream_t tail_stream = nullptr;  // caller-owned compute stream only: everything after k_detect
+  Stream copy_stream;                 // caller-owned compute stream only: device -> pinned host result copies
+  Stream tail_stream;                 // caller-owned compute stream only: everything after k_detect
   // adsb_wait_for_event: the caller's events the NEXT pass has to wait for (applied to the stream its first kernel runs on)
   static constexpr int kMaxExt = 4;
   hipEvent_t ext_ev[kMaxExt] = {nullptr, nullptr, nullptr, nullptr};
   int n_ext = 0;
-  hipStream_t h2d_stream = nullptr;   // host-fed submissions: sample uploads, back to back on their own stream
-  hipStream_t d2h_stream = nullptr;   // record copies of in-line passes while slot 2's stream holds an overlapped pass (created on first use)
+  Stream h2d_stream;                  // host-fed submissions: sample uploads, back to back on their own stream
+  Stream d2h_stream;                  // record copies of in-line passes while slot 2's stream holds an overlapped pass (created on first use)
   bool split_tail = false;
   bool own_stream = false;
   int n_cu = 256;
@@ -363,13 +391,11 @@ struct adsb_ctx {
   int last_slot = 0;
   DevBuf d_in;            // device copy of the host input of the blocking entry points
   int rec_cap_shift = 0;  // rec_cap multiplier (grows on overflow)
-  void* h_stage = nullptr;   // pinned staging for pageable inputs of the blocking entry points
-  size_t h_stage_cap = 0;
-  void* h_dm = nullptr;      // pinned scratch of adsb_demod_work: tag positions in, bits / ok / ratio out
-  size_t h_dm_cap = 0;
+  PinnedBuf h_stage;         // staging for pageable inputs of the blocking entry points
+  PinnedBuf h_dm;            // scratch of adsb_demod_work: tag positions in, bits / ok / ratio out
   static constexpr int kRing = 4;
-  void* h_ring[kRing] = {nullptr, nullptr, nullptr, nullptr};   // pinned chunks for pageable host-fed submissions
-  hipEvent_t ring_done[kRing] = {nullptr, nullptr, nullptr, nullptr};
+  PinnedPtr<void> h_ring[kRing];   // chunks for pageable host-fed submissions
+  Event ring_done[kRing];
   bool ring_used[kRing] = {false, false, false, false};
   unsigned ring_k = 0;
   // NUMA placement of the host side (adsb_numa_info): the node and cpus local to the GPU's PCI device, from sysfs
@@ -378,7 +404,7 @@ struct adsb_ctx {
   char cpulist[256] = {0};
   cpu_set_t local_cpus;
   bool have_local_cpus = false;
-  CopyPool* pool = nullptr;    // host copy threads of the pageable path (adsb_set_copy_threads; created on first use)
+  std::unique_ptr<CopyPool> pool;   // host copy threads of the pageable path (adsb_set_copy_threads; created on first use)
   int copy_threads = -1;       // -1 = default
   adsb_stats stats{};
   // per-launch k_detect durations of the timed calls (ADSB_FLAG_TIMING), a ring of the last kHist: adsb_detect_history
@@ -386,21 +412,21 @@ struct adsb_ctx {
   std::vector<float> det_hist;
   uint64_t det_hist_n = 0;
   // ADSB_FLAG_AIRCRAFT_TABLE: 2^24 first-announcement keys, the step state, and the event behind the last table step queued
-  unsigned long long* d_air = nullptr;
-  AirState* d_air_st = nullptr;
-  hipEvent_t air_ev = nullptr;
+  DevPtr<unsigned long long> d_air;
+  DevPtr<AirState> d_air_st;
+  Event air_ev;
   unsigned long long air_next = 0;    // number of the next published pass (table keys: number << 32 | position)
   // ADSB_FLAG_DECODE: the plane state of every address, the epoch that marks an entry valid, the decoder's settings, and
   // the sort's buffers (one decode step runs at a time: the table step's event chain orders them)
-  Plane* d_planes = nullptr;
+  DevPtr<Plane> d_planes;
   unsigned dec_epoch = 1;
   int dec_all = 1;
   double dec_start = 0;
   DevBuf d_dec_keys, d_dec_sorted, d_dec_tmp;
-  void* h_pdu = nullptr;              // adsb_decode_pdus' staging (pinned, device-visible)
-  size_t h_pdu_cap = 0;
+  PinnedBuf h_pdu;                    // adsb_decode_pdus' staging (device-visible)
   BatchBufs bt;                       // adsb_process_batch*
   char err[256] = {0};
+  __attribute__((visibility("hidden"))) ~adsb_ctx() = default;   // (the library's exported names stay its C entry points)
 };
 
 namespace {
@@ -432,7 +458,8 @@ int fail(adsb_ctx* c, int code, const char* what, hipError_t he = hipSuccess) {
 
 int ensure(adsb_ctx* c, DevBuf& b, size_t bytes) {
   if (bytes <= b.cap) return 0;
-  if (b.p) { HIPCHK(c, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
+  const hipError_t e = b.release();
+  if (e != hipSuccess) return fail(c, -EIO, "hipFree(b.p)", e);
   size_t want = bytes + bytes / 4 + 256;
   HIPCHK(c, hipMalloc(&b.p, want));
   b.cap = want;
@@ -516,12 +543,25 @@ void probe_numa(adsb_ctx* c) {
   }
 }
 
-int ensure_pinned(adsb_ctx* c, void*& p, size_t& cap, size_t bytes, bool coherent = false) {
-  if (bytes <= cap) return 0;
-  if (p) { HIPCHK(c, hipHostFree(p)); p = nullptr; cap = 0; }
+int ensure_pinned(adsb_ctx* c, PinnedBuf& b, size_t bytes, bool coherent = false) {
+  if (bytes <= b.cap) return 0;
+  const hipError_t e = b.release();
+  if (e != hipSuccess) return fail(c, -EIO, "hipHostFree(p)", e);
   size_t want = bytes + bytes / 4 + 4096;
-  HIPCHK(c, host_alloc_near(c, &p, want, coherent));
-  cap = want;
+  HIPCHK(c, host_alloc_near(c, &b.p, want, coherent));
+  b.cap = want;
+  return 0;
+}
+
+// Workgroups of a per-record step: ceil(n / per), at least one, at most kMaxStepGrid.  (adsb_decode_pdus and adsb_demod_work
+// had no floor of one: they return before the launch when n == 0, so the value is the same.)
+constexpr long long kMaxStepGrid = 2048;
+unsigned step_grid(long long n, int per) { return (unsigned)std::max(1ll, std::min(kMaxStepGrid, (n + per - 1) / per)); }
+
+// Nothing runs while a submitted call is pending: -EBUSY with the caller's text (on `err_to` where that is another context).
+const char* const kCallPending = "a submitted call is still pending (adsb_wait first)";
+int require_idle(adsb_ctx* c, const char* text, adsb_ctx* err_to = nullptr) {
+  for (const Slot& sl : c->slot) if (sl.busy) return fail(err_to ? err_to : c, -EBUSY, text);
   return 0;
 }
 
@@ -600,14 +640,11 @@ void launch_confidence(hipStream_t st, int grid, const DetectArgs& a, const Rec*
   hipLaunchKernelGGL((k_confidence<MODE>), dim3(grid), dim3(kThreads), 0, st, a, out, sum, cap, ratio);
 }
 
-// opt-in Conservative FEC (ADSB_FLAG_FEC_CONSERVATIVE) of a pass's records, in place: one thread per list slot up to 2048
-// workgroups, each leaves at once past sum->n_kept
+// opt-in Conservative FEC (ADSB_FLAG_FEC_CONSERVATIVE) of a pass's records, in place: one thread per list slot (step_grid),
+// each leaves at once past sum->n_kept
 void launch_fec(hipStream_t st, const Slot& s, Rec* out, const Summary* sum) {
-  long long g = (s.tot + kThreads - 1) / kThreads;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  hipLaunchKernelGGL(k_fec, dim3((unsigned)g), dim3(kThreads), 0, st, out, sum, (int)s.tot,
-                     (Rec*)(s.host_cap > 0 ? s.h_out : nullptr), s.host_cap);
+  hipLaunchKernelGGL(k_fec, dim3(step_grid(s.tot, kThreads)), dim3(kThreads), 0, st, out, sum, (int)s.tot,
+                     (Rec*)(s.host_cap > 0 ? s.h_out.p : nullptr), s.host_cap);
 }
 
 // opt-in aircraft table (ADSB_FLAG_AIRCRAFT_TABLE): the table step of one published pass (list: out / mirror / sum; slices:
@@ -689,7 +726,7 @@ __global__ void __launch_bounds__(kThreads) k_dec_sort_scatter(const unsigned lo
 
 // ADSB_FLAG_DECODE: the decode step of the same records, behind the last verdict (rows: cap rows; ts: the slices'
 // timestamps, null for a pass's list).  The sort's buffers are the context's: every decode step waits for the one before.
-int launch_dec(adsb_ctx* c, hipStream_t st, const AirArgs& a, long long g, DecRow* rows, const double* ts) {
+int launch_dec(adsb_ctx* c, hipStream_t st, const AirArgs& a, unsigned g, DecRow* rows, const double* ts) {
   const size_t n = (size_t)a.cap;
   if (n == 0) return 0;
   const int nblk = (int)((n + kSortTile - 1) / kSortTile);
@@ -702,7 +739,7 @@ int launch_dec(adsb_ctx* c, hipStream_t st, const AirArgs& a, long long g, DecRo
   DecArgs d{};
   d.air = a; d.ts = ts; d.start = c->dec_start; d.fs = c->fs; d.planes = c->d_planes; d.epoch = c->dec_epoch; d.all = c->dec_all;
   d.keys = (unsigned long long*)c->d_dec_keys.p; d.sorted = (const unsigned long long*)c->d_dec_sorted.p; d.rows = rows;
-  hipLaunchKernelGGL(k_dec_classify, dim3((unsigned)g), dim3(kThreads), 0, st, d);
+  hipLaunchKernelGGL(k_dec_classify, dim3(g), dim3(kThreads), 0, st, d);
   unsigned long long* in = (unsigned long long*)c->d_dec_keys.p;
   unsigned long long* out = (unsigned long long*)c->d_dec_sorted.p;
   for (int shift = 32; shift < 60; shift += 4) {          // seven passes: the result ends in d_dec_sorted
@@ -713,20 +750,18 @@ int launch_dec(adsb_ctx* c, hipStream_t st, const AirArgs& a, long long g, DecRo
                        (const unsigned*)c->d_dec_tmp.p);
     unsigned long long* x = in; in = out; out = x;
   }
-  hipLaunchKernelGGL(k_dec_fold, dim3((unsigned)g), dim3(kThreads), 0, st, d);
+  hipLaunchKernelGGL(k_dec_fold, dim3(g), dim3(kThreads), 0, st, d);
   return 0;
 }
 
 int launch_air(adsb_ctx* c, hipStream_t st, AirArgs a, long long tot, DecRow* rows = nullptr, const double* ts = nullptr) {
   HIPCHK(c, hipStreamWaitEvent(st, c->air_ev, 0));
-  long long g = (tot + kThreads - 1) / kThreads;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
+  const unsigned g = step_grid(tot, kThreads);
   a.table = c->d_air; a.st = c->d_air_st; a.fec = (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) ? 1 : 0;
-  hipLaunchKernelGGL(k_air_announce, dim3((unsigned)g), dim3(kThreads), 0, st, a);
-  hipLaunchKernelGGL(k_air_verdict, dim3((unsigned)g), dim3(kThreads), 0, st, a, 0);
+  hipLaunchKernelGGL(k_air_announce, dim3(g), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(k_air_verdict, dim3(g), dim3(kThreads), 0, st, a, 0);
   hipLaunchKernelGGL(k_air_cond, dim3(1), dim3(64), 0, st, a);
-  hipLaunchKernelGGL(k_air_verdict, dim3((unsigned)g), dim3(kThreads), 0, st, a, 1);
+  hipLaunchKernelGGL(k_air_verdict, dim3(g), dim3(kThreads), 0, st, a, 1);
   if (c->flags & ADSB_FLAG_DECODE) { int r = launch_dec(c, st, a, g, rows, ts); if (r) return r; }
   HIPCHK(c, hipEventRecord(c->air_ev, st));
   return 0;
@@ -734,14 +769,14 @@ int launch_air(adsb_ctx* c, hipStream_t st, AirArgs a, long long tot, DecRow* ro
 
 int launch_air_pass(adsb_ctx* c, Slot& s, hipStream_t st, Rec* out, int force = 0) {
   AirArgs a{};
-  a.out = out; a.mirror = (out != (Rec*)s.h_out && s.host_cap > 0) ? (Rec*)s.h_out : nullptr;
+  a.out = out; a.mirror = (out != (Rec*)s.h_out.p && s.host_cap > 0) ? (Rec*)s.h_out.p : nullptr;
   a.mirror_cap = a.mirror ? s.host_cap : 0;
   a.sum = &((Misc*)s.d_misc.p)->sum; a.cap = (int)s.tot; a.host_sum = s.h_sum; a.pass = s.air_pass; a.force = force;
   if (c->flags & ADSB_FLAG_DECODE) {
-    int r = ensure_pinned(c, s.h_dec, s.h_dec_cap, (size_t)s.tot * sizeof(DecRow));
+    int r = ensure_pinned(c, s.h_dec, (size_t)s.tot * sizeof(DecRow));
     if (r) return r;
   }
-  return launch_air(c, st, a, s.tot, (DecRow*)s.h_dec, nullptr);
+  return launch_air(c, st, a, s.tot, (DecRow*)s.h_dec.p, nullptr);
 }
 
 // the step state's `broken` word cleared behind every table step queued so far (before a pass that overflowed is re-run)
@@ -787,7 +822,7 @@ int enqueue_tail(adsb_ctx* c, Slot& s) {
     t.cands = a.cands; t.recs = a.recs; t.blk_count = a.blk_count; t.blk_lastp = a.blk_lastp; t.blk_flags = a.blk_flags;
     t.blk_off = (int*)s.d_blk_off.p; t.nblk = s.nlists; t.rec_cap = s.rec_cap; t.long_count = a.long_count;
     t.long_lastp = a.long_lastp; t.sorted = (unsigned long long*)s.d_sorted.p; t.sorted_src = (unsigned*)s.d_sorted_src.p;
-    t.seg_count = (int*)s.d_seg.p; t.sum = &misc->sum; t.host_sum = s.h_sum; t.out = (Rec*)s.h_out; t.out_cap = (int)s.tot;
+    t.seg_count = (int*)s.d_seg.p; t.sum = &misc->sum; t.host_sum = s.h_sum; t.out = (Rec*)s.h_out.p; t.out_cap = (int)s.tot;
     t.gate_on = pl.gate ? 1 : 0; t.head_n = pl.head_n; t.gate = 63ll * c->sps;
     t.gate_long = (long long)(pl.long_aware ? 119 : 63) * c->sps; t.prev_eob = pl.prev_eob_stream - pl.origin;
     s.seq = s.seq >= 0x7FFFFFF0 ? 1 : s.seq + 1;
@@ -797,8 +832,8 @@ int enqueue_tail(adsb_ctx* c, Slot& s) {
     if (c->flags & (ADSB_FLAG_FEC_CONSERVATIVE | ADSB_FLAG_AIRCRAFT_TABLE)) {
       // the repair / the table step follow the published pass number: the host waits for the event behind them instead
       // of polling
-      if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) launch_fec(ts, s, (Rec*)s.h_out, &misc->sum);
-      if (pl.air) { int r_ = launch_air_pass(c, s, ts, (Rec*)s.h_out); if (r_) return r_; }
+      if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) launch_fec(ts, s, (Rec*)s.h_out.p, &misc->sum);
+      if (pl.air) { int r_ = launch_air_pass(c, s, ts, (Rec*)s.h_out.p); if (r_) return r_; }
       HIPCHK(c, hipEventRecord(s.done, ts));
       return 0;
     }
@@ -841,8 +876,8 @@ int enqueue_tail(adsb_ctx* c, Slot& s) {
   // k_compact's workgroup 0 stores the summary straight into s.h_sum (pinned host memory, device-visible): visible to the
   // host once the `done` event below has completed
   hipLaunchKernelGGL(k_compact, dim3(ag), dim3(kThreads), 0, ts, (const unsigned long long*)sorted, (const Rec*)a.recs, (const unsigned*)sorted_src,
-                     &misc->sum, (const int*)s.d_seg.p, fmask, fwant, pl.head_n, (Rec*)(s.direct ? s.h_out : s.d_out.p), (int)s.tot,
-                     a.long_count, a.long_lastp, &misc->acc, s.h_sum, (Rec*)(s.host_cap > 0 ? s.h_out : nullptr), s.host_cap);
+                     &misc->sum, (const int*)s.d_seg.p, fmask, fwant, pl.head_n, (Rec*)(s.direct ? s.h_out.p : s.d_out.p), (int)s.tot,
+                     a.long_count, a.long_lastp, &misc->acc, s.h_sum, (Rec*)(s.host_cap > 0 ? s.h_out.p : nullptr), s.host_cap);
   if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) launch_fec(ts, s, (Rec*)s.d_out.p, &misc->sum);
   if (pl.air) { int r_ = launch_air_pass(c, s, ts, (Rec*)s.d_out.p); if (r_) return r_; }
   HIPCHK(c, hipEventRecord(s.done, ts));
@@ -850,7 +885,7 @@ int enqueue_tail(adsb_ctx* c, Slot& s) {
 }
 
 // Queue the whole device pipeline of one plan on the compute stream; nothing here waits for the GPU.
-int enqueue(adsb_ctx* c, Slot& s, const Plan& pl, bool submitted) {
+int enqueue_pass(adsb_ctx* c, Slot& s, const Plan& pl, bool submitted) {
   HIPCHK(c, hipSetDevice(c->device));
   s.plan = pl;
   // the queue(s) of this pass (see adsb_ctx): a submitted pass on the slot's own stream; a blocking one alone on the
@@ -929,11 +964,11 @@ int enqueue(adsb_ctx* c, Slot& s, const Plan& pl, bool submitted) {
   // records are megabytes, the DMA engine moves them beside the next pass's kernels.
   const long long kMidTiles = 65536, kHostRecs = 32768;
   s.host_cap = 0;
-  if (s.direct) { if ((r = ensure_pinned(c, s.h_out, s.h_out_cap, (size_t)s.tot * sizeof(Rec), true))) return r; }
+  if (s.direct) { if ((r = ensure_pinned(c, s.h_out, (size_t)s.tot * sizeof(Rec), true))) return r; }
   else {
     if ((r = ensure(c, s.d_out, (size_t)s.tot * sizeof(Rec)))) return r;
     if (ntiles <= kMidTiles) {
-      if ((r = ensure_pinned(c, s.h_out, s.h_out_cap, (size_t)kHostRecs * sizeof(Rec), true))) return r;
+      if ((r = ensure_pinned(c, s.h_out, (size_t)kHostRecs * sizeof(Rec), true))) return r;
       s.host_cap = (int)kHostRecs;
     }
   }
@@ -976,6 +1011,23 @@ int enqueue(adsb_ctx* c, Slot& s, const Plan& pl, bool submitted) {
   s.polled = false;
   return enqueue_tail(c, s);
 }
+// ... and a pass that could not be queued leaves its slot free: no caller has a ticket to release
+int enqueue(adsb_ctx* c, Slot& s, const Plan& pl, bool submitted) {
+  const int r = enqueue_pass(c, s, pl, submitted);
+  if (r) s.busy = false;
+  return r;
+}
+
+// The pass's lists overflowed: the capacity multiplier grows and the pass is queued again (one call: not counted twice).
+int requeue_grown(adsb_ctx* c, Slot& s) {
+  if ((long long)s.rec_cap >= s.chunk / 2 + 8) return fail(c, -EIO, "centre list overflow at maximum size");
+  c->rec_cap_shift++;
+  c->stats.retries++;
+  const int r = enqueue(c, s, s.plan, s.submitted);
+  if (r) return r;
+  c->stats.calls--;
+  return 0;
+}
 
 // Wait for a queued call; handle the two rare outcomes that need a second pass (pulses longer than the
 // LDS window; per-workgroup list overflow); bring the records to pinned host memory.
@@ -1001,18 +1053,14 @@ int air_settle_all(adsb_ctx* c) {
       const hipStream_t ts = s.direct ? s.ds : s.cs;
       int r;
       if (s.h_sum->overflow) {
-        if ((long long)s.rec_cap >= s.chunk / 2 + 8) return fail(c, -EIO, "centre list overflow at maximum size");
-        c->rec_cap_shift++;
-        c->stats.retries++;
         if ((r = air_unbreak(c, ts))) return r;
         s.air_keep = true;
-        if ((r = enqueue(c, s, s.plan, s.submitted))) return r;
-        c->stats.calls--;
+        if ((r = requeue_grown(c, s))) return r;
         continue;
       }
       if (s.h_sum->flags & kAirSkipped) {
         s.h_sum->flags &= ~kAirSkipped;
-        if ((r = launch_air_pass(c, s, ts, (Rec*)(s.direct ? s.h_out : s.d_out.p), 1))) return r;
+        if ((r = launch_air_pass(c, s, ts, (Rec*)(s.direct ? s.h_out.p : s.d_out.p), 1))) return r;
         HIPCHK(c, hipEventRecord(s.done, ts));
         continue;
       }
@@ -1022,14 +1070,8 @@ int air_settle_all(adsb_ctx* c) {
   return 0;
 }
 
-int finish(adsb_ctx* c, Slot& s, Summary* sum, int32_t* n_res) {
-  // every error exit releases the slot: a failed call must not leave its ticket busy for good
-#define FINCHK(call)                                                           \
-  do {                                                                         \
-    hipError_t e_ = (call);                                                    \
-    if (e_ != hipSuccess) { s.busy = false; return fail(c, -EIO, #call, e_); } \
-  } while (0)
-  FINCHK(hipSetDevice(c->device));
+int finish_pass(adsb_ctx* c, Slot& s, Summary* sum, int32_t* n_res) {
+  HIPCHK(c, hipSetDevice(c->device));
   const bool timing = (c->flags & ADSB_FLAG_TIMING) != 0;
   for (int attempt = 0; attempt < 16; ++attempt) {
     if (s.polled) {
@@ -1047,23 +1089,23 @@ int finish(adsb_ctx* c, Slot& s, Summary* sum, int32_t* n_res) {
       }
       std::atomic_thread_fence(std::memory_order_acquire);
       if (*seqp != s.seq) {
-        FINCHK(hipStreamSynchronize(s.ds));
-        FINCHK(hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(s.ds));
+        HIPCHK(c, hipGetLastError());
         std::atomic_thread_fence(std::memory_order_acquire);
-        if (*seqp != s.seq) { s.busy = false; return fail(c, -EIO, "small pass finished without publishing its summary"); }
+        if (*seqp != s.seq) return fail(c, -EIO, "small pass finished without publishing its summary");
         c->stats.poll_fallbacks++;
       }
     } else {
-      FINCHK(hipEventSynchronize(s.done));
-      FINCHK(hipGetLastError());
+      HIPCHK(c, hipEventSynchronize(s.done));
+      HIPCHK(c, hipGetLastError());
       if (s.plan.air && (s.h_sum->overflow || (s.h_sum->flags & kAirSkipped))) {
         int r_ = air_settle_all(c);
-        if (r_) { s.busy = false; return r_; }
+        if (r_) return r_;
       }
     }
     if (timing) {
       float ms = 0;
-      FINCHK(hipEventElapsedTime(&ms, s.ev0, s.ev1));
+      HIPCHK(c, hipEventElapsedTime(&ms, s.ev0, s.ev1));
       c->stats.detect_launches++;
       c->stats.detect_ms += ms;
       if (c->det_hist.size() < (size_t)adsb_ctx::kHist) c->det_hist.resize(adsb_ctx::kHist);
@@ -1083,24 +1125,20 @@ int finish(adsb_ctx* c, Slot& s, Summary* sum, int32_t* n_res) {
       c->stats.detect_bytes += (uint64_t)s.span * (uint64_t)mode_bytes(s.plan.mode);
     }
     if (s.h_sum->overflow) {
-      if ((long long)s.rec_cap >= s.chunk / 2 + 8) { s.busy = false; return fail(c, -EIO, "centre list overflow at maximum size"); }
-      c->rec_cap_shift++;
-      c->stats.retries++;
-      int r = enqueue(c, s, s.plan, s.submitted);
-      if (r) { s.busy = false; return r; }
-      c->stats.calls--;
+      int r = requeue_grown(c, s);
+      if (r) return r;
       continue;
     }
     if (s.h_sum->long_count > 0) { c->stats.longrun_calls++; c->stats.longrun_pulses += (uint64_t)s.h_sum->long_count; }
-    if (s.h_sum->long_count > s.args.long_cap) { s.busy = false; return fail(c, -EIO, "long-rise list overflow"); }
+    if (s.h_sum->long_count > s.args.long_cap) return fail(c, -EIO, "long-rise list overflow");
     *sum = *s.h_sum;
     const int nres = sum->n_kept;
     // the records are already in h_out: a one-workgroup pass (all of them), or a mid-size pass that delivered no more than
     // k_compact stored there beside d_out (enqueue)
-    const bool in_host = (s.direct || nres <= s.host_cap) && s.h_out != nullptr;
-    int r = in_host ? 0 : ensure_pinned(c, s.h_out, s.h_out_cap, (size_t)(nres > 0 ? nres : 1) * sizeof(Rec), true);
-    if (r) { s.busy = false; return r; }
-    const Rec* recs_dev = (const Rec*)(s.direct ? s.h_out : s.d_out.p);
+    const bool in_host = (s.direct || nres <= s.host_cap) && s.h_out.p != nullptr;
+    int r = in_host ? 0 : ensure_pinned(c, s.h_out, (size_t)(nres > 0 ? nres : 1) * sizeof(Rec), true);
+    if (r) return r;
+    const Rec* recs_dev = (const Rec*)(s.direct ? s.h_out.p : s.d_out.p);
     if (nres > 0 && (!in_host || (c->flags & ADSB_FLAG_CONFIDENCE))) {
       // on the pass's own stream (idle: its last kernel has completed); never on a caller-owned one
       // (a submitted pass that shares its stream with the passes behind it -- kernels in line, or ADSB_FLAG_SINGLE_STREAM --
@@ -1113,42 +1151,45 @@ int finish(adsb_ctx* c, Slot& s, Summary* sum, int32_t* n_res) {
       const bool shared = s.ds != s.cs || (s.submitted && !c->split_tail);
       const Slot& s2 = c->slot[2];
       const bool slot2_taken = &s2 != &s && s2.busy && s2.ds == s2.stream;
-      if (c->own_stream && shared && slot2_taken && !c->d2h_stream) FINCHK(hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking));
-      const hipStream_t xs = !c->own_stream ? c->copy_stream : (shared ? (slot2_taken ? c->d2h_stream : c->slot[2].stream) : s.cs);
+      if (c->own_stream && shared && slot2_taken && !c->d2h_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->d2h_stream.p, hipStreamNonBlocking));
+      const hipStream_t xs = !c->own_stream ? c->copy_stream.p : (shared ? (slot2_taken ? c->d2h_stream.p : c->slot[2].stream.p) : s.cs);
       if (!in_host)
-        FINCHK(hipMemcpyAsync(s.h_out, s.d_out.p, (size_t)nres * sizeof(Rec), hipMemcpyDeviceToHost, xs));
+        HIPCHK(c, hipMemcpyAsync(s.h_out.p, s.d_out.p, (size_t)nres * sizeof(Rec), hipMemcpyDeviceToHost, xs));
       if (c->flags & ADSB_FLAG_CONFIDENCE) {
         // opt-in (demod.py:97-101): bit1/bit0 ratios of the delivered records, computed now that their number is
         // known -- one more small kernel and copy on the copy stream, paid only by callers who ask for it
         const size_t rb = (size_t)nres * 112 * sizeof(float);
-        if ((r = ensure(c, s.d_ratio, rb)) || (r = ensure_pinned(c, s.h_ratio, s.h_ratio_cap, rb))) { s.busy = false; return r; }
-        FINCHK(hipMemsetAsync(s.d_ratio.p, 0, rb, xs));
+        if ((r = ensure(c, s.d_ratio, rb)) || (r = ensure_pinned(c, s.h_ratio, rb))) return r;
+        HIPCHK(c, hipMemsetAsync(s.d_ratio.p, 0, rb, xs));
         int cg = (nres + kWaves - 1) / kWaves;
         if (cg > c->n_cu * 8) cg = c->n_cu * 8;
         ADSB_BY_MODE(s.plan.mode, launch_confidence, xs, cg, s.args, recs_dev,
                      (const Summary*)&((Misc*)s.d_misc.p)->sum, nres, (float*)s.d_ratio.p);
-        FINCHK(hipMemcpyAsync(s.h_ratio, s.d_ratio.p, rb, hipMemcpyDeviceToHost, xs));
+        HIPCHK(c, hipMemcpyAsync(s.h_ratio.p, s.d_ratio.p, rb, hipMemcpyDeviceToHost, xs));
       }
-      FINCHK(hipStreamSynchronize(xs));
-      FINCHK(hipGetLastError());
+      HIPCHK(c, hipStreamSynchronize(xs));
+      HIPCHK(c, hipGetLastError());
     }
     s.nres = nres;
     *n_res = nres;
-    s.busy = false;
     return 0;
   }
-  s.busy = false;
   return fail(c, -EIO, "centre list capacity did not converge");
-#undef FINCHK
+}
+// ... and the slot is free afterwards, whatever came of the call: a failed call must not leave its ticket busy for good
+int finish(adsb_ctx* c, Slot& s, Summary* sum, int32_t* n_res) {
+  const int r = finish_pass(c, s, sum, n_res);
+  s.busy = false;
+  return r;
 }
 
 // Synchronous form used by every blocking entry point.
 int run_pipeline(adsb_ctx* c, const Plan& pl, Summary* sum, int32_t* n_res) {
-  for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
+  int r = require_idle(c, kCallPending);
+  if (r) return r;
   Slot& s = c->slot[0];
   c->last_slot = 0;
-  int r = enqueue(c, s, pl, false);
-  if (r) { s.busy = false; return r; }
+  if ((r = enqueue(c, s, pl, false))) return r;
   return finish(c, s, sum, n_res);
 }
 
@@ -1156,7 +1197,7 @@ int deliver(adsb_ctx* c, int32_t nres, adsb_burst* out, int32_t cap, int32_t* n_
   if (n_out) *n_out = nres;
   if (out) {
     if (nres > cap) return fail(c, -ENOSPC, "output array too small");
-    if (nres > 0) memcpy(out, c->slot[c->last_slot].h_out, (size_t)nres * sizeof(adsb_burst));
+    if (nres > 0) memcpy(out, c->slot[c->last_slot].h_out.p, (size_t)nres * sizeof(adsb_burst));
   }
   return 0;
 }
@@ -1193,7 +1234,7 @@ const void* device_alias(const void* host) {
 
 int ensure_pool(adsb_ctx* c) {
   if (c->pool) return 0;
-  c->pool = new (std::nothrow) CopyPool();
+  c->pool.reset(new (std::nothrow) CopyPool());
   if (!c->pool) return fail(c, -ENOMEM, "copy pool");
   const unsigned hw = std::thread::hardware_concurrency();
   const int nt = c->copy_threads >= 0 ? c->copy_threads : (hw >= 16 ? 5 : (hw >= 4 ? 2 : 0));     // workers besides the caller
@@ -1215,8 +1256,8 @@ int ensure_pool(adsb_ctx* c) {
 // over the context's copy threads) runs beside the DMA of chunk k.  Returns once the last DMA is QUEUED.
 int staged_copy(adsb_ctx* c, void* d_dst, const void* host, size_t bytes, hipStream_t stream) {
   constexpr size_t kRingChunk = (size_t)16 << 20;
-  for (void*& r : c->h_ring)
-    if (!r) HIPCHK(c, host_alloc_near(c, &r, kRingChunk));      // the staging ring: on the GPU's NUMA node
+  for (PinnedPtr<void>& r : c->h_ring)
+    if (!r) HIPCHK(c, host_alloc_near(c, &r.p, kRingChunk));    // the staging ring: on the GPU's NUMA node
   int rc = ensure_pool(c);
   if (rc) return rc;
   // the host copy of piece k+1 runs beside the DMA of piece k: a source of a few megabytes (a GNU Radio work() call of a
@@ -1227,7 +1268,7 @@ int staged_copy(adsb_ctx* c, void* d_dst, const void* host, size_t bytes, hipStr
     const size_t m = bytes - off < kChunk ? bytes - off : kChunk;
     const int b = (int)(c->ring_k++ % (unsigned)adsb_ctx::kRing);
     if (c->ring_used[b]) HIPCHK(c, hipEventSynchronize(c->ring_done[b]));      // the chunk's previous DMA has read it
-    c->pool->copy((char*)c->h_ring[b], (const char*)host + off, m);
+    c->pool->copy((char*)c->h_ring[b].p, (const char*)host + off, m);
     HIPCHK(c, hipMemcpyAsync((char*)d_dst + off, c->h_ring[b], m, hipMemcpyHostToDevice, stream));
     HIPCHK(c, hipEventRecord(c->ring_done[b], stream));
     c->ring_used[b] = true;
@@ -1256,10 +1297,10 @@ int upload(adsb_ctx* c, const void* host, size_t bytes, void** d_out) {
     return 0;
   }
   if (!pinned || (small && (!alias || ((uintptr_t)alias & 15u) != 0))) {
-    if ((rc = ensure_pinned(c, c->h_stage, c->h_stage_cap, bytes))) return rc;
-    memcpy(c->h_stage, host, bytes);
-    src = c->h_stage;
-    alias = c->h_stage;                                   // hipHostMalloc'ed: one address on both sides
+    if ((rc = ensure_pinned(c, c->h_stage, bytes))) return rc;
+    memcpy(c->h_stage.p, host, bytes);
+    src = c->h_stage.p;
+    alias = c->h_stage.p;                                   // hipHostMalloc'ed: one address on both sides
   }
   if (small) {
     *d_out = const_cast<void*>(alias);
@@ -1296,8 +1337,7 @@ int check_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_it
     if (items[i].n > 0 && !items[i].data) return fail(c, -EINVAL, "adsb_process_batch: item.data is NULL");
     if (((uintptr_t)items[i].data & 15u) != 0) return fail(c, -EINVAL, "adsb_process_batch: item.data must be 16-byte aligned");
   }
-  for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
-  return 0;
+  return require_idle(c, kCallPending);
 }
 
 // the dense list and item_first are 32-bit: a batch whose lists have 2^31 slots or more is refused
@@ -1342,15 +1382,15 @@ int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_item
   if ((r = ensure(c, B.d_kept, (size_t)n_items * sizeof(int)))) return r;
   if ((r = ensure(c, B.d_packed, (size_t)(packed_cap + 1) * sizeof(Rec)))) return r;
   if ((r = ensure(c, B.d_tot, sizeof(Summary)))) return r;
-  if ((r = ensure_pinned(c, B.h_tab, B.h_tab_cap, tab_bytes))) return r;
-  if ((r = ensure_pinned(c, B.h_first, B.h_first_cap, (size_t)(2 * (size_t)n_items + 1) * sizeof(int), true))) return r;
-  if ((r = ensure_pinned(c, B.h_out, B.h_out_cap, (size_t)kHostRecs * sizeof(Rec), true))) return r;
-  long long host_cap = (long long)(B.h_out_cap / sizeof(Rec));
+  if ((r = ensure_pinned(c, B.h_tab, tab_bytes))) return r;
+  if ((r = ensure_pinned(c, B.h_first, (size_t)(2 * (size_t)n_items + 1) * sizeof(int), true))) return r;
+  if ((r = ensure_pinned(c, B.h_out, (size_t)kHostRecs * sizeof(Rec), true))) return r;
+  long long host_cap = (long long)(B.h_out.cap / sizeof(Rec));
   if (host_cap > kHostRecs) host_cap = kHostRecs;
 
-  DetectArgs* hda = (DetectArgs*)B.h_tab;
-  TailArgs* hta = (TailArgs*)((char*)B.h_tab + (size_t)n_items * sizeof(DetectArgs));
-  memset(B.h_tab, 0, tab_bytes);
+  DetectArgs* hda = (DetectArgs*)B.h_tab.p;
+  TailArgs* hta = (TailArgs*)((char*)B.h_tab.p + (size_t)n_items * sizeof(DetectArgs));
+  memset(B.h_tab.p, 0, tab_bytes);
   char* const sc = (char*)B.d_scratch.p;
   BatchFixed* const fx = (BatchFixed*)B.d_fixed.p;
   const bool long_aware = (c->flags & ADSB_FLAG_LONG_AWARE_GATE) != 0;
@@ -1364,18 +1404,15 @@ int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_item
   HIPCHK(c, hipMemcpyAsync(B.d_da.p, hda, (size_t)n_items * sizeof(DetectArgs), hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(B.d_ta.p, hta, (size_t)n_items * sizeof(TailArgs), hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemsetAsync(B.d_fixed.p, 0, (size_t)n_items * sizeof(BatchFixed), st));
-  int* const h_first = (int*)B.h_first;
+  int* const h_first = (int*)B.h_first.p;
   int* const h_kept = h_first + n_items + 1;
   ADSB_BY_MODE(fmt, launch_batch, st, c->sps, (int)n_items, (const DetectArgs*)B.d_da.p, (const TailArgs*)B.d_ta.p, (int*)B.d_kept.p);
   hipLaunchKernelGGL(k_batch_pack, dim3(n_items), dim3(kThreads), 0, st, (const TailArgs*)B.d_ta.p, (const int*)B.d_kept.p,
-                     (int)n_items, (Rec*)B.d_packed.p, (int)packed_cap, h_first, h_kept, (Summary*)B.d_tot.p, (Rec*)B.h_out,
+                     (int)n_items, (Rec*)B.d_packed.p, (int)packed_cap, h_first, h_kept, (Summary*)B.d_tot.p, (Rec*)B.h_out.p,
                      (int)host_cap);
   if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) {
-    long long g = (packed_cap + kThreads - 1) / kThreads;
-    if (g > 2048) g = 2048;
-    if (g < 1) g = 1;
-    hipLaunchKernelGGL(k_fec, dim3((unsigned)g), dim3(kThreads), 0, st, (Rec*)B.d_packed.p, (const Summary*)B.d_tot.p,
-                       (int)packed_cap, (Rec*)B.h_out, (int)host_cap);
+    hipLaunchKernelGGL(k_fec, dim3(step_grid(packed_cap, kThreads)), dim3(kThreads), 0, st, (Rec*)B.d_packed.p,
+                       (const Summary*)B.d_tot.p, (int)packed_cap, (Rec*)B.h_out.p, (int)host_cap);
   }
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(st));
@@ -1384,11 +1421,11 @@ int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_item
   const long long nb = h_first[n_items];
   if (nb < 0 || nb > packed_cap) return fail(c, -EIO, "adsb_process_batch: the pack step returned nonsense");
   if (nb > host_cap) {
-    if ((r = ensure_pinned(c, B.h_out, B.h_out_cap, (size_t)nb * sizeof(Rec), true))) return r;
-    HIPCHK(c, hipMemcpyAsync(B.h_out, B.d_packed.p, (size_t)nb * sizeof(Rec), hipMemcpyDeviceToHost, st));
+    if ((r = ensure_pinned(c, B.h_out, (size_t)nb * sizeof(Rec), true))) return r;
+    HIPCHK(c, hipMemcpyAsync(B.h_out.p, B.d_packed.p, (size_t)nb * sizeof(Rec), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
   }
-  const adsb_burst* const packed = (const adsb_burst*)B.h_out;
+  const adsb_burst* const packed = (const adsb_burst*)B.h_out.p;
   int32_t nfb = 0;
   for (int32_t i = 0; i < n_items; ++i) nfb += h_kept[i] < 0 ? 1 : 0;
   if (n_fallback) *n_fallback = nfb;
@@ -1420,10 +1457,9 @@ int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_item
     int32_t nres = 0;
     c->thr = items[i].threshold;
     rc = enqueue(c, fs, pl, false);
-    if (rc) fs.busy = false;
-    else rc = finish(c, fs, &s, &nres);
+    if (rc == 0) rc = finish(c, fs, &s, &nres);
     if (rc == 0 && nres > 0) {
-      const adsb_burst* src = (const adsb_burst*)fs.h_out;
+      const adsb_burst* src = (const adsb_burst*)fs.h_out.p;
       fb[(size_t)k].assign(src, src + nres);
     }
     fb_of[(size_t)i] = k++;
@@ -1494,13 +1530,13 @@ int upload_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_i
     }
     if (cur >= 0 && o + bytes - cur_lo > kRingChunk) { if ((rc = flush())) return rc; }
     if (cur < 0) {
-      for (void*& rg : c->h_ring)
-        if (!rg) HIPCHK(c, host_alloc_near(c, &rg, kRingChunk));
+      for (PinnedPtr<void>& rg : c->h_ring)
+        if (!rg) HIPCHK(c, host_alloc_near(c, &rg.p, kRingChunk));
       cur = (int)(c->ring_k++ % (unsigned)adsb_ctx::kRing);
       if (c->ring_used[cur]) HIPCHK(c, hipEventSynchronize(c->ring_done[cur]));     // the chunk's previous DMA has read it
       cur_lo = o;
     }
-    c->pool->copy((char*)c->h_ring[cur] + (o - cur_lo), (const char*)items[i].data, bytes);     // (the context's copy threads)
+    c->pool->copy((char*)c->h_ring[cur].p + (o - cur_lo), (const char*)items[i].data, bytes);     // (the context's copy threads)
     cur_hi = o + bytes;
   }
   return flush();
@@ -1684,34 +1720,35 @@ int adsb_create(double fs, float threshold, int device, uint32_t flags, adsb_ctx
   c->own_stream = true;
   // submitted passes overlap on the slots' streams unless the caller opts out (ADSB_FLAG_SINGLE_STREAM: everything on ONE stream)
   c->split_tail = (flags & ADSB_FLAG_SINGLE_STREAM) == 0;
-  for (hipEvent_t& e : c->ring_done)
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { adsb_destroy(c); return -EIO; }
+  for (Event& e : c->ring_done)
+    if (hipEventCreateWithFlags(&e.p, hipEventDisableTiming) != hipSuccess) { adsb_destroy(c); return -EIO; }
   for (Slot& sl : c->slot) {
-    if (host_alloc_near(c, (void**)&sl.h_sum, sizeof(Summary), true) != hipSuccess) { adsb_destroy(c); return -ENOMEM; }
+    if (host_alloc_near(c, (void**)&sl.h_sum.p, sizeof(Summary), true) != hipSuccess) { adsb_destroy(c); return -ENOMEM; }
     memset(sl.h_sum, 0, sizeof(Summary));                        // (pad_ is the pass number finish() polls: starts at zero)
-    if (hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking) != hipSuccess) { adsb_destroy(c); return -EIO; }
-    if (hipEventCreate(&sl.ev0) != hipSuccess || hipEventCreate(&sl.ev1) != hipSuccess ||
-        hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&sl.det_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&sl.h2d_done, hipEventDisableTiming) != hipSuccess) { adsb_destroy(c); return -EIO; }
+    if (hipStreamCreateWithFlags(&sl.stream.p, hipStreamNonBlocking) != hipSuccess) { adsb_destroy(c); return -EIO; }
+    if (hipEventCreate(&sl.ev0.p) != hipSuccess || hipEventCreate(&sl.ev1.p) != hipSuccess ||
+        hipEventCreateWithFlags(&sl.done.p, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&sl.det_done.p, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&sl.h2d_done.p, hipEventDisableTiming) != hipSuccess) { adsb_destroy(c); return -EIO; }
   }
   c->stream = c->slot[0].stream;         // blocking calls always run in slot 0 (run_pipeline)
-  if (hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking) != hipSuccess) { adsb_destroy(c); return -EIO; }
+  if (hipStreamCreateWithFlags(&c->h2d_stream.p, hipStreamNonBlocking) != hipSuccess) { adsb_destroy(c); return -EIO; }
   if (flags & ADSB_FLAG_DECODE) {
     // every entry's epoch 0: no plane; adsb_reset moves the epoch on
     const size_t pb = ((size_t)1 << 24) * sizeof(Plane);
-    if (hipMalloc((void**)&c->d_planes, pb) != hipSuccess) { (void)hipGetLastError(); adsb_destroy(c); return -ENOMEM; }
+    if (hipMalloc((void**)&c->d_planes.p, pb) != hipSuccess) { (void)hipGetLastError(); adsb_destroy(c); return -ENOMEM; }
     if (hipMemsetAsync(c->d_planes, 0, pb, c->stream) != hipSuccess) { adsb_destroy(c); return -EIO; }
   }
   if (flags & ADSB_FLAG_AIRCRAFT_TABLE) {
-    if (hipMalloc((void**)&c->d_air, ((size_t)1 << 24) * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void**)&c->d_air_st, sizeof(AirState)) != hipSuccess) { (void)hipGetLastError(); adsb_destroy(c); return -ENOMEM; }
-    if (hipEventCreateWithFlags(&c->air_ev, hipEventDisableTiming) != hipSuccess || air_clear(c) != 0) { adsb_destroy(c); return -EIO; }
+    if (hipMalloc((void**)&c->d_air.p, ((size_t)1 << 24) * sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc((void**)&c->d_air_st.p, sizeof(AirState)) != hipSuccess) { (void)hipGetLastError(); adsb_destroy(c); return -ENOMEM; }
+    if (hipEventCreateWithFlags(&c->air_ev.p, hipEventDisableTiming) != hipSuccess || air_clear(c) != 0) { adsb_destroy(c); return -EIO; }
   }
   *out = c;
   return 0;
 }
 
+// Nothing of the context is still at work on the device when its members let go of what they own.
 void adsb_destroy(adsb_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
@@ -1721,43 +1758,7 @@ void adsb_destroy(adsb_ctx* c) {
   if (c->d2h_stream) (void)hipStreamSynchronize(c->d2h_stream);
   if (c->tail_stream) (void)hipStreamSynchronize(c->tail_stream);
   for (Slot& sl : c->slot) if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-  DevBuf* bufs[] = {&c->d_in};
-  for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
-  for (Slot& sl : c->slot) {
-    DevBuf* sb[] = {&sl.d_cands, &sl.d_recs, &sl.d_sorted, &sl.d_sorted_src, &sl.d_out, &sl.d_seg, &sl.d_blk_count,
-                    &sl.d_blk_lastp, &sl.d_blk_flags, &sl.d_blk_off, &sl.d_long, &sl.d_misc, &sl.d_in, &sl.d_ratio};
-    for (DevBuf* b : sb) if (b->p) (void)hipFree(b->p);
-    if (sl.h_sum) (void)hipHostFree(sl.h_sum);
-    if (sl.h_out) (void)hipHostFree(sl.h_out);
-    if (sl.h_ratio) (void)hipHostFree(sl.h_ratio);
-    if (sl.h2d_done) (void)hipEventDestroy(sl.h2d_done);
-    if (sl.ev0) (void)hipEventDestroy(sl.ev0);
-    if (sl.ev1) (void)hipEventDestroy(sl.ev1);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-    if (sl.det_done) (void)hipEventDestroy(sl.det_done);
-    if (sl.stream) (void)hipStreamDestroy(sl.stream);
-  }
   if (c->air_ev) (void)hipEventSynchronize(c->air_ev);
-  if (c->d_air) (void)hipFree(c->d_air);
-  if (c->d_air_st) (void)hipFree(c->d_air_st);
-  if (c->d_planes) (void)hipFree(c->d_planes);
-  for (DevBuf* b : {&c->d_dec_keys, &c->d_dec_sorted, &c->d_dec_tmp}) if (b->p) (void)hipFree(b->p);
-  if (c->h_pdu) (void)hipHostFree(c->h_pdu);
-  for (DevBuf* b : {&c->bt.d_scratch, &c->bt.d_fixed, &c->bt.d_da, &c->bt.d_ta, &c->bt.d_kept, &c->bt.d_packed, &c->bt.d_tot,
-                    &c->bt.d_in})
-    if (b->p) (void)hipFree(b->p);
-  for (void* p : {c->bt.h_tab, c->bt.h_first, c->bt.h_out}) if (p) (void)hipHostFree(p);
-  for (Slot& sl : c->slot) if (sl.h_dec) (void)hipHostFree(sl.h_dec);
-  if (c->air_ev) (void)hipEventDestroy(c->air_ev);
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  if (c->h_dm) (void)hipHostFree(c->h_dm);
-  for (void* r : c->h_ring) if (r) (void)hipHostFree(r);
-  delete c->pool;
-  for (hipEvent_t e : c->ring_done) if (e) (void)hipEventDestroy(e);
-  if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-  if (c->h2d_stream) (void)hipStreamDestroy(c->h2d_stream);
-  if (c->d2h_stream) (void)hipStreamDestroy(c->d2h_stream);
-  if (c->tail_stream) (void)hipStreamDestroy(c->tail_stream);
   delete c;
 }
 
@@ -1769,11 +1770,11 @@ int adsb_set_threshold(adsb_ctx* c, float threshold) {
 
 int adsb_set_stream(adsb_ctx* c, void* hip_stream) {
   if (!c) return -EINVAL;
-  for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "calls pending");
+  { int r = require_idle(c, "calls pending"); if (r) return r; }
   if (c->own_stream && c->stream) (void)hipStreamSynchronize(c->stream);      // (slot 0's: it stays the slot's)
   HIPCHK(c, hipSetDevice(c->device));
-  if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  if (!c->tail_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->tail_stream, hipStreamNonBlocking));
+  if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream.p, hipStreamNonBlocking));
+  if (!c->tail_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->tail_stream.p, hipStreamNonBlocking));
   c->stream = (hipStream_t)hip_stream;
   c->own_stream = false;
   return 0;
@@ -1835,15 +1836,15 @@ int adsb_clear_pending_events(adsb_ctx* c) {
 int adsb_reset(adsb_ctx* c) {
   if (!c) return -EINVAL;
   if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) {
-    for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
+    int r = require_idle(c, kCallPending);
+    if (r) return r;
     HIPCHK(c, hipSetDevice(c->device));
     if ((c->flags & ADSB_FLAG_DECODE) && ++c->dec_epoch == 0) {   // (2^32 resets: every entry cleared once more, behind
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->air_ev, 0));    //  every step queued so far and before air_clear's event)
       HIPCHK(c, hipMemsetAsync(c->d_planes, 0, ((size_t)1 << 24) * sizeof(Plane), c->stream));
       c->dec_epoch = 1;
     }
-    int r = air_clear(c);
-    if (r) return r;
+    if ((r = air_clear(c))) return r;
   }
   c->st = FramerState();
   c->n_ext = 0;           // a fresh stream starts without remembered producers
@@ -1857,12 +1858,35 @@ int adsb_framer_state(adsb_ctx* c, float* prev_in0, int64_t* prev_eob_idx) {
   return 0;
 }
 
-int adsb_process_iq_device(adsb_ctx* c, const void* d_iq, int64_t n, int64_t abs_offset, adsb_burst* out,
-                           int32_t cap, int32_t* n_out) {
-  return canonical(c, 0, d_iq, n, abs_offset, out, cap, n_out);
-}
-
+// The entry points named after one format are the format-generic ones with that format.
 int adsb_set_iq16_scale(adsb_ctx* c, float scale) { return adsb_set_format_scale(c, ADSB_FMT_SC16, scale); }
+int adsb_process_iq(adsb_ctx* c, const float* iq_host, int64_t n, int64_t abs_offset, adsb_burst* out, int32_t cap, int32_t* n_out) {
+  return adsb_process_format(c, ADSB_FMT_FC32, iq_host, n, abs_offset, out, cap, n_out);
+}
+int adsb_process_iq_device(adsb_ctx* c, const void* d_iq, int64_t n, int64_t abs_offset, adsb_burst* out, int32_t cap, int32_t* n_out) {
+  return adsb_process_format_device(c, ADSB_FMT_FC32, d_iq, n, abs_offset, out, cap, n_out);
+}
+int adsb_submit_iq_device(adsb_ctx* c, const void* d_iq, int64_t n, int64_t abs_offset, int32_t* ticket) {
+  return adsb_submit_format_device(c, ADSB_FMT_FC32, d_iq, n, abs_offset, ticket);
+}
+int adsb_process_mag2(adsb_ctx* c, const float* mag2_host, int64_t n, int64_t abs_offset, adsb_burst* out, int32_t cap, int32_t* n_out) {
+  return adsb_process_format(c, ADSB_FMT_MAG2, mag2_host, n, abs_offset, out, cap, n_out);
+}
+int adsb_process_mag2_device(adsb_ctx* c, const void* d_mag2, int64_t n, int64_t abs_offset, adsb_burst* out, int32_t cap, int32_t* n_out) {
+  return adsb_process_format_device(c, ADSB_FMT_MAG2, d_mag2, n, abs_offset, out, cap, n_out);
+}
+int adsb_submit_mag2_device(adsb_ctx* c, const void* d_mag2, int64_t n, int64_t abs_offset, int32_t* ticket) {
+  return adsb_submit_format_device(c, ADSB_FMT_MAG2, d_mag2, n, abs_offset, ticket);
+}
+int adsb_process_iq16(adsb_ctx* c, const int16_t* iq16_host, int64_t n, int64_t abs_offset, adsb_burst* out, int32_t cap, int32_t* n_out) {
+  return adsb_process_format(c, ADSB_FMT_SC16, iq16_host, n, abs_offset, out, cap, n_out);
+}
+int adsb_process_iq16_device(adsb_ctx* c, const void* d_iq16, int64_t n, int64_t abs_offset, adsb_burst* out, int32_t cap, int32_t* n_out) {
+  return adsb_process_format_device(c, ADSB_FMT_SC16, d_iq16, n, abs_offset, out, cap, n_out);
+}
+int adsb_submit_iq16_device(adsb_ctx* c, const void* d_iq16, int64_t n, int64_t abs_offset, int32_t* ticket) {
+  return adsb_submit_format_device(c, ADSB_FMT_SC16, d_iq16, n, abs_offset, ticket);
+}
 
 int adsb_set_format_scale(adsb_ctx* c, int format, float scale) {
   if (!c || format < ADSB_FMT_SC16 || format >= ADSB_FMT_COUNT) return -EINVAL;
@@ -1915,65 +1939,27 @@ int adsb_process_batch(adsb_ctx* c, int format, const adsb_batch_item* items, in
   return run_batch(c, format, dev.data(), n_items, out, cap, item_first, n_out, n_fallback);
 }
 
-int adsb_process_iq16_device(adsb_ctx* c, const void* d_iq16, int64_t n, int64_t abs_offset, adsb_burst* out,
-                             int32_t cap, int32_t* n_out) {
-  return canonical(c, 2, d_iq16, n, abs_offset, out, cap, n_out);
-}
-
-int adsb_process_iq16(adsb_ctx* c, const int16_t* iq16_host, int64_t n, int64_t abs_offset, adsb_burst* out,
-                      int32_t cap, int32_t* n_out) {
-  if (!c || n < 0 || (n > 0 && !iq16_host)) return -EINVAL;
-  if (n == 0) { if (n_out) *n_out = 0; c->slot[c->last_slot].nres = 0; return 0; }
-  HIPCHK(c, hipSetDevice(c->device));
-  void* d = nullptr;
-  int rc = upload(c, iq16_host, (size_t)n * 4, &d);
-  if (rc) return rc;
-  return canonical(c, 2, d, n, abs_offset, out, cap, n_out);
-}
-
-int adsb_process_mag2_device(adsb_ctx* c, const void* d_mag2, int64_t n, int64_t abs_offset, adsb_burst* out,
-                             int32_t cap, int32_t* n_out) {
-  return canonical(c, 1, d_mag2, n, abs_offset, out, cap, n_out);
-}
-
-int adsb_process_iq(adsb_ctx* c, const float* iq_host, int64_t n, int64_t abs_offset, adsb_burst* out,
-                    int32_t cap, int32_t* n_out) {
-  if (!c || n < 0 || (n > 0 && !iq_host)) return -EINVAL;
-  if (n == 0) { if (n_out) *n_out = 0; c->slot[c->last_slot].nres = 0; return 0; }
-  HIPCHK(c, hipSetDevice(c->device));
-  void* d = nullptr;
-  int rc = upload(c, iq_host, (size_t)n * 8, &d);
-  if (rc) return rc;
-  return canonical(c, 0, d, n, abs_offset, out, cap, n_out);
-}
-
-int adsb_process_mag2(adsb_ctx* c, const float* mag2_host, int64_t n, int64_t abs_offset, adsb_burst* out,
-                      int32_t cap, int32_t* n_out) {
-  if (!c || n < 0 || (n > 0 && !mag2_host)) return -EINVAL;
-  if (n == 0) { if (n_out) *n_out = 0; c->slot[c->last_slot].nres = 0; return 0; }
-  HIPCHK(c, hipSetDevice(c->device));
-  void* d = nullptr;
-  int rc = upload(c, mag2_host, (size_t)n * 4, &d);
-  if (rc) return rc;
-  return canonical(c, 1, d, n, abs_offset, out, cap, n_out);
-}
-
 static int shard_post(adsb_ctx* c, Slot& s, const Summary& sum, int32_t* nres_io, bool drop_overlong = false);
+
+// The context's next pipeline slot takes the pass; the slot's number is the caller's ticket.
+static int claim_and_enqueue(adsb_ctx* c, const Plan& pl, bool is_shard, int32_t* ticket) {
+  Slot& s = c->slot[c->next_slot];
+  const int r = enqueue(c, s, pl, true);
+  if (r) return r;
+  s.is_shard = is_shard;
+  *ticket = c->next_slot;
+  c->next_slot = (c->next_slot + 1) % ADSB_MAX_IN_FLIGHT;
+  return 0;
+}
 
 static int submit_canonical(adsb_ctx* c, int mode, const void* d_data, int64_t n, int64_t abs_offset, int32_t* ticket) {
   if (!c || n < 1 || !ticket) return -EINVAL;
   if (((uintptr_t)d_data & 15u) != 0) return fail(c, -EINVAL, "device pointer must be 16-byte aligned");
-  Slot& s = c->slot[c->next_slot];
-  if (s.busy) return fail(c, -EBUSY, "every pipeline slot is in flight (adsb_wait first)");
+  if (c->slot[c->next_slot].busy) return fail(c, -EBUSY, "every pipeline slot is in flight (adsb_wait first)");
   Plan pl = plan_canonical(mode, d_data, n, abs_offset, c->sps);
   pl.long_aware = (c->flags & ADSB_FLAG_LONG_AWARE_GATE) != 0;
   pl.air = (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) != 0;
-  int r = enqueue(c, s, pl, true);
-  if (r) { s.busy = false; return r; }
-  s.is_shard = false;
-  *ticket = c->next_slot;
-  c->next_slot = (c->next_slot + 1) % ADSB_MAX_IN_FLIGHT;
-  return 0;
+  return claim_and_enqueue(c, pl, false, ticket);
 }
 
 // Host buffer -> the slot's own device input buffer on the upload stream; only this slot's k_detect waits for it.
@@ -2007,7 +1993,7 @@ int adsb_last_confidence(adsb_ctx* c, const float** ratio, int32_t* n) {
   if (!c) return -EINVAL;
   if (!(c->flags & ADSB_FLAG_CONFIDENCE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_CONFIDENCE");
   const Slot& s = c->slot[c->last_slot];
-  if (ratio) *ratio = s.nres > 0 ? (const float*)s.h_ratio : nullptr;
+  if (ratio) *ratio = s.nres > 0 ? (const float*)s.h_ratio.p : nullptr;
   if (n) *n = s.nres;
   return 0;
 }
@@ -2016,7 +2002,7 @@ int adsb_set_decoder(adsb_ctx* c, int32_t msg_filter, double start_timestamp) {
   if (!c) return -EINVAL;
   if (!(c->flags & ADSB_FLAG_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_DECODE");
   if (msg_filter != ADSB_DEC_ALL_MESSAGES && msg_filter != ADSB_DEC_EXTENDED_SQUITTER_ONLY) return fail(c, -EINVAL, "msg_filter");
-  for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
+  { int r = require_idle(c, kCallPending); if (r) return r; }
   c->dec_all = msg_filter == ADSB_DEC_ALL_MESSAGES;
   c->dec_start = start_timestamp;
   return 0;
@@ -2026,7 +2012,7 @@ int adsb_last_decoded(adsb_ctx* c, const adsb_decoded** rows, int32_t* n) {
   if (!c) return -EINVAL;
   if (!(c->flags & ADSB_FLAG_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_DECODE");
   const Slot& s = c->slot[c->last_slot];
-  if (rows) *rows = s.nres > 0 ? (const adsb_decoded*)s.h_dec : nullptr;
+  if (rows) *rows = s.nres > 0 ? (const adsb_decoded*)s.h_dec.p : nullptr;
   if (n) *n = s.nres;
   return 0;
 }
@@ -2034,18 +2020,18 @@ int adsb_last_decoded(adsb_ctx* c, const adsb_decoded** rows, int32_t* n) {
 int adsb_decode_pdus(adsb_ctx* c, const uint8_t* bits14, const double* timestamps, int32_t n, adsb_decoded* rows) {
   if (!c || n < 0 || (n > 0 && (!bits14 || !timestamps || !rows))) return -EINVAL;
   if (!(c->flags & ADSB_FLAG_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_DECODE");
-  for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
+  int rc = require_idle(c, kCallPending);
+  if (rc) return rc;
   if (n == 0) return 0;
   HIPCHK(c, hipSetDevice(c->device));
   // staging in pinned, device-visible memory: rows (72 B) | timestamps (8 B) | bits (14 B) | ok (1 B) per PDU
   const size_t nt = (size_t)n, o_ts = nt * sizeof(adsb_decoded), o_bits = o_ts + nt * 8, o_ok = o_bits + nt * 14;
-  int rc;
-  if ((rc = ensure_pinned(c, c->h_pdu, c->h_pdu_cap, o_ok + nt))) return rc;
-  char* h = (char*)c->h_pdu;
+  if ((rc = ensure_pinned(c, c->h_pdu, o_ok + nt))) return rc;
+  char* h = (char*)c->h_pdu.p;
   memcpy(h + o_ts, timestamps, nt * 8);
   memcpy(h + o_bits, bits14, nt * 14);
   if ((rc = apply_ext(c, c->stream))) return rc;
-  const int g = (int)((nt + kThreads - 1) / kThreads < 2048 ? (nt + kThreads - 1) / kThreads : 2048);
+  const unsigned g = step_grid((long long)nt, kThreads);
   hipLaunchKernelGGL(k_dec_pdu_flags, dim3(g), dim3(kThreads), 0, c->stream, (const unsigned char*)(h + o_bits),
                      (unsigned char*)(h + o_ok), (int)n);
   if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE)
@@ -2070,18 +2056,6 @@ int adsb_submit_format_device(adsb_ctx* c, int format, const void* d_data, int64
   return submit_canonical(c, format, d_data, n, abs_offset, ticket);
 }
 
-int adsb_submit_iq_device(adsb_ctx* c, const void* d_iq, int64_t n, int64_t abs_offset, int32_t* ticket) {
-  return submit_canonical(c, 0, d_iq, n, abs_offset, ticket);
-}
-
-int adsb_submit_iq16_device(adsb_ctx* c, const void* d_iq16, int64_t n, int64_t abs_offset, int32_t* ticket) {
-  return submit_canonical(c, 2, d_iq16, n, abs_offset, ticket);
-}
-
-int adsb_submit_mag2_device(adsb_ctx* c, const void* d_mag2, int64_t n, int64_t abs_offset, int32_t* ticket) {
-  return submit_canonical(c, 1, d_mag2, n, abs_offset, ticket);
-}
-
 int adsb_wait(adsb_ctx* c, int32_t ticket, adsb_burst* out, int32_t cap, int32_t* n_out) {
   if (!c || ticket < 0 || ticket >= ADSB_MAX_IN_FLIGHT) return -EINVAL;
   Slot& s = c->slot[ticket];
@@ -2097,7 +2071,7 @@ int adsb_wait(adsb_ctx* c, int32_t ticket, adsb_burst* out, int32_t cap, int32_t
 
 int adsb_last_result(adsb_ctx* c, const adsb_burst** bursts, int32_t* n) {
   if (!c) return -EINVAL;
-  if (bursts) *bursts = (const adsb_burst*)c->slot[c->last_slot].h_out;
+  if (bursts) *bursts = (const adsb_burst*)c->slot[c->last_slot].h_out.p;
   if (n) *n = c->slot[c->last_slot].nres;
   return 0;
 }
@@ -2121,14 +2095,13 @@ int adsb_framer_work_passthrough(adsb_ctx* c, const float* in0, int64_t n_in0, i
   if (c->flags & ADSB_FLAG_FRAMER_SLICES) pl.dem_hi = n_in0;   // bursts that end inside this call's input get their bits
   Summary s;
   int32_t nres = 0;
-  for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
+  if ((rc = require_idle(c, kCallPending))) return rc;
   {
     // the device pass is queued, THEN the block's pass-through copy (framer.py:181: out0[:] = in0[history:]) runs on the
     // host -- beside the upload's DMA and the kernels instead of behind them -- then the pass is waited for
     Slot& sl0 = c->slot[0];
     c->last_slot = 0;
-    rc = enqueue(c, sl0, pl, false);
-    if (rc) { sl0.busy = false; return rc; }
+    if ((rc = enqueue(c, sl0, pl, false))) return rc;
     if (out0) {
       const size_t pb = (size_t)N * sizeof(float);
       if (pb >= ((size_t)1 << 20) && ensure_pool(c) == 0) c->pool->copy((char*)out0, (const char*)(in0 + (H - 1)), pb);
@@ -2148,8 +2121,9 @@ int adsb_demod_work(adsb_ctx* c, const float* in0, int64_t n, int64_t nitems_rea
   if (!c || n < 0 || ntags < 0 || (n > 0 && !in0) || (ntags > 0 && (!tag_offsets || !bits112 || !ok))) return -EINVAL;
   if (c->flags & ADSB_FLAG_DECODE) return fail(c, -EINVAL, "adsb_demod_work is not for ADSB_FLAG_DECODE contexts (adsb_decode_pdus)");
   if (ntags == 0) return 0;
-  if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE)      // (the table steps of passes in flight may still be settled: finish)
-    for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
+  int rc;
+  // (the table steps of passes in flight may still be settled: finish)
+  if ((c->flags & ADSB_FLAG_AIRCRAFT_TABLE) && (rc = require_idle(c, kCallPending))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   // (independent of submitted calls still in flight: own buffers, ordered behind them on the compute stream)
   // Tag positions, packed bits, ok flags and ratios live in the context's pinned, device-visible scratch (layout: tag
@@ -2159,25 +2133,20 @@ int adsb_demod_work(adsb_ctx* c, const float* in0, int64_t n, int64_t nitems_rea
   const size_t nt = (size_t)ntags;
   const size_t o_bits = nt * 8, o_ok = o_bits + nt * 14, o_ratio = (o_ok + nt + 15) & ~(size_t)15;
   const size_t total = o_ratio + (ratio ? nt * 112 * sizeof(float) : 0);
-  int rc;
-  if ((rc = ensure_pinned(c, c->h_dm, c->h_dm_cap, total))) return rc;
-  char* h = (char*)c->h_dm;
+  if ((rc = ensure_pinned(c, c->h_dm, total))) return rc;
+  char* h = (char*)c->h_dm.p;
   long long* loc = (long long*)h;
   // local positions of the tags inside in0 (demod.py:79: offset - nitems_written); a tag outside the chunk -- the
   // reference's get_tags_in_range never returns one (demod.py:67) -- is dropped by the kernel (ok = 0)
   for (int t = 0; t < ntags; ++t) loc[t] = tag_offsets[t] - nitems_read;
   void* d = nullptr;
   if ((rc = upload(c, in0, (size_t)n * 4, &d))) return rc;
-  int nb = (ntags + kWaves - 1) / kWaves;
-  if (nb > 2048) nb = 2048;
-  hipLaunchKernelGGL((k_slice<1>), dim3(nb), dim3(kThreads), 0, c->stream, (const void*)d, (long long)n,
+  hipLaunchKernelGGL((k_slice<1>), dim3(step_grid(ntags, kWaves)), dim3(kThreads), 0, c->stream, (const void*)d, (long long)n,
                      (const long long*)loc, (int)ntags, c->sps, (unsigned char*)(h + o_bits),
                      (unsigned char*)(h + o_ok), ratio ? (float*)(h + o_ratio) : (float*)nullptr);
-  if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) {
-    const int fb = (int)((nt + kThreads - 1) / kThreads < 2048 ? (nt + kThreads - 1) / kThreads : 2048);
-    hipLaunchKernelGGL(k_fec_slices, dim3(fb), dim3(kThreads), 0, c->stream, (unsigned char*)(h + o_bits),
+  if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE)
+    hipLaunchKernelGGL(k_fec_slices, dim3(step_grid(ntags, kThreads)), dim3(kThreads), 0, c->stream, (unsigned char*)(h + o_bits),
                        (unsigned char*)(h + o_ok), (int)ntags);
-  }
   if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) {
     // the slices with ok != 0 are this call's published PDUs, in tag order
     AirArgs aa{};
@@ -2206,7 +2175,7 @@ int adsb_demod_work(adsb_ctx* c, const float* in0, int64_t n, int64_t nitems_rea
 // call is never evaluated, framer.py:102-108; a burst past the end of the chunk is dropped, demod.py:130-133).
 static int shard_post(adsb_ctx* c, Slot& s, const Summary& sum, int32_t* nres_io, bool drop_overlong) {
   if ((sum.flags & 4u) && !drop_overlong) return fail(c, -EOVERFLOW, "pulse runs past the shard's forward halo");
-  Rec* r = (Rec*)s.h_out;
+  Rec* r = (Rec*)s.h_out.p;
   const int32_t nres = *nres_io;
   const long long origin = s.plan.origin, n = s.plan.n, stream_len = s.plan.origin + s.plan.dem_hi;
   int32_t w = 0;
@@ -2223,7 +2192,7 @@ static int shard_post(adsb_ctx* c, Slot& s, const Summary& sum, int32_t* nres_io
     if (w != i) {
       r[w] = r[i];
       // row t of adsb_last_confidence belongs to record t of the delivered list: rows move with their records
-      if ((c->flags & ADSB_FLAG_CONFIDENCE) && s.h_ratio) memcpy((float*)s.h_ratio + (size_t)w * 112, (float*)s.h_ratio + (size_t)i * 112, 112 * sizeof(float));
+      if ((c->flags & ADSB_FLAG_CONFIDENCE) && s.h_ratio.p) memcpy((float*)s.h_ratio.p + (size_t)w * 112, (float*)s.h_ratio.p + (size_t)i * 112, 112 * sizeof(float));
     }
     ++w;
   }
@@ -2281,14 +2250,8 @@ int adsb_submit_shard_device(adsb_ctx* c, int fmt, const void* d_data, int64_t n
   Plan pl;
   int rc = shard_plan_checked(c, fmt, d_data, n, origin, own_lo, own_hi, stream_len, head_cands, &pl);
   if (rc) return rc;
-  Slot& s = c->slot[c->next_slot];
-  if (s.busy) return fail(c, -EBUSY, "every pipeline slot is in flight (adsb_wait first)");
-  rc = enqueue(c, s, pl, true);
-  if (rc) { s.busy = false; return rc; }
-  s.is_shard = true;
-  *ticket = c->next_slot;
-  c->next_slot = (c->next_slot + 1) % ADSB_MAX_IN_FLIGHT;
-  return 0;
+  if (c->slot[c->next_slot].busy) return fail(c, -EBUSY, "every pipeline slot is in flight (adsb_wait first)");
+  return claim_and_enqueue(c, pl, true, ticket);
 }
 
 int32_t adsb_shard_bounds(int64_t stream_len, int32_t n_shards, int32_t g, int sps, int64_t align, int64_t* own_lo,
@@ -2333,7 +2296,8 @@ int adsb_process_sharded_device(adsb_ctx* c, int fmt, const void* d_data, int64_
   if (!c || fmt < 0 || fmt >= ADSB_FMT_COUNT || n < 0 || shards < 1 || cap < 0 || (cap > 0 && !out) || !n_out) return -EINVAL;
   if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) return fail(c, -EINVAL, "sharded calls are not for ADSB_FLAG_AIRCRAFT_TABLE contexts");
   if (((uintptr_t)d_data & 15u) != 0) return fail(c, -EINVAL, "device pointer must be 16-byte aligned");
-  for (const Slot& sl : c->slot) if (sl.busy) return fail(c, -EBUSY, "a submitted call is still pending (adsb_wait first)");
+  int rc = require_idle(c, kCallPending);
+  if (rc) return rc;
   // the rows of adsb_last_confidence belong to the records of ONE pass in the order that pass delivered them; this driver
   // re-gates and concatenates the records of many passes on the host
   if (c->flags & ADSB_FLAG_CONFIDENCE) return fail(c, -EINVAL, "adsb_process_sharded_device: not for ADSB_FLAG_CONFIDENCE contexts");
@@ -2352,7 +2316,6 @@ int adsb_process_sharded_device(adsb_ctx* c, int fmt, const void* d_data, int64_
   int n_pend = 0, head = 0;
   long long eob = -(1ll << 60);
   int64_t total = 0;
-  int rc = 0;
   const int kHead = 64;
 
   // collect the oldest pass: fix up its head with the carried state, append what it kept
@@ -2366,7 +2329,7 @@ int adsb_process_sharded_device(adsb_ctx* c, int fmt, const void* d_data, int64_
     if (r) return r;
     c->last_slot = p.ticket;
     if ((r = shard_post(c, s, sum, &nres))) return r;
-    adsb_burst* recs = (adsb_burst*)s.h_out;
+    adsb_burst* recs = (adsb_burst*)s.h_out.p;
     int32_t kept = 0;
     r = adsb_shard_fixup(recs, nres, c->sps, eob, &kept);
     if (r == -EAGAIN) {
@@ -2377,10 +2340,10 @@ int adsb_process_sharded_device(adsb_ctx* c, int fmt, const void* d_data, int64_
         if ((r = shard_plan_checked(c, fmt, (const char*)d_data + (size_t)p.lo * bps, p.hi - p.lo, p.lo, p.own_lo, p.own_hi, n,
                                     attempt == 0 ? 4096 : 0, &pl))) return r;
         rearm();
-        if ((r = enqueue(c, s, pl, true))) { s.busy = false; return r; }
+        if ((r = enqueue(c, s, pl, true))) return r;
         if ((r = finish(c, s, &sum, &nres))) return r;
         if ((r = shard_post(c, s, sum, &nres))) return r;
-        recs = (adsb_burst*)s.h_out;
+        recs = (adsb_burst*)s.h_out.p;
         if (attempt == 0) r = adsb_shard_fixup(recs, nres, c->sps, eob, &kept);
         else { long long e = eob; kept = gate_from(recs, nres, c->sps, &e); r = 0; }
       }
@@ -2407,13 +2370,11 @@ int adsb_process_sharded_device(adsb_ctx* c, int fmt, const void* d_data, int64_
     if (n_pend == ADSB_MAX_IN_FLIGHT && (rc = collect())) break;
     Plan pl;
     if ((rc = shard_plan_checked(c, fmt, (const char*)d_data + (size_t)lo * bps, hi - lo, lo, own_lo, own_hi, n, kHead, &pl))) break;
-    Slot& s = c->slot[c->next_slot];
+    int32_t ticket = -1;
     rearm();
-    if ((rc = enqueue(c, s, pl, true))) { s.busy = false; break; }
-    s.is_shard = true;
-    pend[(head + n_pend) % ADSB_MAX_IN_FLIGHT] = Pend{c->next_slot, own_lo, own_hi, lo, hi};
+    if ((rc = claim_and_enqueue(c, pl, true, &ticket))) break;
+    pend[(head + n_pend) % ADSB_MAX_IN_FLIGHT] = Pend{ticket, own_lo, own_hi, lo, hi};
     ++n_pend;
-    c->next_slot = (c->next_slot + 1) % ADSB_MAX_IN_FLIGHT;
   }
   while (n_pend > 0) {
     const int r = collect();          // (after an error too: no pass stays in flight behind this call)
@@ -2454,11 +2415,7 @@ int submit_shard_host(adsb_ctx* c, int fmt, const char* host, const MultiShard& 
   if (rc) return rc;
   Plan pl;
   if ((rc = shard_plan_checked(c, fmt, s.d_in.p, sh.hi - sh.lo, sh.lo, sh.own_lo, sh.own_hi, stream_len, head, &pl))) return rc;
-  if ((rc = enqueue(c, s, pl, true))) { s.busy = false; return rc; }
-  s.is_shard = true;
-  *ticket = c->next_slot;
-  c->next_slot = (c->next_slot + 1) % ADSB_MAX_IN_FLIGHT;
-  return 0;
+  return claim_and_enqueue(c, pl, true, ticket);
 }
 
 int collect_shard(adsb_ctx* c, int32_t ticket, std::vector<adsb_burst>* out) {
@@ -2469,7 +2426,7 @@ int collect_shard(adsb_ctx* c, int32_t ticket, std::vector<adsb_burst>* out) {
   if (r) return r;
   c->last_slot = ticket;
   if ((r = shard_post(c, s, sum, &nres))) return r;
-  const adsb_burst* recs = (const adsb_burst*)s.h_out;
+  const adsb_burst* recs = (const adsb_burst*)s.h_out.p;
   try {
     out->assign(recs, recs + nres);
   } catch (...) {                                     // (no exception crosses the ABI or ends a feeder thread)
@@ -2497,7 +2454,7 @@ int adsb_process_sharded_multi(adsb_ctx* const* ctxs, int32_t n_ctx, int fmt, co
       return fail(c0, -EINVAL, "adsb_process_sharded_multi: contexts differ in rate, threshold, gate, FEC or format scale");
     if (c->flags & ADSB_FLAG_CONFIDENCE) return fail(c0, -EINVAL, "adsb_process_sharded_multi: not for ADSB_FLAG_CONFIDENCE contexts");
     if (!c->own_stream) return fail(c0, -EINVAL, "adsb_process_sharded_multi: not for contexts on a caller-owned stream");
-    for (const Slot& sl : c->slot) if (sl.busy) return fail(c0, -EBUSY, "a submitted call is still pending on one of the contexts");
+    if (require_idle(c, "a submitted call is still pending on one of the contexts", c0)) return -EBUSY;
   }
   *n_out = 0;
   if (stats) memset(stats, 0, sizeof(*stats));

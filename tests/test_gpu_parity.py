@@ -673,6 +673,30 @@ def test_submit_wait_pipeline_matches_blocking_calls(native, torch_mod, mode):
         ctx.wait(t2)                     # nothing pending on that ticket any more
 
 
+def test_failed_submission_leaves_its_slot_free(native, torch_mod):
+    """A pass that cannot be queued (here: refused for its length, before anything is allocated or launched) must not
+    keep its pipeline slot: canonical submission, shard submission and the blocking call each fail with -EINVAL, and the
+    same ticket is handed out by the next submission, whose result is the blocking call's."""
+    from gr_adsb_amd import modulator as M
+    n, too_long = 1 << 20, 1 << 46
+    t = to_dev(torch_mod, M.synth_iq(n, 2e6, 2000, 17))
+    ctx = native.Context(2e6, 0.01)
+    want = ctx.process_iq_device(t.data_ptr(), n)
+    assert len(want) > 100
+    fails = (lambda: ctx.submit_format_device(native.FMT_FC32, t.data_ptr(), too_long),
+             lambda: ctx.submit_shard_device(native.FMT_FC32, t.data_ptr(), too_long, 0, 0, too_long - 4000, 1 << 50, 64),
+             lambda: ctx.process_format_device(native.FMT_FC32, t.data_ptr(), too_long))
+    for rep in range(2):                 # twice round the three slots
+        for k, fail in enumerate(fails):
+            with pytest.raises(native.AdsbError) as e:
+                fail()
+            assert e.value.code == -22 and "too long" in str(e.value)
+            ticket = ctx.submit_iq_device(t.data_ptr(), n)
+            assert ticket == k           # the slot the failed call had claimed
+            assert ctx.wait(ticket).tobytes() == want.tobytes()
+    ctx.close()
+
+
 def test_mixed_df_low_snr_config(native, torch_mod):
     """BASELINE.json config 5: mixed DF0/4/5/11/16/17 at 3-25 dB over noise 2e-3."""
     from gr_adsb_amd import modulator as M
@@ -1119,6 +1143,47 @@ def test_lifecycle_stress(native, torch_mod):
         ctx.wait(0)                                                            # nothing pending
 
 
+def test_lifecycle_releases_every_optional_buffer(native, torch_mod):
+    """The create / use / close loop of test_lifecycle_stress, same bound, for what a plain context never allocates: the
+    2^24-entry aircraft and plane tables, the decode rows and the PDU staging (FEC + table + decode contexts); the batch
+    buffers, a slot's upload buffer and the pinned staging ring (a batch and a host-fed submission of pageable arrays); the
+    confidence ratios (a FLAG_CONFIDENCE pass)."""
+    torch = torch_mod
+    from gr_adsb_amd import modulator as M
+    fs = 2e6
+    iq = M.synth_iq(1 << 21, fs, 4000, 61)
+    items = [iq[k << 17:(k + 1) << 17].copy() for k in range(4)]
+    full = native.FLAG_FEC_CONSERVATIVE | native.FLAG_AIRCRAFT_TABLE | native.FLAG_DECODE
+
+    def decoding():
+        ctx = native.Context(fs, 0.01, flags=full)
+        recs = ctx.process_iq(iq[:1 << 18])
+        rows = ctx.last_decoded()
+        assert len(recs) > 100 and len(rows) == len(recs)
+        pdus = recs[(recs["flags"] & native.BURST_DEMOD) != 0]
+        assert len(ctx.decode_pdus(pdus["bits"], pdus["offset"] / fs)) == len(pdus) > 100
+        ctx.close()
+
+    def batch_hostfed_confidence():
+        ctx = native.Context(fs, 0.01)
+        got, first = ctx.process_batch(native.FMT_FC32, items)
+        assert first[-1] == len(got) > 100
+        assert len(ctx.wait(ctx.submit_format_host(native.FMT_FC32, iq))) > 1000      # 16 MiB, pageable: through the ring
+        ctx.close()
+        ctx = native.Context(fs, 0.01, flags=native.FLAG_CONFIDENCE)
+        recs = ctx.process_iq(iq[:1 << 18])
+        assert ctx.last_confidence().shape == (len(recs), 112) and len(recs) > 100
+        ctx.close()
+
+    for use in (decoding, batch_hostfed_confidence):
+        free = []
+        for rep in range(31):
+            use()
+            torch.cuda.synchronize()
+            free.append(torch.cuda.mem_get_info()[0])
+        assert free[10] - free[30] < (16 << 20), (use.__name__, [(f - free[0]) >> 20 for f in free])
+
+
 def test_adversarial_streams(native):
     """The seam-hunting streams of test_sim_property.py (plateaus and bursts planted on tile / window
     boundaries, exact ties, thresholds on sample values, NaNs) through the real kernels."""
@@ -1380,6 +1445,44 @@ def test_c_abi_output_array_and_error_paths(native):
     assert lib.adsb_wait(ctx._h, 7, None, 0, ctypes.byref(n_out)) == -22
     # empty input is a valid call
     assert lib.adsb_process_iq(ctx._h, ctypes.c_void_p(g.iq.ctypes.data), 0, 0, None, 0, ctypes.byref(n_out)) == 0 and n_out.value == 0
+
+
+def test_entry_points_named_after_a_format_are_the_generic_ones(native, torch_mod):
+    """adsb_process_iq / _mag2 / _iq16, their _device and adsb_submit_*_device forms and adsb_set_iq16_scale, called the way
+    a C caller does: the records of the format-generic entry point with that format, and its argument checks (a null
+    context is refused untouched, an empty input is a valid call that clears the last result)."""
+    import ctypes
+    g = Golden("g2msps_df17")
+    lib = native.load()
+    ctx = native.Context(g.fs, g.thr)
+    scale = 1.0 / 4096
+    i16 = np.round(np.ascontiguousarray(g.iq).view(np.float32) / scale).clip(-32768, 32767).astype(np.int16)
+    n_out, ticket = ctypes.c_int32(0), ctypes.c_int32(-1)
+    ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
+    assert lib.adsb_set_iq16_scale(ctx._h, scale) == 0
+    for name, fmt, host in (("iq", native.FMT_FC32, g.iq), ("mag2", native.FMT_MAG2, g.x), ("iq16", native.FMT_SC16, i16)):
+        n = len(g.x)
+        want = ctx.process_format(fmt, host)
+        assert len(want) > 0
+        dev = torch_mod.from_numpy(np.ascontiguousarray(host).view(np.uint8).copy()).to("cuda:0")
+        process, process_dev = getattr(lib, "adsb_process_" + name), getattr(lib, "adsb_process_%s_device" % name)
+        submit = getattr(lib, "adsb_submit_%s_device" % name)
+        assert process(ctx._h, ptr(host), n, 0, None, 0, ctypes.byref(n_out)) == 0 and n_out.value == len(want)
+        assert ctx.last_result().tobytes() == want.tobytes(), name
+        assert process_dev(ctx._h, ctypes.c_void_p(dev.data_ptr()), n, 0, None, 0, ctypes.byref(n_out)) == 0
+        assert ctx.last_result().tobytes() == want.tobytes(), name
+        assert submit(ctx._h, ctypes.c_void_p(dev.data_ptr()), n, 0, ctypes.byref(ticket)) == 0
+        assert ctx.wait(ticket.value).tobytes() == want.tobytes(), name
+        # empty input: a valid call, nothing delivered; a null buffer, a null context: -EINVAL
+        assert process(ctx._h, ptr(host), 0, 0, None, 0, ctypes.byref(n_out)) == 0 and n_out.value == 0
+        assert len(ctx.last_result()) == 0
+        assert process(ctx._h, None, 10, 0, None, 0, ctypes.byref(n_out)) == -22
+        assert process(None, ptr(host), n, 0, None, 0, ctypes.byref(n_out)) == -22
+        assert process_dev(None, ctypes.c_void_p(dev.data_ptr()), n, 0, None, 0, ctypes.byref(n_out)) == -22
+        assert submit(None, ctypes.c_void_p(dev.data_ptr()), n, 0, ctypes.byref(ticket)) == -22
+        assert submit(ctx._h, ctypes.c_void_p(dev.data_ptr()), n, 0, None) == -22
+    assert lib.adsb_set_iq16_scale(None, scale) == -22
+    ctx.close()
 
 
 def test_polled_small_passes_never_show_stale_or_partial_records(native):
