@@ -2505,8 +2505,9 @@ __global__ void __launch_bounds__(64) k_air_cond(AirArgs a) {
 // context, error_corr "Conservative" iff ADSB_FLAG_FEC_CONSERVATIVE) whose clock is the PDU's own timestamp:
 // now = (long long)timestamp, Python's int() (include/adsb_hip.h ADSB_FLAG_DECODE).  Three stages behind k_air_verdict, with
 // its skip rules: k_dec_classify (one thread per record: its row at once when it touches no plane, else a key address << 32 |
-// position), a sort of the keys (adsb_hip.hip: rocPRIM; the emulator sorts on the host), k_dec_fold (one lane per address
-// segment, in list order).
+// position), k_dec_sort_hist / k_dec_sort_scan / k_dec_sort_scatter (the library's own stable radix sort of the keys by address,
+// queued by adsb_hip.hip launch_dec; the emulator runs the same kernels), k_dec_fold (one lane per address segment, in list
+// order).
 constexpr unsigned kDecNone = 0, kDecDecoded = 1, kDecUnknown = 2, kDecRaised = 3;     // adsb_decoded.port
 constexpr unsigned kHasPlane = 1, kHasCallsign = 2, kHasAltitude = 4, kHasVelocity = 8;  // adsb_decoded.present
 constexpr unsigned kHasEven = 16, kHasOdd = 32;                                           // Plane.present only
@@ -2790,3 +2791,83 @@ __global__ void __launch_bounds__(kThreads) k_dec_pdu_flags(const unsigned char*
 }
 
 }  // namespace adsb
+
+// Stage 2 of the decode step.  Outside adsb, in an unnamed namespace: the three kernels are the including unit's own, so the
+// library exports nothing for them.
+namespace {
+using adsb::kThreads;
+using adsb::kWaves;
+// ADSB_FLAG_DECODE's group stage: a stable LSD radix sort of the keys (address << 32 | position, written in list order) by
+// bits 32..59 -- the address and the "no key" marker; stability keeps list order inside an address.  Seven passes of four
+// bits, each a block histogram, one scan, a stable scatter.  Small on purpose: 4096 keys per workgroup, 272 bytes of LDS,
+// so that every stage fits beside the next pass's k_detect.
+constexpr int kSortItems = 16, kSortTile = kThreads * kSortItems;
+__global__ void __launch_bounds__(kThreads) k_dec_sort_hist(const unsigned long long* in, int n, int shift, unsigned* hist) {
+  __shared__ unsigned cnt[16];
+  if (threadIdx.x < 16) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const int base = (int)blockIdx.x * kSortTile;
+  for (int r = 0; r < kSortItems; ++r) {
+    const int i = base + r * kThreads + (int)threadIdx.x;
+    if (i < n) atomicAdd(&cnt[(unsigned)(in[i] >> shift) & 15u], 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x < 16) hist[threadIdx.x * gridDim.x + blockIdx.x] = cnt[threadIdx.x];
+}
+// exclusive scan of hist[16 * nblk] (digit-major), one workgroup
+__global__ void __launch_bounds__(kThreads) k_dec_sort_scan(unsigned* hist, int total) {
+  __shared__ unsigned wsum[kWaves];
+  __shared__ unsigned carry;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  for (int base = 0; base < total; base += kThreads) {
+    const int i = base + (int)threadIdx.x;
+    const unsigned v = i < total ? hist[i] : 0u;
+    unsigned x = v;
+    for (int o = 1; o < 64; o <<= 1) { const unsigned y = __shfl_up(x, o); if (lane >= o) x += y; }
+    if (lane == 63) wsum[wave] = x;
+    __syncthreads();
+    unsigned pre = carry;
+    for (int w = 0; w < wave; ++w) pre += wsum[w];
+    if (i < total) hist[i] = pre + x - v;
+    __syncthreads();
+    if (threadIdx.x == kThreads - 1) carry = pre + x;
+    __syncthreads();
+  }
+}
+__global__ void __launch_bounds__(kThreads) k_dec_sort_scatter(const unsigned long long* in, unsigned long long* out, int n,
+                                                               int shift, const unsigned* hist) {
+  __shared__ unsigned off[16];
+  __shared__ unsigned wcnt[kWaves][16];
+  if (threadIdx.x < 16) off[threadIdx.x] = hist[threadIdx.x * gridDim.x + blockIdx.x];
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const int base = (int)blockIdx.x * kSortTile;
+  for (int r = 0; r < kSortItems; ++r) {
+    const int i = base + r * kThreads + (int)threadIdx.x;
+    const bool live = i < n;
+    const unsigned long long k = live ? in[i] : 0ull;
+    const unsigned d = (unsigned)(k >> shift) & 15u;
+    unsigned rank = 0;
+    for (unsigned q = 0; q < 16; ++q) {
+      const unsigned long long m = __ballot(live && d == q);
+      if (lane == 0) wcnt[wave][q] = (unsigned)__popcll(m);
+      if (live && d == q) rank = (unsigned)__popcll(m & lt);
+    }
+    __syncthreads();
+    if (live) {
+      unsigned pos = off[d] + rank;
+      for (int w = 0; w < wave; ++w) pos += wcnt[w][d];
+      out[pos] = k;
+    }
+    __syncthreads();
+    if (threadIdx.x < 16) {
+      unsigned t = 0;
+      for (int w = 0; w < kWaves; ++w) t += wcnt[w][threadIdx.x];
+      off[threadIdx.x] += t;
+    }
+    __syncthreads();
+  }
+}
+}  // namespace

@@ -650,80 +650,6 @@ void launch_fec(hipStream_t st, const Slot& s, Rec* out, const Summary* sum) {
 // opt-in aircraft table (ADSB_FLAG_AIRCRAFT_TABLE): the table step of one published pass (list: out / mirror / sum; slices:
 // bits14 / ok, n = ntags), in stream order behind every earlier pass's step: the three slots run on their own streams, so
 // the step waits for the event recorded behind the previous one (pass n's verdict needs every announcement of passes < n)
-// ADSB_FLAG_DECODE's group stage: a stable LSD radix sort of the keys (address << 32 | position, written in list order) by
-// bits 32..59 -- the address and the "no key" marker; stability keeps list order inside an address.  Seven passes of four
-// bits, each a block histogram, one scan, a stable scatter.  Small on purpose: 4096 keys per workgroup, 272 bytes of LDS,
-// so that every stage fits beside the next pass's k_detect.
-constexpr int kSortItems = 16, kSortTile = kThreads * kSortItems;
-__global__ void __launch_bounds__(kThreads) k_dec_sort_hist(const unsigned long long* in, int n, int shift, unsigned* hist) {
-  __shared__ unsigned cnt[16];
-  if (threadIdx.x < 16) cnt[threadIdx.x] = 0;
-  __syncthreads();
-  const int base = (int)blockIdx.x * kSortTile;
-  for (int r = 0; r < kSortItems; ++r) {
-    const int i = base + r * kThreads + (int)threadIdx.x;
-    if (i < n) atomicAdd(&cnt[(unsigned)(in[i] >> shift) & 15u], 1u);
-  }
-  __syncthreads();
-  if (threadIdx.x < 16) hist[threadIdx.x * gridDim.x + blockIdx.x] = cnt[threadIdx.x];
-}
-// exclusive scan of hist[16 * nblk] (digit-major), one workgroup
-__global__ void __launch_bounds__(kThreads) k_dec_sort_scan(unsigned* hist, int total) {
-  __shared__ unsigned wsum[kWaves];
-  __shared__ unsigned carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
-  for (int base = 0; base < total; base += kThreads) {
-    const int i = base + (int)threadIdx.x;
-    const unsigned v = i < total ? hist[i] : 0u;
-    unsigned x = v;
-    for (int o = 1; o < 64; o <<= 1) { const unsigned y = __shfl_up(x, o); if (lane >= o) x += y; }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    unsigned pre = carry;
-    for (int w = 0; w < wave; ++w) pre += wsum[w];
-    if (i < total) hist[i] = pre + x - v;
-    __syncthreads();
-    if (threadIdx.x == kThreads - 1) carry = pre + x;
-    __syncthreads();
-  }
-}
-__global__ void __launch_bounds__(kThreads) k_dec_sort_scatter(const unsigned long long* in, unsigned long long* out, int n,
-                                                               int shift, const unsigned* hist) {
-  __shared__ unsigned off[16];
-  __shared__ unsigned wcnt[kWaves][16];
-  if (threadIdx.x < 16) off[threadIdx.x] = hist[threadIdx.x * gridDim.x + blockIdx.x];
-  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  const int base = (int)blockIdx.x * kSortTile;
-  for (int r = 0; r < kSortItems; ++r) {
-    const int i = base + r * kThreads + (int)threadIdx.x;
-    const bool live = i < n;
-    const unsigned long long k = live ? in[i] : 0ull;
-    const unsigned d = (unsigned)(k >> shift) & 15u;
-    unsigned rank = 0;
-    for (unsigned q = 0; q < 16; ++q) {
-      const unsigned long long m = __ballot(live && d == q);
-      if (lane == 0) wcnt[wave][q] = (unsigned)__popcll(m);
-      if (live && d == q) rank = (unsigned)__popcll(m & lt);
-    }
-    __syncthreads();
-    if (live) {
-      unsigned pos = off[d] + rank;
-      for (int w = 0; w < wave; ++w) pos += wcnt[w][d];
-      out[pos] = k;
-    }
-    __syncthreads();
-    if (threadIdx.x < 16) {
-      unsigned t = 0;
-      for (int w = 0; w < kWaves; ++w) t += wcnt[w][threadIdx.x];
-      off[threadIdx.x] += t;
-    }
-    __syncthreads();
-  }
-}
-
 // ADSB_FLAG_DECODE: the decode step of the same records, behind the last verdict (rows: cap rows; ts: the slices'
 // timestamps, null for a pass's list).  The sort's buffers are the context's: every decode step waits for the one before.
 int launch_dec(adsb_ctx* c, hipStream_t st, const AirArgs& a, unsigned g, DecRow* rows, const double* ts) {

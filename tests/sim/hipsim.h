@@ -48,6 +48,8 @@ struct Block {
   unsigned bar_gen = 0;
   std::vector<WaveState> waves;
   std::vector<ucontext_t> ctx;
+  std::vector<void*> sp;      // HIPSIM_FAST_SWITCH: each parked fiber's stack pointer, and the scheduler's
+  void* sched_sp = nullptr;
   std::vector<char*> stacks;
   std::vector<char> done;
   ucontext_t sched;
@@ -62,10 +64,32 @@ inline hipsim_dim3& bIdx() { static hipsim_dim3 v; return v; }
 inline hipsim_dim3& bDim() { static hipsim_dim3 v; return v; }
 inline hipsim_dim3& gDim() { static hipsim_dim3 v; return v; }
 
+// A fiber switch.  swapcontext saves and restores the signal mask with a system call at every switch, which is most of its
+// cost; no kernel under test touches signals, so on x86-64 a switch is the callee-saved registers and the stack pointer.
+#if defined(__x86_64__) && defined(__linux__)
+#define HIPSIM_FAST_SWITCH 1
+extern "C" void hipsim_switch(void** save_sp, void* load_sp);
+__asm__(
+    ".text\n"
+    ".weak hipsim_switch\n"
+    ".hidden hipsim_switch\n"
+    ".type hipsim_switch,@function\n"
+    "hipsim_switch:\n"
+    "  pushq %rbp\n  pushq %rbx\n  pushq %r12\n  pushq %r13\n  pushq %r14\n  pushq %r15\n"
+    "  movq %rsp, (%rdi)\n"
+    "  movq %rsi, %rsp\n"
+    "  popq %r15\n  popq %r14\n  popq %r13\n  popq %r12\n  popq %rbx\n  popq %rbp\n"
+    "  ret\n"
+    ".size hipsim_switch,.-hipsim_switch\n");
+#endif
+
+inline void to_sched(Block* b, int me);
+inline void to_fiber(Block* b, int t);
+
 inline void yield() {
   Block* b = cur_block();
   int me = b->cur;
-  swapcontext(&b->ctx[me], &b->sched);
+  to_sched(b, me);
   // resumed: restore my thread index
   tIdx().x = (unsigned)me;
 }
@@ -77,8 +101,32 @@ inline void trampoline() {
   b->body();
   b->done[me] = 1;
   b->ndone++;
-  swapcontext(&b->ctx[me], &b->sched);
+  to_sched(b, me);
 }
+
+#ifdef HIPSIM_FAST_SWITCH
+inline void to_sched(Block* b, int me) { hipsim_switch(&b->sp[me], b->sched_sp); }
+inline void to_fiber(Block* b, int t) { hipsim_switch(&b->sched_sp, b->sp[t]); }
+// a new fiber's stack: six zeroed registers, trampoline as the return address, and above it the slot a caller's return
+// address would take (trampoline never returns), so that it starts with the alignment of a called function
+inline void new_fiber(Block* b, int t) {
+  uintptr_t* p = (uintptr_t*)(((uintptr_t)b->stacks[t] + kStack) & ~(uintptr_t)15);
+  *--p = 0;
+  *--p = (uintptr_t)(void (*)())trampoline;
+  for (int k = 0; k < 6; ++k) *--p = 0;
+  b->sp[t] = p;
+}
+#else
+inline void to_sched(Block* b, int me) { swapcontext(&b->ctx[me], &b->sched); }
+inline void to_fiber(Block* b, int t) { swapcontext(&b->sched, &b->ctx[t]); }
+inline void new_fiber(Block* b, int t) {
+  getcontext(&b->ctx[t]);
+  b->ctx[t].uc_stack.ss_sp = b->stacks[t];
+  b->ctx[t].uc_stack.ss_size = kStack;
+  b->ctx[t].uc_link = nullptr;
+  makecontext(&b->ctx[t], (void (*)())trampoline, 0);
+}
+#endif
 
 inline void run_block(Block& b) {
   cur_block() = &b;
@@ -86,11 +134,7 @@ inline void run_block(Block& b) {
   b.bar_arrived = 0;
   for (int t = 0; t < b.nthreads; ++t) {
     b.done[t] = 0;
-    getcontext(&b.ctx[t]);
-    b.ctx[t].uc_stack.ss_sp = b.stacks[t];
-    b.ctx[t].uc_stack.ss_size = kStack;
-    b.ctx[t].uc_link = nullptr;
-    makecontext(&b.ctx[t], (void (*)())trampoline, 0);
+    new_fiber(&b, t);
   }
   for (auto& w : b.waves) { w.arrived = 0; }
   long spins = 0;
@@ -98,7 +142,7 @@ inline void run_block(Block& b) {
     for (int t = 0; t < b.nthreads; ++t) {
       if (b.done[t]) continue;
       b.cur = t;
-      swapcontext(&b.sched, &b.ctx[t]);
+      to_fiber(&b, t);
     }
     if (++spins > 100000000L) { fprintf(stderr, "hipsim: deadlock (divergent barrier?)\n"); abort(); }
   }
@@ -112,6 +156,9 @@ inline void wave_sync(WaveState& w) {
   else while (w.gen == g) yield();
 }
 
+// the fibers' stacks, kept from launch to launch (a decode call is dozens of launches)
+inline std::vector<char*>& stack_pool() { static std::vector<char*> pool; return pool; }
+
 template <class K, class... A>
 void launch(K kernel, unsigned grid, unsigned block, A... args) {
   assert(block % kWave == 0);
@@ -119,9 +166,12 @@ void launch(K kernel, unsigned grid, unsigned block, A... args) {
   b.nthreads = (int)block;
   b.waves.resize(block / kWave);
   b.ctx.resize(block);
+  b.sp.resize(block);
   b.done.resize(block);
   b.stacks.resize(block);
-  for (unsigned t = 0; t < block; ++t) b.stacks[t] = (char*)malloc(kStack);
+  std::vector<char*>& pool = stack_pool();
+  while (pool.size() < block) pool.push_back((char*)malloc(kStack));
+  for (unsigned t = 0; t < block; ++t) b.stacks[t] = pool[t];
   bDim().x = block;
   gDim().x = grid;
   b.body = [&]() { kernel(args...); };
@@ -129,7 +179,6 @@ void launch(K kernel, unsigned grid, unsigned block, A... args) {
     bIdx().x = g;
     run_block(b);
   }
-  for (unsigned t = 0; t < block; ++t) free(b.stacks[t]);
   cur_block() = nullptr;
 }
 }  // namespace hipsim

@@ -1,7 +1,8 @@
 """ADSB_FLAG_DECODE on the CPU: the decoder's message decoding (decode_message / decode_me, the CPR global decode,
 update_plane, the published ports) against tests/golden/g_decode.npz -- the reference decoder's answers under both msg_filter
 and error_corr values.  A plain-Python replay (tests/decode_replay.py), the host function that turns a row into the
-reference's PDU (_native.decoded_pdu), the emulated kernels (tests/sim/decode_driver.cpp) and the kernels' resources."""
+reference's PDU (_native.decoded_pdu), the emulated kernels (tests/sim/decode_driver.cpp: the product's own sort included;
+the sort alone is tests/test_decode_sort.py) and the kernels' resources."""
 import ctypes
 import json
 import os
@@ -207,10 +208,11 @@ class SimDecoder:
         t = np.ascontiguousarray(ts, dtype=np.float64)
         rows = np.zeros(len(b), dtype=N.DECODED_DTYPE)
         vp = ctypes.c_void_p
-        self.lib.sim_dec_pdus(b.ctypes.data_as(vp), t.ctypes.data_as(vp), ctypes.c_int(len(b)), ctypes.c_int(grid),
+        rc = self.lib.sim_dec_pdus(b.ctypes.data_as(vp), t.ctypes.data_as(vp), ctypes.c_int(len(b)), ctypes.c_int(grid),
                               self.table.ctypes.data_as(vp), self.st.ctypes.data_as(vp), self.planes.ctypes.data_as(vp),
                               ctypes.c_uint(self.epoch), ctypes.c_ulonglong(self.next), ctypes.c_int(self.fec), ctypes.c_int(self.all),
                               rows.ctypes.data_as(vp))
+        assert rc == 0, "the sort wrote outside its %d keys (-1) or left a key that names no record (-2): %d" % (len(b), rc)
         self.next += 1
         return rows
 
@@ -264,6 +266,109 @@ def test_emulated_kernels_many_aircraft_and_edge_addresses(sim):
         assert got["num_msgs"].max() >= 300
         assert {0, 0xFFFFFF} <= set(got["icao"][got["present"] != 0].tolist())
         S.assert_rows_equal(got, exp)
+
+
+SORT_TILE = 4096           # adsb_device.h kSortTile: the keys one workgroup of the sort takes
+BUSY = 0x5A5A5A
+_large = {}
+
+
+def large_stream():
+    """13500 PDUs in timestamp order: 7000 of one aircraft among 6500 of 3000 others, addresses 0 and 0xFFFFFF included."""
+    import decode_streams as S
+    if "stream" not in _large:
+        others = [0, 0xFFFFFF, 1, 0xFFFFFE] + [0x300000 + 4099 * k for k in range(2996)]
+        b0, t0 = S.mixed(np.random.default_rng(31), n=7000, addresses=[BUSY], dt=(0.002, 0.2))
+        b1, t1 = S.mixed(np.random.default_rng(32), n=6500, addresses=others, dt=(0.002, 0.2))
+        order = np.argsort(np.concatenate([t0, t1]), kind="stable")
+        _large["stream"] = np.concatenate([b0, b1])[order], np.concatenate([t0, t1])[order]
+    return _large["stream"]
+
+
+def large_expected(filt, corr):
+    """The replay's rows of large_stream in one decoder.  The busy aircraft's num_msgs counts its events, each of which has a
+    sort key in a call that holds them all: more than a tile of them, so its sorted segment crosses a tile boundary wherever
+    it starts."""
+    import decode_streams as S
+    if (filt, corr) not in _large:
+        b14, ts = large_stream()
+        exp = S.to_rows(D.Decoder(filt, corr).rows(b14, ts))
+        assert len(exp) >= 10000 and exp["num_msgs"][exp["icao"] == BUSY].max() > SORT_TILE + 200
+        planes = set(exp["icao"][(exp["present"] & N.DEC_HAS_PLANE) != 0].tolist())
+        assert len(planes) > 2000 and {0, 0xFFFFFF} <= planes
+        _large[(filt, corr)] = exp
+    return _large[(filt, corr)]
+
+
+LARGE_CONFIGS = (("All Messages", "None"), ("All Messages", "Conservative"), ("Extended Squitter Only", "None"))
+
+
+@pytest.mark.parametrize("filt,corr", LARGE_CONFIGS)
+def test_emulated_kernels_over_several_sort_tiles(sim, filt, corr):
+    """More than three tiles of keys in one call, one aircraft's segment across a tile boundary; then the same stream in calls
+    of a tile - 1, a tile, a tile + 1 and the rest on one decoder: both equal the replay."""
+    import decode_streams as S
+    b14, ts = large_stream()
+    exp = large_expected(filt, corr)
+    S.assert_rows_equal(SimDecoder(sim, filt, corr).call(b14, ts), exp)
+    dec = SimDecoder(sim, filt, corr)
+    cut = np.cumsum([0, SORT_TILE - 1, SORT_TILE, SORT_TILE + 1])
+    assert cut[-1] < len(b14)
+    spans = list(zip(cut, list(cut[1:]) + [len(b14)]))
+    S.assert_rows_equal(np.concatenate([dec.call(b14[lo:hi], ts[lo:hi]) for lo, hi in spans]), exp)
+
+
+# ---- the NL zone edges on the CPR grid -----------------------------------------------------------------------------------------
+EDGES = os.path.join(HERE, "golden", "g_decode_edges.npz")
+GRID = 360.0 / 59 / 131072           # the coarser of the two latitude grids (odd frames); even frames: 6 / 131072
+
+
+@pytest.fixture(scope="module")
+def ge():
+    return np.load(EDGES)
+
+
+def test_edges_golden_holds_fixes_on_the_grid_points_beside_every_edge(ge):
+    """From the reference's answers alone: beside each of the 58 edges, in both hemispheres, fixes on the last grid point below
+    and the first at or above it, from an even and from an odd frame; pairs across an edge without a fix whose altitude is
+    stored; NL = 1, latitude 0, longitudes on each side of 180, latitudes on each side of the 270 wrap, negative j and m."""
+    lat, lon = ge["lat_all_none"].view(np.float64), ge["lon_all_none"].view(np.float64)
+    fix = ~np.isnan(lat)
+    for e in D.NL_EDGES:
+        for sign in (1, -1):
+            a = sign * lat[fix & (np.sign(lat) == sign)]
+            below, above = np.unique(a[(a >= e - GRID) & (a < e)]), np.unique(a[(a >= e) & (a < e + GRID)])
+            assert len(below) >= 2 and len(above) >= 2, (e, sign, below, above)
+    bits = np.unpackbits(ge["bits"], axis=1)
+    fld = lambda lo, n: bits[:, lo:lo + n].dot(1 << np.arange(n - 1, -1, -1))      # noqa: E731
+    sls = seq_slices(ge["seq"])
+    nofix = [sl for sl in sls if not fix[sl].any()]
+    assert len(nofix) >= 2 * 2 * 58 and all((ge["altset_all_none"][sl] == 1).all() for sl in nofix)
+    assert (fix & (np.abs(lat) >= 87) & (np.abs(lat) <= 90)).sum() >= 20 and (fix & (lat == 0)).any()
+    assert (fix & (lon > 179.999)).any() and (fix & (lon < -179.999)).any()
+    assert (fix & (lat > 269.99)).any() and (fix & (lat < -89.999)).any()
+    odd, clat, clon = fld(53, 1), fld(54, 17), fld(71, 17)
+    js, ms = [], []
+    for sl in sls:
+        i = sl.start
+        assert (odd[i], odd[i + 1], odd[i + 2]) == (0, 1, 0) and sl.stop - i == 3
+        js.append(np.floor(59 * clat[i] / 131072 - 60 * clat[i + 1] / 131072 + 0.5))
+        if fix[i + 1]:
+            n = D.nl(lat[i + 1])
+            ms.append(np.floor(clon[i] / 131072 * (n - 1) - clon[i + 1] / 131072 * n + 0.5))
+    assert min(js) < 0 < max(js) and min(ms) < 0 < max(ms)
+
+
+@pytest.mark.parametrize("tag,filt,corr", CONFIGS)
+def test_replay_equals_edges_golden(ge, tag, filt, corr):
+    check_rows(replay_rows(ge, filt, corr), ge, tag)
+
+
+@pytest.mark.parametrize("tag,filt,corr", CONFIGS[:1] + CONFIGS[3:])
+def test_emulated_kernels_equal_edges_golden(sim, ge, tag, filt, corr):
+    """The sequences use distinct addresses: one decoder takes them all in one call, as many aircraft at once."""
+    assert len(set(ge["icao_all_none"].tolist())) == len(seq_slices(ge["seq"]))
+    check_rows(SimDecoder(sim, filt, corr).call(ge["bits"], ge["ts"]), ge, tag)
 
 
 # ---- resources ---------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """Opt-in decode step on the MI355X (ADSB_FLAG_DECODE): adsb_decode_pdus over every sequence of tests/golden/g_decode.npz
-under both msg_filter and error_corr values, whole and cut into pieces; adsb_process_* / adsb_submit_* in three formats at
-two rates over a stream modulated from the golden rows, against the plain-Python replay (tests/decode_replay.py) of the
+and g_decode_edges.npz under both msg_filter and error_corr values, whole and cut into pieces; adsb_process_* /
+adsb_submit_* in three formats at two rates over a stream modulated from the golden rows, against the plain-Python replay (tests/decode_replay.py) of the
 published records -- with calls cut between an aircraft's even and odd frames, three submissions waited for out of order,
 adsb_reset, device memory; records byte-identical to a context without the flag; the refused entry points; blocks.decoder;
 a stream with a new address in every burst over several passes.  The CPU half is tests/test_decode.py."""
@@ -11,7 +11,7 @@ import decode_replay as D
 import decode_streams as S
 from gr_adsb_amd import _native as N
 from gr_adsb_amd import modulator as M
-from test_decode import CONFIGS, GOLD, check_rows, expected, seq_slices
+from test_decode import CONFIGS, EDGES, GOLD, check_rows, expected, seq_slices
 
 pytestmark = pytest.mark.gpu
 
@@ -56,6 +56,17 @@ def test_decode_pdus_equals_golden(native, g, tag, filt, corr):
                 hi = min(lo + step, sl.stop)
                 got[lo:hi] = c.decode_pdus(g["bits"][lo:hi], g["ts"][lo:hi])
         check_rows(got, g, tag)
+
+
+@pytest.mark.parametrize("tag,filt,corr", CONFIGS)
+def test_decode_pdus_equals_edges_golden(native, tag, filt, corr):
+    """The NL zone edges on the CPR grid (tests/golden/g_decode_edges.npz): every sequence has its own address, so one call
+    takes them all; then sequence by sequence."""
+    ge = np.load(EDGES)
+    c = dec_ctx(filt, corr)
+    check_rows(c.decode_pdus(ge["bits"], ge["ts"]), ge, tag)
+    c.reset()
+    check_rows(np.concatenate([c.decode_pdus(ge["bits"][sl], ge["ts"][sl]) for sl in seq_slices(ge["seq"])]), ge, tag)
 
 
 _streams = {}

@@ -1,4 +1,4 @@
-"""Container-only: generate tests/golden/g_decode.npz -- known answers of the REFERENCE decoder's message decoding
+"""Container-only: generate tests/golden/g_decode.npz and tests/golden/g_decode_edges.npz -- known answers of the REFERENCE decoder's message decoding
 (decoder.py:330-352 decode_packet, :883-1060 decode_message, :1065-1301 decode_me, :1309-1512 the CPR global decode, :413-440
 update_plane, :512-538 the published PDUs) for sequences of PDUs, under msg_filter "All Messages" / "Extended Squitter Only"
 and error_corr "None" / "Conservative".  Data only: inputs (packed bits, timestamps, snr, sequence ids) and the reference's
@@ -29,6 +29,10 @@ Outputs per configuration <m>_<e> (m: all / es, e: none / cons), one entry per P
   types_*     for published "decoded" PDUs: type codes of callsign, altitude, speed, heading, vertical_rate, latitude,
               longitude, num_msgs (0 None, 1 int, 2 float, 3 numpy.float64, 4 str)
 Shared: datetime (the published "datetime" string of every PDU), keys_decoded / keys_unknown (the published dicts' keys).
+
+g_decode_edges.npz has the same fields for the sequences of edge_sequences: CPR pairs on the latitude grid points next to each
+of the 58 NL zone edges in both hemispheres with either frame the newer one, pairs whose frames lie on different sides of an
+edge, |latitude| >= 87, latitude 0, longitudes on each side of 180 and CPR latitudes around the 270 wrap.
 """
 import math
 import os
@@ -266,6 +270,80 @@ def decode_sequences(rng, addr):
     return seqs
 
 
+# ---- tests/golden/g_decode_edges.npz: the NL zone edges on the CPR latitude grid --------------------------------------------
+# A decoded latitude is a grid point: 6 k / 131072 degrees from an even frame, (360 / 59) k / 131072 from an odd one (k < 0 in
+# the south).  Around every edge, in both hemispheres, the file holds the fixes of the last grid point below it and of the first
+# one at or above it, from each frame, and pairs whose frames lie on different sides (no fix).
+DLAT = (360.0 / 60, 360.0 / 59)
+
+
+def grid_lat(k, odd):
+    return DLAT[odd] * (k / 131072)
+
+
+def grid_below(e, odd):
+    """The largest k whose grid latitude is below e (e > 0)."""
+    k = int(e / DLAT[odd] * 131072) + 2
+    while not grid_lat(k, odd) < e:
+        k -= 1
+    return k
+
+
+def table_nl(lat):
+    lat = abs(lat)
+    for k, e in enumerate(NL_EDGES):
+        if lat < e:
+            return 59 - k
+    return 1
+
+
+def grid_position(aa, odd, k, lon, alt12):
+    """The position reply of frame `odd` at grid latitude index k (signed) and longitude lon."""
+    dlon = 360.0 / max(table_nl(grid_lat(k, odd)) - odd, 1)
+    xz = math.floor(131072 * (lon % dlon) / dlon + 0.5)
+    return position(aa, odd, k % 131072, int(xz) % 131072, alt12=alt12)
+
+
+def triple(aa, ke, ko, lon, t, rng):
+    """Even, odd, even one second apart: after the second reply the odd frame is the newer one, after the third the even."""
+    alt = [int(v) | 0x10 for v in rng.integers(0, 4096, 3)]
+    return [(grid_position(aa, 0, ke, lon, alt[0]), t), (grid_position(aa, 1, ko, lon, alt[1]), t + 1.0),
+            (grid_position(aa, 0, ke, lon + 0.0001, alt[2]), t + 2.0)]
+
+
+def edge_sequences(rng):
+    addr = iter(rng.permutation(np.arange(0x100000, 0xFFFFFF))[:2000].tolist())
+    seqs = []
+    t = T0
+    for e in NL_EDGES:
+        be, bo = grid_below(e, 0), grid_below(e, 1)
+        for hemi in (1, -1):
+            lon = float(rng.uniform(-180, 180))
+            for ke, ko in ((be, bo), (be + 1, bo + 1), (be, bo + 1), (be + 1, bo)):     # below, above, two straddles
+                t += 7.0
+                seqs.append(triple(next(addr), hemi * ke, hemi * ko, lon, t, rng))
+    # NL = 1 (ni clamped to 1 for the odd frame), the poles' neighbourhood, latitude 0 and its neighbours
+    for lat in (87.5, 89.0, 89.9999, -87.5, -89.0, -89.9999, 0.0, 0.00005, -0.00005):
+        for lon in (-170.0, -0.00001, 0.0, 33.0, 179.99999):
+            t += 7.0
+            ke, ko = int(round(lat / DLAT[0] * 131072)), int(round(lat / DLAT[1] * 131072))
+            seqs.append(triple(next(addr), ke, ko, lon, t, rng))
+    # longitudes on each side of 180 in many zones
+    for lat in (-80.0, -52.3, -10.0, 0.0, 10.0, 33.3, 61.0, 86.0):
+        for lon in (179.9999, 179.99999, 180.0, -179.99999, -179.9999, 180.00001):
+            t += 7.0
+            ke, ko = int(round(lat / DLAT[0] * 131072)), int(round(lat / DLAT[1] * 131072))
+            seqs.append(triple(next(addr), ke, ko, lon, t, rng))
+    # the 270 wrap of lat_even / lat_odd: CPR latitudes around the south pole's (even 0, odd 32768 with j = -15)
+    for yz0 in (131070, 131071, 0, 1, 2):
+        for yz1 in (32766, 32767, 32768, 32769, 32770):
+            t += 7.0
+            a = next(addr)
+            xz = [int(v) for v in rng.integers(0, 131072, 3)]
+            seqs.append([(position(a, 0, yz0, xz[0]), t), (position(a, 1, yz1, xz[1]), t + 1.0), (position(a, 0, yz0, xz[2]), t + 2.0)])
+    return seqs
+
+
 def all_sequences(rng):
     addr = iter(rng.permutation(np.arange(0x100000, 0xFFFFFF))[:6000].tolist())
     seqs = []
@@ -352,9 +430,8 @@ def run(dec, rows, out, keys):
             out["types"].append([0] * 8)
 
 
-def main():
-    rng = np.random.default_rng(20261017)
-    seqs = all_sequences(rng)
+def emit(seqs, rng, name):
+    """Run every sequence through a fresh reference decoder under each configuration and write tests/golden/<name>."""
     rows = [(np.asarray(b, np.uint8), float(ts)) for s in seqs for b, ts in s]
     snr = rng.uniform(0, 40, len(rows)).astype(np.float32)
     bits = np.array([b for b, _ in rows], dtype=np.uint8)
@@ -381,11 +458,19 @@ def main():
         p = res["port_" + tag]
         print(tag, "decoded", int((p == 1).sum()), "unknown", int((p == 2).sum()), "raised", int((p == 3).sum()),
               "planes", len(set(res["icao_" + tag][res["has_" + tag] == 1].tolist())))
-    res["keys_decoded"] = np.array(keys[1])
-    res["keys_unknown"] = np.array(keys[2])
-    path = os.path.join(ROOT, "tests", "golden", "g_decode.npz")
+    for port, key in ((1, "keys_decoded"), (2, "keys_unknown")):
+        if port in keys:
+            res[key] = np.array(keys[port])
+    path = os.path.join(ROOT, "tests", "golden", name)
     np.savez_compressed(path, **res)
     print(path, len(bits), "pdus in", len(seqs), "sequences", os.path.getsize(path), "bytes")
+
+
+def main():
+    rng = np.random.default_rng(20261017)
+    emit(all_sequences(rng), rng, "g_decode.npz")
+    rng = np.random.default_rng(20261018)
+    emit(edge_sequences(rng), rng, "g_decode_edges.npz")
 
 
 if __name__ == "__main__":
