@@ -56,6 +56,12 @@ MAX_IN_FLIGHT = 3
 BATCH_ITEM_DTYPE = np.dtype([("data", "<u8"), ("n", "<i8"), ("abs_offset", "<i8"), ("threshold", "<f4"), ("reserved", "<u4")])
 assert BATCH_ITEM_DTYPE.itemsize == 32
 BATCH_ITEM_MAX = 1 << 22     # ADSB_BATCH_ITEM_MAX: longer items take the ordinary pass inside the call
+# one item of adsb_process_stream_batch* (adsb_stream_item): pointer, samples, stream id, flags (STREAM_END), threshold
+STREAM_ITEM_DTYPE = np.dtype([("data", "<u8"), ("n", "<i8"), ("stream", "<i4"), ("flags", "<u4"), ("threshold", "<f4"),
+                              ("reserved", "<u4")])
+assert STREAM_ITEM_DTYPE.itemsize == 32
+STREAM_END = 1               # ADSB_STREAM_END: the stream's last item
+STREAM_FRESH_EOB = -(1 << 61)    # the carried end-of-burst offset of a fresh stream
 
 EXPORTS = [
     "adsb_abi_version", "adsb_create", "adsb_destroy", "adsb_set_threshold", "adsb_set_stream", "adsb_set_copy_threads", "adsb_host_copy", "adsb_wait_for_event", "adsb_reset", "adsb_framer_state",
@@ -67,6 +73,8 @@ EXPORTS = [
     "adsb_framer_work", "adsb_framer_work_passthrough", "adsb_demod_work", "adsb_shard_bounds", "adsb_process_sharded_device", "adsb_shard_device", "adsb_shard_host", "adsb_shard_fixup", "adsb_stitch", "adsb_snr_db", "adsb_mode_s_syndrome", "adsb_mode_s_fec", "adsb_mode_s_aircraft", "adsb_plan_chunks", "adsb_get_stats",
     "adsb_process_sharded_multi", "adsb_device_alloc", "adsb_device_free", "adsb_device_upload", "adsb_clear_pending_events",
     "adsb_process_batch_device", "adsb_process_batch",
+    "adsb_streams_open", "adsb_streams_close", "adsb_stream_set_base", "adsb_stream_state", "adsb_stream_reset",
+    "adsb_process_stream_batch", "adsb_process_stream_batch_device",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
 ]
 
@@ -158,8 +166,13 @@ def load():
     lib.adsb_shard_bounds.restype = c.c_int32
     lib.adsb_process_sharded_device.argtypes = [vp, c.c_int, vp, i64, i64, i32, vp, i32, c.POINTER(i32)]
     lib.adsb_process_sharded_multi.argtypes = [c.POINTER(vp), i32, c.c_int, vp, i64, i64, i32, vp, i32, c.POINTER(i32), c.POINTER(MultiStats)]
-    for name in ("adsb_process_batch_device", "adsb_process_batch"):
+    for name in ("adsb_process_batch_device", "adsb_process_batch", "adsb_process_stream_batch_device", "adsb_process_stream_batch"):
         getattr(lib, name).argtypes = [vp, c.c_int, vp, i32, vp, i32, vp, c.POINTER(i32), c.POINTER(i32)]
+    lib.adsb_streams_open.argtypes = [vp, i32]
+    lib.adsb_streams_close.argtypes = [vp]
+    lib.adsb_stream_set_base.argtypes = [vp, i32, i64]
+    lib.adsb_stream_state.argtypes = [vp, i32, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
+    lib.adsb_stream_reset.argtypes = [vp, i32]
     lib.adsb_device_alloc.argtypes = [vp, c.POINTER(vp), c.c_size_t]
     lib.adsb_device_free.argtypes = [vp, vp]
     lib.adsb_device_upload.argtypes = [vp, vp, vp, c.c_size_t]
@@ -379,6 +392,65 @@ class Context:
                 arrays[k][...] = a
         return self._batch(self.lib.adsb_process_batch, fmt, [a.ctypes.data for a in arrays], [len(a) // per for a in arrays],
                            thresholds, abs_offsets)
+
+    # Receiver streams carried across batch calls (adsb_process_stream_batch*; include/adsb_hip.h has the contract)
+    def open_streams(self, n_streams):
+        self._chk(self.lib.adsb_streams_open(self._h, int(n_streams)))
+
+    def close_streams(self):
+        self._chk(self.lib.adsb_streams_close(self._h))
+
+    def set_stream_base(self, stream, abs_offset):
+        self._chk(self.lib.adsb_stream_set_base(self._h, int(stream), int(abs_offset)))
+
+    def stream_state(self, stream):
+        """(pos, eob, n_overlong): samples consumed, the carried end-of-burst offset (STREAM_FRESH_EOB on a fresh stream),
+        pulses / bursts left out because they ran past a call's buffer"""
+        p, e, o = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._chk(self.lib.adsb_stream_state(self._h, int(stream), ctypes.byref(p), ctypes.byref(e), ctypes.byref(o)))
+        return p.value, e.value, o.value
+
+    def reset_stream(self, stream):
+        self._chk(self.lib.adsb_stream_reset(self._h, int(stream)))
+
+    def _stream_batch(self, fn, fmt, ids, ptrs, ns, thresholds, end, cap=None):
+        k = len(ids)
+        items = np.zeros(k, dtype=STREAM_ITEM_DTYPE)
+        items["data"] = np.asarray(ptrs, dtype=np.uint64)
+        items["n"] = np.asarray(ns, dtype=np.int64)
+        items["stream"] = np.asarray(ids, dtype=np.int32)
+        items["flags"] = np.where(np.broadcast_to(np.asarray(end, dtype=bool), (k,)), STREAM_END, 0)
+        items["threshold"] = self._thr if thresholds is None else np.asarray(thresholds, dtype=np.float32)
+        first = np.zeros(k + 1, dtype=np.int32)
+        n_out, n_fb = ctypes.c_int32(0), ctypes.c_int32(0)
+        fixed = cap is not None
+        cap = cap if fixed else getattr(self, "_batch_cap", 1 << 16)
+        while True:
+            out = np.empty(cap, dtype=BURST_DTYPE)
+            rc = fn(self._h, int(fmt), ctypes.c_void_p(items.ctypes.data), k, ctypes.c_void_p(out.ctypes.data), cap,
+                    ctypes.c_void_p(first.ctypes.data), ctypes.byref(n_out), ctypes.byref(n_fb))
+            if rc == -28 and n_out.value > cap and not fixed:      # -ENOSPC: no stream has moved, the call is repeated
+                cap = self._batch_cap = n_out.value + n_out.value // 4
+                continue
+            self.last_stream_needed = n_out.value
+            self._chk(rc)
+            break
+        self.last_batch_fallbacks = n_fb.value
+        return out[:n_out.value].copy(), first
+
+    def process_stream_batch_device(self, fmt, ids, ptrs, ns, thresholds=None, end=False, cap=None):
+        """The next chunk of streams ids[i] in one device pass (adsb_process_stream_batch_device): ptrs[i] = device pointer
+        (aligned to a sample) of ns[i] new samples; end: bool or one per item (STREAM_END).  Returns (records, item_first).
+        cap: a fixed output capacity (the call raises AdsbError -ENOSPC instead of growing it; last_stream_needed = the
+        number of records needed)."""
+        return self._stream_batch(self.lib.adsb_process_stream_batch_device, fmt, ids, [int(p) for p in ptrs], ns, thresholds, end, cap)
+
+    def process_stream_batch(self, fmt, ids, arrays, thresholds=None, end=False, cap=None):
+        """The same for host arrays in the format's layout, any length and alignment (adsb_process_stream_batch)."""
+        dt, per = FMT_LAYOUT[int(fmt)]
+        arrays = [np.ascontiguousarray(a, dtype=dt) for a in arrays]
+        return self._stream_batch(self.lib.adsb_process_stream_batch, fmt, ids, [a.ctypes.data for a in arrays],
+                                  [len(a) // per for a in arrays], thresholds, end, cap)
 
     def submit_format_device(self, fmt, dev_ptr, n, abs_offset=0):
         return self._submit(int(fmt), dev_ptr, n, abs_offset)

@@ -2790,6 +2790,67 @@ __global__ void __launch_bounds__(kThreads) k_dec_pdu_flags(const unsigned char*
   }
 }
 
+// ---- k_stream_stage / k_stream_save: the sample plumbing of receiver streams around k_batch (adsb_process_stream_batch*) ----
+// A stream keeps its last samples -- the next call's back halo and look-ahead, in the wire format -- in a carry store on the
+// device.  In front of k_batch, k_stream_stage assembles item b's contiguous buffer [stream carry | new chunk] in the
+// library's staging buffer (the host entry point has uploaded the chunk into place already: chunk.bytes == 0); behind the
+// pack step, k_stream_save copies the buffer's last samples into the stream's OTHER carry slot (the host flips the two when
+// the call is delivered, so a call that is refused for want of room can be repeated) and puts the item's status where the
+// host reads it.  One workgroup per item, no LDS.
+// A copy moves whole samples (unit = 2, 4 or 8 bytes; both addresses are multiples of it): 16-byte vectors where source and
+// destination agree modulo 16, between ragged ends of single samples, and single samples throughout where they do not.
+struct StreamCopy { const void* src; void* dst; long long bytes; };
+struct StreamStage { StreamCopy carry, chunk; int unit, pad; };
+struct StreamSave { StreamCopy carry; int unit, pad; };
+struct StreamStatus { int kept; unsigned flags; };       // k_batch's verdict for the item; its Summary.flags (bit 2: halo exceeded)
+typedef unsigned long long stream_v16 __attribute__((vector_size(16), may_alias));
+typedef unsigned long long __attribute__((may_alias)) stream_u8;
+typedef unsigned __attribute__((may_alias)) stream_u4;
+typedef unsigned short __attribute__((may_alias)) stream_u2;
+template <class T>
+__device__ __forceinline__ void stream_copy_as(char* d, const char* s, long long lo, long long hi) {
+  for (long long i = lo + (long long)threadIdx.x * (long long)sizeof(T); i < hi; i += (long long)kThreads * (long long)sizeof(T))
+    *reinterpret_cast<T*>(d + i) = *reinterpret_cast<const T*>(s + i);
+}
+__device__ __forceinline__ void stream_copy_samples(char* d, const char* s, long long lo, long long hi, int unit) {
+  if (unit == 8) stream_copy_as<stream_u8>(d, s, lo, hi);
+  else if (unit == 4) stream_copy_as<stream_u4>(d, s, lo, hi);
+  else stream_copy_as<stream_u2>(d, s, lo, hi);
+}
+__device__ __forceinline__ void stream_copy(const StreamCopy& c, int unit) {
+  if (c.bytes <= 0) return;
+  char* d = static_cast<char*>(c.dst);
+  const char* s = static_cast<const char*>(c.src);
+  long long head = c.bytes, body = c.bytes;                    // [0, head) and [body, bytes): samples; [head, body): vectors
+  const unsigned long long da = reinterpret_cast<unsigned long long>(d), sa = reinterpret_cast<unsigned long long>(s);
+  if (((da ^ sa) & 15ull) == 0ull) {
+    head = (long long)((16ull - (da & 15ull)) & 15ull);
+    if (head > c.bytes) head = c.bytes;
+    body = head + ((c.bytes - head) & ~15ll);
+  }
+  stream_copy_samples(d, s, 0, head, unit);
+  stream_copy_as<stream_v16>(d, s, head, body);
+  stream_copy_samples(d, s, body, c.bytes, unit);
+}
+__global__ void __launch_bounds__(kThreads) k_stream_stage(const StreamStage* __restrict__ tab) {
+  const StreamStage e = tab[blockIdx.x];
+  stream_copy(e.carry, e.unit);
+  stream_copy(e.chunk, e.unit);
+}
+__global__ void __launch_bounds__(kThreads) k_stream_save(const StreamSave* __restrict__ tab, const TailArgs* __restrict__ ta,
+                                                          const int* __restrict__ kept, StreamStatus* __restrict__ status) {
+  const int b = (int)blockIdx.x;
+  const StreamSave e = tab[b];
+  stream_copy(e.carry, e.unit);
+  if (threadIdx.x == 0) {
+    const Summary* s = ta[b].sum;                              // (null: the item ran no pass)
+    StreamStatus st;
+    st.kept = kept[b];
+    st.flags = s ? s->flags : 0u;
+    status[b] = st;
+  }
+}
+
 }  // namespace adsb
 
 // Stage 2 of the decode step.  Outside adsb, in an unnamed namespace: the three kernels are the including unit's own, so the

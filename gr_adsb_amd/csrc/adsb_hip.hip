@@ -269,6 +269,29 @@ struct BatchBufs {
   PinnedBuf h_out;               // device-visible: the dense list (its head straight from k_batch_pack)
 };
 
+// adsb_process_stream_batch*: the receiver streams of a context (adsb_streams_open).  Host state per stream, its last
+// samples on the device in two slots of the widest format's size, and the buffers of one call.
+struct StreamState {
+  long long pos = 0;                   // samples consumed
+  long long eob = kStreamFreshEob;     // carried end-of-burst offset (record offsets: base included)
+  long long base = 0;                  // what the records' offsets add to the stream's sample index
+  long long overlong = 0;              // pulses / bursts left out because they ran past a call's buffer
+  int cur = 0;                         // the carry slot that holds the stream's last samples
+  int fmt = -1;                        // the format the stream started with (-1: fresh)
+};
+// fresh again (adsb_stream_reset, adsb_reset): the base stays, the overlong count starts over.  (An END item leaves the
+// stream fresh too, but keeps its count.)
+inline void stream_make_fresh(StreamState& s) { s.pos = 0; s.eob = kStreamFreshEob; s.overlong = 0; s.fmt = -1; }
+struct StreamBufs {
+  std::vector<StreamState> st;
+  size_t slot_bytes = 0;         // one carry slot: stream_carry_max(sps) complex64 samples, whole 256-byte lines
+  DevBuf d_carry;                // [n_streams][2][slot_bytes]
+  DevBuf d_stage;                // this call's item buffers [stream carry | new chunk], each on a 256-byte boundary
+  DevBuf d_tab;                  // StreamStage[n_items], StreamSave[n_items]
+  PinnedBuf h_tab;               // ... as the host builds them
+  PinnedBuf h_status;            // device-visible: StreamStatus[n_items] (k_stream_save)
+};
+
 }  // namespace
 
 // Host threads that copy a pageable source into the pinned staging ring of a host-fed submission: one host core moves
@@ -425,6 +448,7 @@ struct adsb_ctx {
   DevBuf d_dec_keys, d_dec_sorted, d_dec_tmp;
   PinnedBuf h_pdu;                    // adsb_decode_pdus' staging (device-visible)
   BatchBufs bt;                       // adsb_process_batch*
+  StreamBufs sb;                      // adsb_process_stream_batch*
   char err[256] = {0};
   __attribute__((visibility("hidden"))) ~adsb_ctx() = default;   // (the library's exported names stay its C entry points)
 };
@@ -1275,14 +1299,28 @@ int batch_slots_ok(adsb_ctx* c, const adsb_batch_item* items, int32_t n_items) {
   return 0;
 }
 
-// items[i].data: memory the device can read.  Arguments have been checked (check_batch).
-int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_items, adsb_burst* out, int32_t cap,
-              int32_t* item_first, int32_t* n_out, int32_t* n_fallback) {
-  *n_out = 0;
-  item_first[0] = 0;
-  if (n_fallback) *n_fallback = 0;
-  if (n_items == 0) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
+// One item of a batch pass as batch_core runs it: its plan (the buffer the device reads included), its threshold, and who
+// runs it -- k_batch, nobody (no samples, or nothing owned), or the host through the ordinary pass (longer than
+// ADSB_BATCH_ITEM_MAX; k_batch hands back the items whose lists overflow itself).
+struct BatchWork { Plan plan; float thr; enum Kind { kEmpty, kKernel, kHost } kind; };
+// the two small kernels of a stream batch around k_batch / the pack step (run_stream_batch), their tables on the device
+struct StreamHooks { const StreamStage* stage; const StreamSave* save; StreamStatus* status; };
+// What batch_core leaves: the dense list of the items k_batch finished (item i: packed[first[i] .. first[i + 1]), kept[i]
+// >= 0) and, per item it did not (kept[i] < 0), the records and the Summary flags of its ordinary pass (fb[fb_of[i]]).
+struct BatchResult {
+  const adsb_burst* packed = nullptr;
+  const int* first = nullptr;
+  const int* kept = nullptr;
+  long long nb = 0;
+  int32_t nfb = 0;
+  std::vector<std::vector<adsb_burst>> fb;
+  std::vector<unsigned> fb_flags;
+  std::vector<int32_t> fb_of;
+};
+
+// The device pass of a batch: the tables, k_batch, k_batch_pack, k_fec, and the ordinary pass for what is left.
+int batch_core(adsb_ctx* c, int fmt, const std::vector<BatchWork>& work, const StreamHooks* hooks, BatchResult* R) {
+  const int32_t n_items = (int32_t)work.size();
   BatchBufs& B = c->bt;
   const hipStream_t st = c->stream;
   int r;
@@ -1293,12 +1331,15 @@ int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_item
   for (int32_t i = 0; i < n_items; ++i) {
     BatchLay& L = lay[(size_t)i];
     L.slots = 0;
-    if (items[i].n == 0 || items[i].n > kBatchItemMax) continue;
-    L = plan_batch_layout(total, plan_batch_item(items[i].n, c->sps, kWaves, kWTile), kWaves, kThreads, sizeof(Rec), sizeof(LongRise));
+    if (work[(size_t)i].kind != BatchWork::kKernel) continue;
+    // (plan_batch_item takes a canonical call's length: its scan range ends 8 * sps - 1 samples in front of that)
+    L = plan_batch_layout(total, plan_batch_item(work[(size_t)i].plan.scan_hi + (8ll * c->sps - 1), c->sps, kWaves, kWTile), kWaves,
+                          kThreads, sizeof(Rec), sizeof(LongRise));
     total = L.end;
     packed_cap += L.slots;
   }
-  if ((r = batch_slots_ok(c, items, n_items))) return r;
+  // the dense list and item_first are 32-bit: a batch whose lists have 2^31 slots or more is refused
+  if (packed_cap >= (1ll << 31)) return fail(c, -EINVAL, "adsb_process_batch: batch too large for one call (list slots >= 2^31)");
   const long long kHostRecs = 32768;
   const size_t tab_bytes = (size_t)n_items * (sizeof(DetectArgs) + sizeof(TailArgs));
   if ((r = ensure(c, B.d_scratch, total + 128))) return r;
@@ -1322,9 +1363,9 @@ int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_item
   const bool long_aware = (c->flags & ADSB_FLAG_LONG_AWARE_GATE) != 0;
   for (int32_t i = 0; i < n_items; ++i) {
     const BatchLay& L = lay[(size_t)i];
-    if (L.slots == 0) { hda[i].n = items[i].n == 0 ? 0 : -1; continue; }     // empty, or the host's own (too long)
-    fill_batch_item(hda[i], hta[i], plan_canonical(fmt, items[i].data, items[i].n, items[i].abs_offset, c->sps), L, sc, fx[i],
-                    items[i].threshold, c->scale[fmt], c->sps, long_aware, kWaves);
+    const BatchWork& w = work[(size_t)i];
+    if (L.slots == 0) { hda[i].n = w.kind == BatchWork::kEmpty ? 0 : -1; continue; }     // empty, or the host's own (too long)
+    fill_batch_item(hda[i], hta[i], w.plan, L, sc, fx[i], w.thr, c->scale[fmt], c->sps, long_aware, kWaves);
   }
   if ((r = apply_ext(c, st))) return r;
   HIPCHK(c, hipMemcpyAsync(B.d_da.p, hda, (size_t)n_items * sizeof(DetectArgs), hipMemcpyHostToDevice, st));
@@ -1332,6 +1373,7 @@ int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_item
   HIPCHK(c, hipMemsetAsync(B.d_fixed.p, 0, (size_t)n_items * sizeof(BatchFixed), st));
   int* const h_first = (int*)B.h_first.p;
   int* const h_kept = h_first + n_items + 1;
+  if (hooks) hipLaunchKernelGGL(k_stream_stage, dim3(n_items), dim3(kThreads), 0, st, hooks->stage);
   ADSB_BY_MODE(fmt, launch_batch, st, c->sps, (int)n_items, (const DetectArgs*)B.d_da.p, (const TailArgs*)B.d_ta.p, (int*)B.d_kept.p);
   hipLaunchKernelGGL(k_batch_pack, dim3(n_items), dim3(kThreads), 0, st, (const TailArgs*)B.d_ta.p, (const int*)B.d_kept.p,
                      (int)n_items, (Rec*)B.d_packed.p, (int)packed_cap, h_first, h_kept, (Summary*)B.d_tot.p, (Rec*)B.h_out.p,
@@ -1339,6 +1381,10 @@ int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_item
   if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) {
     hipLaunchKernelGGL(k_fec, dim3(step_grid(packed_cap, kThreads)), dim3(kThreads), 0, st, (Rec*)B.d_packed.p,
                        (const Summary*)B.d_tot.p, (int)packed_cap, (Rec*)B.h_out.p, (int)host_cap);
+  }
+  if (hooks) {
+    hipLaunchKernelGGL(k_stream_save, dim3(n_items), dim3(kThreads), 0, st, hooks->save, (const TailArgs*)B.d_ta.p,
+                       (const int*)B.d_kept.p, hooks->status);
   }
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(st));
@@ -1351,25 +1397,23 @@ int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_item
     HIPCHK(c, hipMemcpyAsync(B.h_out.p, B.d_packed.p, (size_t)nb * sizeof(Rec), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
   }
-  const adsb_burst* const packed = (const adsb_burst*)B.h_out.p;
+  R->packed = (const adsb_burst*)B.h_out.p;
+  R->first = h_first;
+  R->kept = h_kept;
+  R->nb = nb;
   int32_t nfb = 0;
   for (int32_t i = 0; i < n_items; ++i) nfb += h_kept[i] < 0 ? 1 : 0;
-  if (n_fallback) *n_fallback = nfb;
-  if (nfb == 0) {
-    *n_out = (int32_t)nb;
-    for (int32_t i = 0; i <= n_items; ++i) item_first[i] = h_first[i];
-    if (nb > cap) return fail(c, -ENOSPC, "output array too small");
-    if (nb > 0) memcpy(out, packed, (size_t)nb * sizeof(adsb_burst));
-    return 0;
-  }
-  // The items k_batch could not finish (or was not given): each through the ordinary pass, as a blocking canonical pass with
-  // the item's threshold -- enqueue / finish regrow the list capacity themselves -- and its records take the item's place.
+  R->nfb = nfb;
+  if (nfb == 0) return 0;
+  // The items k_batch could not finish (or was not given): each through the ordinary pass, as a blocking pass with the
+  // item's plan and threshold -- enqueue / finish regrow the list capacity themselves -- and its records take the item's place.
   // The pass runs in a pipeline slot OTHER than the one adsb_last_result refers to (no slot is busy: check_batch), so the
   // previous call's records, their count and any view the caller holds into that slot's pinned buffer stay as they are; the
   // context's threshold and its list-capacity multiplier are put back afterwards (an item's density says nothing about the
   // caller's other streams).  stats.calls / stats.retries do count these passes.
-  std::vector<std::vector<adsb_burst>> fb((size_t)nfb);
-  std::vector<int32_t> fb_of((size_t)n_items, -1);
+  R->fb.assign((size_t)nfb, std::vector<adsb_burst>());
+  R->fb_flags.assign((size_t)nfb, 0u);
+  R->fb_of.assign((size_t)n_items, -1);
   const float thr_saved = c->thr;
   const int shift_saved = c->rec_cap_shift;
   Slot& fs = c->slot[(c->last_slot + 1) % ADSB_MAX_IN_FLIGHT];
@@ -1377,56 +1421,77 @@ int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_item
   int rc = 0;
   for (int32_t i = 0; i < n_items && rc == 0; ++i) {
     if (h_kept[i] >= 0) continue;
-    Plan pl = plan_canonical(fmt, items[i].data, items[i].n, items[i].abs_offset, c->sps);
+    Plan pl = work[(size_t)i].plan;
     pl.long_aware = long_aware;
     Summary s;
     int32_t nres = 0;
-    c->thr = items[i].threshold;
+    c->thr = work[(size_t)i].thr;
     rc = enqueue(c, fs, pl, false);
     if (rc == 0) rc = finish(c, fs, &s, &nres);
     if (rc == 0 && nres > 0) {
       const adsb_burst* src = (const adsb_burst*)fs.h_out.p;
-      fb[(size_t)k].assign(src, src + nres);
+      R->fb[(size_t)k].assign(src, src + nres);
     }
-    fb_of[(size_t)i] = k++;
+    if (rc == 0) R->fb_flags[(size_t)k] = s.flags;
+    R->fb_of[(size_t)i] = k++;
   }
   c->thr = thr_saved;
   c->rec_cap_shift = shift_saved;
-  if (rc) return rc;
+  return rc;
+}
+
+// items[i].data: memory the device can read.  Arguments have been checked (check_batch).
+int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_items, adsb_burst* out, int32_t cap,
+              int32_t* item_first, int32_t* n_out, int32_t* n_fallback) {
+  *n_out = 0;
+  item_first[0] = 0;
+  if (n_fallback) *n_fallback = 0;
+  if (n_items == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  int r;
+  if ((r = batch_slots_ok(c, items, n_items))) return r;
+  std::vector<BatchWork> work((size_t)n_items);
+  for (int32_t i = 0; i < n_items; ++i) {
+    work[(size_t)i].plan = plan_canonical(fmt, items[i].data, items[i].n, items[i].abs_offset, c->sps);
+    work[(size_t)i].thr = items[i].threshold;
+    work[(size_t)i].kind = items[i].n == 0 ? BatchWork::kEmpty : items[i].n > kBatchItemMax ? BatchWork::kHost : BatchWork::kKernel;
+  }
+  BatchResult R;
+  if ((r = batch_core(c, fmt, work, nullptr, &R))) return r;
+  if (n_fallback) *n_fallback = R.nfb;
   long long tot = 0;
   for (int32_t i = 0; i < n_items; ++i) {
     item_first[i] = (int32_t)tot;
-    tot += fb_of[(size_t)i] >= 0 ? (long long)fb[(size_t)fb_of[(size_t)i]].size() : (long long)(h_first[i + 1] - h_first[i]);
+    tot += R.kept[i] < 0 ? (long long)R.fb[(size_t)R.fb_of[(size_t)i]].size() : (long long)(R.first[i + 1] - R.first[i]);
     if (tot >= (1ll << 31)) return fail(c, -EINVAL, "adsb_process_batch: more than 2^31 records");
   }
   item_first[n_items] = (int32_t)tot;
   *n_out = (int32_t)tot;
   if (tot > cap) return fail(c, -ENOSPC, "output array too small");
+  if (R.nfb == 0) {
+    if (tot > 0) memcpy(out, R.packed, (size_t)tot * sizeof(adsb_burst));
+    return 0;
+  }
   for (int32_t i = 0; i < n_items; ++i) {
     const int32_t cnt = item_first[i + 1] - item_first[i];
     if (cnt == 0) continue;
-    const adsb_burst* src = fb_of[(size_t)i] >= 0 ? fb[(size_t)fb_of[(size_t)i]].data() : packed + h_first[i];
+    const adsb_burst* src = R.kept[i] < 0 ? R.fb[(size_t)R.fb_of[(size_t)i]].data() : R.packed + R.first[i];
     memcpy(out + item_first[i], src, (size_t)cnt * sizeof(adsb_burst));
   }
   return 0;
 }
 
-// adsb_process_batch: every item into ONE device buffer of the context (each on a 256-byte boundary).  Page-locked sources are
-// DMA'd where they lie; pageable ones go through the staging ring, consecutive items gathered into one ring chunk (by the
-// context's copy threads, like staged_copy) and sent with one DMA (an item larger than a chunk: staged_copy, in pieces).
-int upload_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_items, std::vector<adsb_batch_item>* dev) {
+// Host chunks into ONE device buffer, chunk i at byte offset off[i] (ascending, no overlap).  Page-locked sources are DMA'd
+// where they lie; pageable ones go through the staging ring, consecutive chunks gathered into one ring chunk at their
+// device spacing (by the context's copy threads, like staged_copy) and sent with one DMA -- the bytes BETWEEN two gathered
+// chunks are overwritten with whatever the ring held -- (a chunk larger than a ring chunk: staged_copy, in pieces).
+struct HostChunk { const void* src; size_t bytes, off; };
+int upload_chunks(adsb_ctx* c, char* d, const std::vector<HostChunk>& ch) {
   constexpr size_t kRingChunk = (size_t)16 << 20;
-  const size_t bps = (size_t)mode_bytes(fmt);
-  std::vector<size_t> off((size_t)n_items + 1);
-  size_t total = 0;
-  for (int32_t i = 0; i < n_items; ++i) { off[(size_t)i] = total; total += ((size_t)items[i].n * bps + 255) & ~(size_t)255; }
-  off[(size_t)n_items] = total;
   int rc;
-  if ((rc = ensure(c, c->bt.d_in, total + 256))) return rc;
   if ((rc = ensure_pool(c))) return rc;
   const hipStream_t st = c->stream;
   if ((rc = apply_ext(c, st))) return rc;
-  char* const d = (char*)c->bt.d_in.p;
   int cur = -1;                 // ring chunk being filled, or -1
   size_t cur_lo = 0, cur_hi = 0;   // ... with the device range [cur_lo, cur_hi)
   auto flush = [&]() -> int {
@@ -1439,19 +1504,17 @@ int upload_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_i
     cur = -1;
     return 0;
   };
-  for (int32_t i = 0; i < n_items; ++i) {
-    const size_t bytes = (size_t)items[i].n * bps, o = off[(size_t)i];
-    (*dev)[(size_t)i] = items[i];
-    (*dev)[(size_t)i].data = d + o;
+  for (const HostChunk& h : ch) {
+    const size_t bytes = h.bytes, o = h.off;
     if (bytes == 0) continue;
-    if (is_pinned_host(items[i].data)) {
+    if (is_pinned_host(h.src)) {
       if ((rc = flush())) return rc;
-      HIPCHK(c, hipMemcpyAsync(d + o, items[i].data, bytes, hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemcpyAsync(d + o, h.src, bytes, hipMemcpyHostToDevice, st));
       continue;
     }
     if (bytes > kRingChunk) {
       if ((rc = flush())) return rc;
-      if ((rc = staged_copy(c, d + o, items[i].data, bytes, st))) return rc;
+      if ((rc = staged_copy(c, d + o, h.src, bytes, st))) return rc;
       continue;
     }
     if (cur >= 0 && o + bytes - cur_lo > kRingChunk) { if ((rc = flush())) return rc; }
@@ -1462,10 +1525,149 @@ int upload_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_i
       if (c->ring_used[cur]) HIPCHK(c, hipEventSynchronize(c->ring_done[cur]));     // the chunk's previous DMA has read it
       cur_lo = o;
     }
-    c->pool->copy((char*)c->h_ring[cur].p + (o - cur_lo), (const char*)items[i].data, bytes);     // (the context's copy threads)
+    c->pool->copy((char*)c->h_ring[cur].p + (o - cur_lo), (const char*)h.src, bytes);     // (the context's copy threads)
     cur_hi = o + bytes;
   }
   return flush();
+}
+
+// adsb_process_batch: every item into ONE device buffer of the context (each on a 256-byte boundary).
+int upload_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_items, std::vector<adsb_batch_item>* dev) {
+  const size_t bps = (size_t)mode_bytes(fmt);
+  std::vector<HostChunk> ch((size_t)n_items);
+  size_t total = 0;
+  for (int32_t i = 0; i < n_items; ++i) {
+    ch[(size_t)i] = HostChunk{items[i].data, (size_t)items[i].n * bps, total};
+    total += ((size_t)items[i].n * bps + 255) & ~(size_t)255;
+  }
+  int rc;
+  if ((rc = ensure(c, c->bt.d_in, total + 256))) return rc;
+  char* const d = (char*)c->bt.d_in.p;
+  for (int32_t i = 0; i < n_items; ++i) {
+    (*dev)[(size_t)i] = items[i];
+    (*dev)[(size_t)i].data = d + ch[(size_t)i].off;
+  }
+  return upload_chunks(c, d, ch);
+}
+
+// ---- adsb_process_stream_batch*: receiver streams carried across batch calls -------------------------------------------------
+// One call pushes the next chunk of any subset of the context's streams through ONE k_batch launch: item i is one overlapped
+// time shard of its stream (adsb_plan.h: plan_stream_item) whose gate starts from the stream's carried end-of-burst offset.
+// Around the launch, k_stream_stage assembles each item's buffer [stream carry | new chunk] in d_stage and k_stream_save keeps
+// the buffer's last samples for the next call.  A stream's carry has two slots: the save step writes the one the stage step
+// did not read, and the host flips them when the call's records are delivered -- so a call that fails (-ENOSPC) has moved
+// nothing and can be repeated.
+int check_stream_batch(adsb_ctx* c, int fmt, const adsb_stream_item* items, int32_t n_items, bool device, adsb_burst* out,
+                       int32_t cap, int32_t* item_first, int32_t* n_out) {
+  if (!c) return -EINVAL;
+  if (fmt < 0 || fmt >= ADSB_FMT_COUNT) return fail(c, -EINVAL, "adsb_process_stream_batch: bad format");
+  if (n_items < 0 || (n_items > 0 && !items) || cap < 0 || (cap > 0 && !out) || !item_first || !n_out)
+    return fail(c, -EINVAL, "adsb_process_stream_batch: bad argument");
+  if (c->flags & (ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE | ADSB_FLAG_CONFIDENCE))
+    return fail(c, -EINVAL, "adsb_process_stream_batch: not for ADSB_FLAG_AIRCRAFT_TABLE / _DECODE / _CONFIDENCE contexts (one receiver each)");
+  StreamBufs& S = c->sb;
+  if (S.st.empty()) return fail(c, -EINVAL, "adsb_process_stream_batch: no streams (adsb_streams_open first)");
+  const uintptr_t unit = (uintptr_t)mode_bytes(fmt);
+  std::vector<char> seen(S.st.size(), 0);
+  for (int32_t i = 0; i < n_items; ++i) {
+    const adsb_stream_item& it = items[i];
+    if (it.reserved != 0u || (it.flags & ~ADSB_STREAM_END)) return fail(c, -EINVAL, "adsb_process_stream_batch: item.reserved / unknown item.flags must be 0");
+    if (it.n < 0) return fail(c, -EINVAL, "adsb_process_stream_batch: item.n < 0");
+    if (it.n > 0 && !it.data) return fail(c, -EINVAL, "adsb_process_stream_batch: item.data is NULL");
+    if (device && it.n > 0 && ((uintptr_t)it.data % unit) != 0) return fail(c, -EINVAL, "adsb_process_stream_batch: item.data must be aligned to a sample");
+    if (it.stream < 0 || (size_t)it.stream >= S.st.size()) return fail(c, -EINVAL, "adsb_process_stream_batch: no such stream");
+    if (seen[(size_t)it.stream]) return fail(c, -EINVAL, "adsb_process_stream_batch: a stream appears twice in one call");
+    seen[(size_t)it.stream] = 1;
+    const StreamState& s = S.st[(size_t)it.stream];
+    if (s.pos > 0 && s.fmt != fmt) return fail(c, -EINVAL, "adsb_process_stream_batch: the stream started with another format");
+  }
+  return require_idle(c, kCallPending);
+}
+
+int run_stream_batch(adsb_ctx* c, int fmt, const adsb_stream_item* items, int32_t n_items, bool device, adsb_burst* out, int32_t cap,
+                     int32_t* item_first, int32_t* n_out, int32_t* n_fallback) {
+  *n_out = 0;
+  item_first[0] = 0;
+  if (n_fallback) *n_fallback = 0;
+  if (n_items == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  StreamBufs& S = c->sb;
+  const hipStream_t st = c->stream;
+  const int sps = c->sps, bps = mode_bytes(fmt);
+  int r;
+  // every item's buffer on a 256-byte boundary of the staging buffer
+  std::vector<StreamItem> plan((size_t)n_items);
+  std::vector<size_t> off((size_t)n_items);
+  size_t total = 0;
+  for (int32_t i = 0; i < n_items; ++i) {
+    const StreamState& s = S.st[(size_t)items[i].stream];
+    plan[(size_t)i] = plan_stream_item(fmt, s.pos, items[i].n, (items[i].flags & ADSB_STREAM_END) != 0, s.base, s.eob, sps);
+    off[(size_t)i] = total;
+    total += ((size_t)plan[(size_t)i].n_buf * (size_t)bps + 255) & ~(size_t)255;
+  }
+  const size_t tab_bytes = (size_t)n_items * (sizeof(StreamStage) + sizeof(StreamSave));
+  if ((r = ensure(c, S.d_stage, total + 256))) return r;
+  if ((r = ensure(c, S.d_tab, tab_bytes))) return r;
+  if ((r = ensure_pinned(c, S.h_tab, tab_bytes))) return r;
+  if ((r = ensure_pinned(c, S.h_status, (size_t)n_items * sizeof(StreamStatus), true))) return r;
+  char* const d = (char*)S.d_stage.p;
+  StreamStage* const hsg = (StreamStage*)S.h_tab.p;
+  StreamSave* const hsv = (StreamSave*)(hsg + n_items);
+  std::vector<BatchWork> work((size_t)n_items);
+  std::vector<HostChunk> ch;
+  for (int32_t i = 0; i < n_items; ++i) {
+    const StreamState& s = S.st[(size_t)items[i].stream];
+    StreamItem& it = plan[(size_t)i];
+    char* const slot = (char*)S.d_carry.p + (size_t)items[i].stream * 2 * S.slot_bytes;
+    fill_stream_copies(hsg[i], hsv[i], it, s.pos, items[i].n, sps, bps, d + off[(size_t)i], slot + (size_t)s.cur * S.slot_bytes,
+                       slot + (size_t)(s.cur ^ 1) * S.slot_bytes, device && items[i].n > 0 ? items[i].data : nullptr);
+    if (!device) ch.push_back(HostChunk{items[i].data, (size_t)items[i].n * (size_t)bps, (size_t)((char*)hsg[i].chunk.dst - d)});
+    it.plan.d_data = d + off[(size_t)i];
+    work[(size_t)i].plan = it.plan;
+    work[(size_t)i].thr = items[i].threshold;
+    work[(size_t)i].kind = !it.run ? BatchWork::kEmpty : it.n_buf > kBatchItemMax ? BatchWork::kHost : BatchWork::kKernel;
+  }
+  // the host entry point's chunks go straight into place: only the carries are copied on the device
+  if (!device && (r = upload_chunks(c, d, ch))) return r;
+  if ((r = apply_ext(c, st))) return r;
+  HIPCHK(c, hipMemcpyAsync(S.d_tab.p, S.h_tab.p, tab_bytes, hipMemcpyHostToDevice, st));
+  StreamStatus* const status = (StreamStatus*)S.h_status.p;
+  const StreamHooks hooks{(const StreamStage*)S.d_tab.p, (const StreamSave*)((const StreamStage*)S.d_tab.p + n_items), status};
+  BatchResult R;
+  if ((r = batch_core(c, fmt, work, &hooks, &R))) return r;
+  if (n_fallback) *n_fallback = R.nfb;
+  // what each item delivers and where its stream stands afterwards (adsb_plan.h: stream_deliver) -- nothing is committed yet
+  size_t room = (size_t)R.nb + 1;
+  for (const std::vector<adsb_burst>& f : R.fb) room += f.size();
+  std::vector<adsb_burst> keep(room);
+  std::vector<StreamState> next((size_t)n_items);
+  long long tot = 0;
+  for (int32_t i = 0; i < n_items; ++i) {
+    const bool fb = R.kept[i] < 0;
+    const std::vector<adsb_burst>* f = fb ? &R.fb[(size_t)R.fb_of[(size_t)i]] : nullptr;
+    const adsb_burst* src = fb ? f->data() : R.packed + R.first[i];
+    const int cnt = fb ? (int)f->size() : R.first[i + 1] - R.first[i];
+    const unsigned sum_flags = fb ? R.fb_flags[(size_t)R.fb_of[(size_t)i]] : status[i].flags;
+    if (!fb && status[i].kept != R.kept[i]) return fail(c, -EIO, "adsb_process_stream_batch: the save step returned nonsense");
+    StreamState n = S.st[(size_t)items[i].stream];
+    const int w = stream_deliver(src, cnt, keep.data() + tot, plan[(size_t)i].plan, sum_flags, sps,
+                                 [](const adsb_burst& b) { return (long long)b.offset; },
+                                 [](const adsb_burst& b) { return (unsigned)b.flags; }, &n.eob, &n.overlong);
+    item_first[i] = (int32_t)tot;
+    tot += w;
+    if (tot >= (1ll << 31)) return fail(c, -EINVAL, "adsb_process_stream_batch: more than 2^31 records");
+    n.cur ^= 1;
+    n.fmt = fmt;
+    if (items[i].flags & ADSB_STREAM_END) { n.pos = 0; n.eob = kStreamFreshEob; n.fmt = -1; }
+    else n.pos += items[i].n;
+    next[(size_t)i] = n;
+  }
+  item_first[n_items] = (int32_t)tot;
+  *n_out = (int32_t)tot;
+  if (tot > cap) return fail(c, -ENOSPC, "output array too small");
+  if (tot > 0) memcpy(out, keep.data(), (size_t)tot * sizeof(adsb_burst));
+  for (int32_t i = 0; i < n_items; ++i) S.st[(size_t)items[i].stream] = next[(size_t)i];
+  return 0;
 }
 
 }  // namespace
@@ -1774,6 +1976,7 @@ int adsb_reset(adsb_ctx* c) {
   }
   c->st = FramerState();
   c->n_ext = 0;           // a fresh stream starts without remembered producers
+  for (StreamState& s : c->sb.st) stream_make_fresh(s);
   return 0;
 }
 
@@ -1845,6 +2048,81 @@ int adsb_process_batch_device(adsb_ctx* c, int format, const adsb_batch_item* it
   int rc = check_batch(c, format, items, n_items, out, cap, item_first, n_out);
   if (rc) return rc;
   return run_batch(c, format, items, n_items, out, cap, item_first, n_out, n_fallback);
+}
+
+static_assert(sizeof(adsb_stream_item) == 32 && offsetof(adsb_stream_item, stream) == 16 && offsetof(adsb_stream_item, threshold) == 24,
+              "adsb_stream_item layout");
+static_assert(ADSB_BURST_DEMOD == kStreamRecDemod && ADSB_BURST_LONG_HINT == kStreamRecLongHint, "adsb_plan.h and the header agree on the record flags");
+
+int adsb_streams_open(adsb_ctx* c, int32_t n_streams) {
+  if (!c) return -EINVAL;
+  if (n_streams < 1) return fail(c, -EINVAL, "adsb_streams_open: n_streams < 1");
+  if (c->flags & (ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE | ADSB_FLAG_CONFIDENCE))
+    return fail(c, -EINVAL, "adsb_streams_open: not for ADSB_FLAG_AIRCRAFT_TABLE / _DECODE / _CONFIDENCE contexts (one receiver each)");
+  int rc = require_idle(c, kCallPending);
+  if (rc) return rc;
+  if (!c->sb.st.empty()) return fail(c, -EINVAL, "adsb_streams_open: streams are open (adsb_streams_close first)");
+  HIPCHK(c, hipSetDevice(c->device));
+  StreamBufs& S = c->sb;
+  S.slot_bytes = ((size_t)stream_carry_max(c->sps) * 8 + 255) & ~(size_t)255;
+  if ((rc = ensure(c, S.d_carry, (size_t)n_streams * 2 * S.slot_bytes))) return rc;
+  S.st.assign((size_t)n_streams, StreamState());
+  return 0;
+}
+
+int adsb_streams_close(adsb_ctx* c) {
+  if (!c) return -EINVAL;
+  int rc = require_idle(c, kCallPending);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  StreamBufs& S = c->sb;
+  S.st.clear();
+  S.slot_bytes = 0;
+  for (DevBuf* b : {&S.d_carry, &S.d_stage, &S.d_tab}) HIPCHK(c, b->release());
+  for (PinnedBuf* b : {&S.h_tab, &S.h_status}) HIPCHK(c, b->release());
+  return 0;
+}
+
+int adsb_stream_set_base(adsb_ctx* c, int32_t stream, int64_t abs_offset) {
+  if (!c) return -EINVAL;
+  if (stream < 0 || (size_t)stream >= c->sb.st.size()) return fail(c, -EINVAL, "adsb_stream_set_base: no such stream");
+  if (c->sb.st[(size_t)stream].pos != 0) return fail(c, -EINVAL, "adsb_stream_set_base: the stream is not fresh");
+  c->sb.st[(size_t)stream].base = abs_offset;
+  return 0;
+}
+
+int adsb_stream_state(adsb_ctx* c, int32_t stream, int64_t* pos, int64_t* eob, int64_t* n_overlong) {
+  if (!c) return -EINVAL;
+  if (stream < 0 || (size_t)stream >= c->sb.st.size()) return fail(c, -EINVAL, "adsb_stream_state: no such stream");
+  const StreamState& s = c->sb.st[(size_t)stream];
+  if (pos) *pos = s.pos;
+  if (eob) *eob = s.eob;
+  if (n_overlong) *n_overlong = s.overlong;
+  return 0;
+}
+
+int adsb_stream_reset(adsb_ctx* c, int32_t stream) {
+  if (!c) return -EINVAL;
+  if (stream < 0 || (size_t)stream >= c->sb.st.size()) return fail(c, -EINVAL, "adsb_stream_reset: no such stream");
+  stream_make_fresh(c->sb.st[(size_t)stream]);
+  return 0;
+}
+
+int adsb_process_stream_batch_device(adsb_ctx* c, int format, const adsb_stream_item* items, int32_t n_items, adsb_burst* out,
+                                     int32_t cap, int32_t* item_first, int32_t* n_out, int32_t* n_fallback) {
+  int rc = check_stream_batch(c, format, items, n_items, true, out, cap, item_first, n_out);
+  if (rc) return rc;
+  return run_stream_batch(c, format, items, n_items, true, out, cap, item_first, n_out, n_fallback);
+}
+
+int adsb_process_stream_batch(adsb_ctx* c, int format, const adsb_stream_item* items, int32_t n_items, adsb_burst* out, int32_t cap,
+                              int32_t* item_first, int32_t* n_out, int32_t* n_fallback) {
+  int rc = check_stream_batch(c, format, items, n_items, false, out, cap, item_first, n_out);
+  if (rc) return rc;
+  rc = run_stream_batch(c, format, items, n_items, false, out, cap, item_first, n_out, n_fallback);
+  // as adsb_process_batch: no upload that reads the CALLER's page-locked buffers is still queued when the call returns
+  if (rc != 0 && rc != -ENOSPC) (void)hipStreamSynchronize(c->stream);
+  return rc;
 }
 
 int adsb_process_batch(adsb_ctx* c, int format, const adsb_batch_item* items, int32_t n_items, adsb_burst* out, int32_t cap,

@@ -184,5 +184,83 @@ inline Plan plan_shard(int mode, const void* d, long long n, long long origin, l
   return p;
 }
 
+// ---- receiver streams carried across batch calls (adsb_process_stream_batch*) ------------------------------------------
+// A stream's calls are sequential in time, so one call is ONE overlapped time shard whose incoming end-of-burst state is
+// known before the launch: the gate starts from the carried value (no head, no fix-up).  With the back halo B and the
+// look-ahead F of adsb_shard_bounds, the call that appends samples [pos, pos + n) owns the rises of [pos - F, pos + n - F)
+// -- the first owning call from the stream's start -- and the END item owns up to the end of the stream, with the
+// end-of-call rules (framer.py:102-108, demod.py:82).  Offsets here are relative to the stream's first sample; `base` is
+// what the records' offsets add to them.
+constexpr long long kStreamUnbounded = 1ll << 60;        // STREAM_UNBOUNDED: plan_shard's stream_len of a stream that goes on
+constexpr long long kStreamFreshEob = -(1ll << 61);      // the end-of-burst offset of a fresh stream: gates nothing
+inline long long stream_back(int sps) { return 100 + 8ll * sps + 4; }          // B
+inline long long stream_ahead(int sps) { return 256 + 121ll * sps; }           // F
+inline long long stream_carry_max(int sps) { return stream_back(sps) + stream_ahead(sps) + 7; }
+// A call's buffer starts at stream sample stream_origin(pos): B + F samples in front of the new chunk, rounded down to a
+// multiple of 8 samples (16 bytes in every format), or at the stream's first sample.
+inline long long stream_origin(long long pos, int sps) {
+  const long long o = pos - stream_back(sps) - stream_ahead(sps);
+  return o <= 0 ? 0 : o - o % 8;
+}
+// The stream's last samples that are kept on the device once it has consumed `pos` samples: exactly those the next call's
+// buffer holds in front of its chunk -- all of a stream shorter than B + F, else B + F .. B + F + 7 of them.
+inline long long stream_carry_len(long long pos, int sps) { return pos - stream_origin(pos, sps); }
+struct StreamItem {
+  long long origin;        // stream sample at the item's local index 0: a multiple of 8, so of 16 bytes in every format
+  long long n_buf;         // the buffer holds stream samples [origin, pos + n): n_buf - n of them from the carry
+  bool run;                // false: the item owns nothing (and is no END item): no pass, no records
+  Plan plan;               // (d_data is the caller's to set when the buffer has its place)
+};
+inline StreamItem plan_stream_item(int mode, long long pos, long long n, bool end, long long base, long long eob, int sps) {
+  const long long F = stream_ahead(sps);
+  StreamItem it;
+  it.origin = stream_origin(pos, sps);
+  it.n_buf = pos + n - it.origin;
+  const long long own_lo = pos - F, own_hi = end ? pos + n : pos + n - F;
+  it.run = end ? it.n_buf > 0 : own_hi > 0;
+  it.plan = plan_shard(mode, nullptr, it.n_buf, it.origin, own_lo, own_hi, end ? pos + n : kStreamUnbounded, sps, 0);
+  it.plan.origin += base;
+  it.plan.gate = true;
+  it.plan.head_n = 0;
+  it.plan.prev_eob_stream = eob;
+  return it;
+}
+// The two copies of one stream item (SG = StreamStage, SV = StreamSave of adsb_device.h).  `carry_cur` holds the stream's last
+// stream_carry_len(pos) samples (the buffer's head), `carry_next` takes those of pos + n; `buf` is the item's place in the
+// staging buffer (16-byte aligned), `chunk` the caller's n new samples when the device has to copy them (else null: they
+// are in place already).
+template <class SG, class SV>
+inline void fill_stream_copies(SG& g, SV& v, const StreamItem& it, long long pos, long long n, int sps, int bps, char* buf,
+                               const char* carry_cur, char* carry_next, const void* chunk) {
+  const long long head = stream_carry_len(pos, sps), keep = stream_carry_len(pos + n, sps);
+  g.carry.src = carry_cur; g.carry.dst = buf; g.carry.bytes = head * bps;
+  g.chunk.src = chunk; g.chunk.dst = buf + head * bps; g.chunk.bytes = chunk ? n * bps : 0;
+  g.unit = bps; g.pad = 0;
+  v.carry.src = buf + (it.n_buf - keep) * bps; v.carry.dst = carry_next; v.carry.bytes = keep * bps;
+  v.unit = bps; v.pad = 0;
+}
+// What a stream item delivers and how its stream's state moves (ONE statement of both rules, for the library and the
+// emulator driver).  A record is left out when its burst ends at or beyond the end of the item's buffer -- its last bits
+// were sliced from samples that had not arrived: shard_post's rule (ADSB_SHARD_DROP_OVERLONG) -- and so is, by the kernel,
+// a pulse still high there (Summary.flags bit 2): both are counted in *overlong.  *eob moves to the end of the last
+// DELIVERED record's gate window (framer.py:165; 119 symbols behind a long-hinted record of a long-aware context).
+// off(r) / flags(r): a record's stream offset and its 16 flag bits.  Returns the number of records kept in dst (may be src).
+constexpr unsigned kStreamRecDemod = 1u, kStreamRecLongHint = 0x2000u;         // ADSB_BURST_DEMOD, ADSB_BURST_LONG_HINT
+template <class R, class Off, class Fl>
+inline int stream_deliver(const R* src, int n, R* dst, const Plan& pl, unsigned sum_flags, int sps, Off off, Fl flags,
+                          long long* eob, long long* overlong) {
+  const long long buf_end = pl.origin + pl.n;
+  int w = 0;
+  if (sum_flags & 4u) ++*overlong;
+  for (int i = 0; i < n; ++i) {
+    const long long o = off(src[i]);
+    const unsigned f = flags(src[i]);
+    if ((f & kStreamRecDemod) && o + 119ll * sps + sps / 2 >= buf_end) { ++*overlong; continue; }
+    *eob = o + ((f & kStreamRecLongHint) ? 119ll : 63ll) * sps;
+    dst[w++] = src[i];
+  }
+  return w;
+}
+
 }  // namespace adsb
 

@@ -149,6 +149,11 @@ class FrontEnd:
     def last_batch_fallbacks(self):
         return self.ctx.last_batch_fallbacks
 
+    # -- many receivers that go on: streams carried across batch calls -----------------------------------
+    def receivers(self, n, fmt=None):
+        """n receiver streams on this context (Receivers below).  fmt: one of _native.FMT_*, or None: by the arrays' dtype."""
+        return Receivers(self.ctx, n, fmt)
+
     def shard_tensor(self, t, origin, own_lo, own_hi, stream_len, fmt=0, head_cands=0):
         _after_torch(self.ctx, t)
         return self.ctx.shard_device(fmt, t.data_ptr(), t.shape[0], origin, own_lo, own_hi, stream_len, head_cands)
@@ -168,6 +173,62 @@ class FrontEnd:
     @staticmethod
     def bits(bursts):
         return _native.unpack_bits(bursts["bits"])[:, :112]
+
+
+_FMT_OF_DTYPE = {np.dtype(dt): fmt for fmt, (dt, _) in _native.FMT_LAYOUT.items()}
+
+
+class Receivers:
+    """A fleet of receivers on one context (FrontEnd.receivers): every push() runs the next chunk of any subset of the streams
+    through one device pass (adsb_process_stream_batch), seam-exact: a stream's records over all pushes and its finish() are
+    those of process_format over the concatenation of its chunks, delayed by the look-ahead of 256 + 121 * sps samples.
+    .overlong counts, over all streams, what the bounded carry made it leave out (pulses still high at the end of a call's
+    buffer).  One set of streams per context; close() releases it."""
+
+    def __init__(self, ctx, n, fmt=None):
+        self.ctx, self.n, self.fmt = ctx, int(n), fmt
+        ctx.open_streams(self.n)
+
+    def _run(self, arrays, ids, thresholds, end):
+        ids = list(range(len(arrays))) if ids is None else [int(i) for i in ids]
+        assert len(ids) == len(arrays)
+        if not ids:
+            return []
+        arrays = [np.asarray(a) for a in arrays]
+        fmt = self._last_fmt = self.fmt if self.fmt is not None else _FMT_OF_DTYPE[arrays[0].dtype]
+        recs, first = self.ctx.process_stream_batch(fmt, ids, arrays, thresholds, end)
+        return [recs[first[i]:first[i + 1]] for i in range(len(ids))]
+
+    def push(self, arrays, ids=None, thresholds=None):
+        """arrays[i]: the next samples of stream ids[i] (None: streams 0 .. len(arrays) - 1), any length -> a list of record
+        arrays, one per pushed stream"""
+        return self._run(arrays, ids, thresholds, False)
+
+    def finish(self, ids=None, thresholds=None):
+        """End streams `ids` (None: all): what they still owe, with the end-of-call rules -> a list of record arrays.  The
+        streams are fresh afterwards."""
+        ids = list(range(self.n)) if ids is None else list(ids)
+        live = [i for i in ids if self.ctx.stream_state(i)[0] > 0]
+        dt = _native.FMT_LAYOUT[self.fmt][0] if self.fmt is not None else None
+        out = {i: np.zeros(0, dtype=_native.BURST_DTYPE) for i in ids}
+        if live:
+            if dt is None:
+                dt = _native.FMT_LAYOUT[self._last_fmt][0]
+            thr = None if thresholds is None else [thresholds[ids.index(i)] for i in live]
+            for i, r in zip(live, self._run([np.zeros(0, dtype=dt)] * len(live), live, thr, True)):
+                out[i] = r
+        return [out[i] for i in ids]
+
+    def state(self, i):
+        """(pos, eob, n_overlong) of stream i"""
+        return self.ctx.stream_state(i)
+
+    @property
+    def overlong(self):
+        return sum(self.ctx.stream_state(i)[2] for i in range(self.n))
+
+    def close(self):
+        self.ctx.close_streams()
 
 
 class MultiDevice:

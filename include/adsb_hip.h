@@ -464,6 +464,50 @@ int adsb_process_batch_device(adsb_ctx* ctx, int format, const adsb_batch_item* 
  * where they lie, pageable ones through the staging ring), then run as above. */
 int adsb_process_batch(adsb_ctx* ctx, int format, const adsb_batch_item* items, int32_t n_items, adsb_burst* out, int32_t cap,
                        int32_t* item_first, int32_t* n_out, int32_t* n_fallback);
+/* RECEIVER STREAMS carried across batch calls.  adsb_process_batch* starts every item as a fresh stream; a receiver delivers a
+ * chunk every few tens of milliseconds, indefinitely.  A context holds n_streams streams (adsb_streams_open), each with the
+ * number of samples consumed (pos), a carried end-of-burst offset (eob), a base offset that its records' offsets add to the
+ * stream's sample index, and -- on the device, in the wire format -- a carry of its last 100 + 8*sps + 4 + 256 + 121*sps
+ * samples (up to 7 more: the next buffer starts on a multiple of 8 samples).  One call pushes the next chunk of ANY SUBSET of
+ * the streams through one k_batch launch: a small kernel in front of it assembles every item's buffer [stream carry | new chunk]
+ * (the host entry point uploads the chunks straight into place; the device entry point's chunks are copied by that kernel),
+ * one behind the pack step keeps each buffer's last samples for the next call.
+ * With F = 256 + 121*sps, the call that appends samples [pos, pos + n) owns the pulse rises of [pos - F, pos + n - F) (the
+ * first call owns from the stream's start): output is delayed by the look-ahead F, as in blocks.framer(improved=True).  An
+ * item flagged ADSB_STREAM_END owns up to the end of the stream and applies the end-of-call rules (framer.py:102-108,
+ * demod.py:82); after it the stream is fresh again (pos 0, nothing carried, the same base).
+ * CONTRACT: for a stream whose threshold is constant and in which no owned pulse is still high at the end of its call's
+ * buffer, the concatenation of its records over all calls, the END item included, is byte-identical to adsb_process_format
+ * over the concatenation of its chunks -- same records, order and flags, for ANY chunking (n == 0 included).  A threshold
+ * that changes between calls applies to the rises the call owns.
+ * DEVIATION: the carry is bounded.  A pulse that is still high at the end of its call's buffer, and a burst whose last bit
+ * lies at or beyond it, is left out (as ADSB_SHARD_DROP_OVERLONG does) and counted in the stream's n_overlong.
+ * Output as adsb_process_batch: out[item_first[i] .. item_first[i+1]) belong to item i.  -ENOSPC with *n_out = the number
+ * needed when cap is too small: NO stream has moved, the same call can be repeated with more room.  Items whose buffer exceeds
+ * ADSB_BATCH_ITEM_MAX samples or whose lists overflow run through the ordinary pass with the same plan and carried state
+ * (*n_fallback).  -EINVAL: a stream twice in one call, an unknown stream, a format other than the one the stream started with,
+ * n < 0, device data not aligned to a sample, reserved != 0, unknown flags, no open streams, ADSB_FLAG_AIRCRAFT_TABLE / _DECODE
+ * / _CONFIDENCE contexts; -EBUSY while tickets are pending.  ADSB_FLAG_LONG_AWARE_GATE and ADSB_FLAG_FEC_CONSERVATIVE apply as
+ * in the batch.  adsb_reset makes every stream fresh.  adsb_last_result and the framer state are left alone.  No reference
+ * counterpart. */
+#define ADSB_STREAM_END 1u /* adsb_stream_item.flags: the stream's last item */
+typedef struct adsb_stream_item {
+  const void* data;   /* the next n samples: host memory (adsb_process_stream_batch) or device-readable, aligned to a sample (.._device) */
+  int64_t n;          /* samples; 0 is legal, with and without ADSB_STREAM_END */
+  int32_t stream;     /* 0 .. n_streams - 1; at most once per call */
+  uint32_t flags;     /* ADSB_STREAM_END or 0 */
+  float threshold;    /* the framer threshold for the rises this call owns */
+  uint32_t reserved;  /* must be 0 */
+} adsb_stream_item;   /* 32 bytes */
+int adsb_streams_open(adsb_ctx* ctx, int32_t n_streams);  /* n fresh streams with base 0; -EINVAL while streams are open */
+int adsb_streams_close(adsb_ctx* ctx);                    /* releases the carry store and the call buffers */
+int adsb_stream_set_base(adsb_ctx* ctx, int32_t stream, int64_t abs_offset); /* fresh streams only */
+int adsb_stream_state(adsb_ctx* ctx, int32_t stream, int64_t* pos, int64_t* eob, int64_t* n_overlong); /* any pointer may be NULL */
+int adsb_stream_reset(adsb_ctx* ctx, int32_t stream);     /* fresh again: pos 0, nothing carried, n_overlong 0; the base stays */
+int adsb_process_stream_batch(adsb_ctx* ctx, int format, const adsb_stream_item* items, int32_t n_items, adsb_burst* out,
+                              int32_t cap, int32_t* item_first, int32_t* n_out, int32_t* n_fallback);
+int adsb_process_stream_batch_device(adsb_ctx* ctx, int format, const adsb_stream_item* items, int32_t n_items, adsb_burst* out,
+                                     int32_t cap, int32_t* item_first, int32_t* n_out, int32_t* n_fallback);
 /* Device memory on the context's device for callers that do not link HIP (a C or ctypes client of the *_device entry
  * points): hipMalloc / hipFree / a blocking hipMemcpy host -> device.  16-byte alignment is guaranteed.  No reference
  * counterpart (the reference never leaves host memory). */
