@@ -25,6 +25,7 @@ FLAG_LOW_LATENCY = 16     # the tail of a pass runs beside the next pass's k_det
 FLAG_FEC_CONSERVATIVE = 128  # opt-in: the decoder's "Conservative" 1-2-bit burst repair on the device (decoder.py:738-780)
 FLAG_AIRCRAFT_TABLE = 256    # opt-in: the decoder's aircraft table on the device: verdicts for address/parity replies
 FLAG_DECODE = 512            # opt-in (with FLAG_AIRCRAFT_TABLE): the decoder's message decoding and plane fields on the device
+FLAG_STREAM_DECODE = 1024    # opt-in: one decoder behind every receiver stream (open_streams), one device step per stream-batch call
 # include/adsb_hip.h adsb_decoded: one row per delivered record of a FLAG_DECODE context
 DECODED_DTYPE = np.dtype([("port", "u1"), ("df", "u1"), ("present", "u1"), ("pad0", "u1"), ("icao", "<i4"), ("bits", "u1", (14,)),
                           ("callsign", "S8"), ("pad1", "u1", (2,)), ("altitude", "<i4"), ("velocity_we", "<i4"),
@@ -75,6 +76,8 @@ EXPORTS = [
     "adsb_process_batch_device", "adsb_process_batch",
     "adsb_streams_open", "adsb_streams_close", "adsb_stream_set_base", "adsb_stream_state", "adsb_stream_reset",
     "adsb_process_stream_batch", "adsb_process_stream_batch_device",
+    "adsb_streams_set_decoder", "adsb_stream_set_start", "adsb_stream_last_decoded", "adsb_stream_decoder_reserve",
+    "adsb_stream_decoder_stats",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
 ]
 
@@ -173,6 +176,11 @@ def load():
     lib.adsb_stream_set_base.argtypes = [vp, i32, i64]
     lib.adsb_stream_state.argtypes = [vp, i32, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
     lib.adsb_stream_reset.argtypes = [vp, i32]
+    lib.adsb_streams_set_decoder.argtypes = [vp, i32]
+    lib.adsb_stream_set_start.argtypes = [vp, i32, c.c_double]
+    lib.adsb_stream_last_decoded.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
+    lib.adsb_stream_decoder_reserve.argtypes = [vp, i64]
+    lib.adsb_stream_decoder_stats.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
     lib.adsb_device_alloc.argtypes = [vp, c.POINTER(vp), c.c_size_t]
     lib.adsb_device_free.argtypes = [vp, vp]
     lib.adsb_device_upload.argtypes = [vp, vp, vp, c.c_size_t]
@@ -213,6 +221,7 @@ class Context:
         self._h = ctypes.c_void_p()
         self._thr = np.float32(threshold)
         self.last_batch_fallbacks = 0
+        self.flags = int(flags)
         rc = self.lib.adsb_create(float(fs), float(np.float32(threshold)), int(device), int(flags), ctypes.byref(self._h))
         if rc != 0:
             self._h = ctypes.c_void_p()
@@ -412,6 +421,36 @@ class Context:
 
     def reset_stream(self, stream):
         self._chk(self.lib.adsb_stream_reset(self._h, int(stream)))
+
+    # FLAG_STREAM_DECODE contexts: one decoder behind every stream (include/adsb_hip.h STREAM DECODERS)
+    def set_streams_decoder(self, msg_filter="All Messages"):
+        """The msg_filter of every stream's decoder (adsb_streams_set_decoder)."""
+        self._chk(self.lib.adsb_streams_set_decoder(self._h, DEC_MSG_FILTERS[msg_filter]))
+
+    def set_stream_start(self, stream, start_timestamp):
+        """The start timestamp of a fresh stream: a record's PDU timestamp is start + offset / fs (adsb_stream_set_start)."""
+        self._chk(self.lib.adsb_stream_set_start(self._h, int(stream), float(start_timestamp)))
+
+    def last_stream_decoded(self, copy=True):
+        """DECODED_DTYPE rows of the last delivered stream-batch call: row t belongs to its record t (adsb_stream_last_decoded)."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int32(0)
+        self._chk(self.lib.adsb_stream_last_decoded(self._h, ctypes.byref(p), ctypes.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=DECODED_DTYPE)
+        buf = (ctypes.c_char * (n.value * DECODED_DTYPE.itemsize)).from_address(p.value)
+        v = np.frombuffer(buf, dtype=DECODED_DTYPE)
+        return v.copy() if copy else v
+
+    def stream_decoder_reserve(self, slots):
+        """The capacity of the decoders' store, while it holds nothing (adsb_stream_decoder_reserve)."""
+        self._chk(self.lib.adsb_stream_decoder_reserve(self._h, int(slots)))
+
+    def stream_decoder_stats(self):
+        """(planes of all streams together, slots of the store, growths since open_streams)"""
+        p, c_, g = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._chk(self.lib.adsb_stream_decoder_stats(self._h, ctypes.byref(p), ctypes.byref(c_), ctypes.byref(g)))
+        return p.value, c_.value, g.value
 
     def _stream_batch(self, fn, fmt, ids, ptrs, ns, thresholds, end, cap=None):
         k = len(ids)

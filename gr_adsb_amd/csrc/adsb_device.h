@@ -56,6 +56,24 @@
 #define ADSB_AIR_STORE(p, v) ((void)(*(p) = (v)))
 #endif
 #endif
+// ADSB_FLEET_CAS(p, expected, desired): the claim of a slot of the per-stream decoders' store (ADSB_FLAG_STREAM_DECODE): a
+// 64-bit compare-and-swap at agent scope that returns the word it found.  The emulator's fibers switch only at barriers and
+// wave intrinsics, so a host build's read-compare-write is indivisible; tests/sim/fleet_driver.cpp defines its own.
+#ifndef ADSB_FLEET_CAS
+#if defined(__HIP__)
+__device__ __forceinline__ unsigned long long adsb_fleet_cas(unsigned long long* p, unsigned long long e, unsigned long long d) {
+  __hip_atomic_compare_exchange_strong(p, &e, d, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return e;
+}
+#else
+inline unsigned long long adsb_fleet_cas(unsigned long long* p, unsigned long long e, unsigned long long d) {
+  const unsigned long long o = *p;
+  if (o == e) *p = d;
+  return o;
+}
+#endif
+#define ADSB_FLEET_CAS(p, e, d) adsb_fleet_cas((p), (e), (d))
+#endif
 // ADSB_COLD_AT(e): the argument block *e of a device TABLE (const DetectArgs* e, not written during the launch) as the pointer
 // type adsb_cold() returns.  The product maps it to the constant address space behind an empty asm statement; a host build
 // (the SIMT emulator) reads the entry where it lies.
@@ -2704,6 +2722,59 @@ __global__ void __launch_bounds__(kThreads) k_dec_classify(DecArgs d) {
   }
 }
 
+// update_plane and the event of an accepted PDU (c.ev > kEvSnap) on its plane p, as the decoder's clock `ts` has it: a new
+// entry when p holds no plane (true then); port: what the PDU publishes (a position only once the fix is known)
+__device__ __forceinline__ bool dec_apply(Plane& p, const DecClass& c, double ts, unsigned epoch, unsigned& port) {
+  const bool fresh = !(p.present & kHasPlane);
+  if (fresh) {                                    // update_plane: a new entry (reset_plane_altimetry)
+    p.epoch = epoch; p.present = kHasPlane; p.num_msgs = 0; p.altitude = 0;
+    p.callsign = 0;
+    p.vwe = p.vsn = p.vr = 0;
+    p.lat = p.lon = __builtin_nan("");
+    p.cpr_lat0 = p.cpr_lat1 = p.cpr_lon0 = p.cpr_lon1 = 0; p.pad = 0;
+    p.cpr_t0 = p.cpr_t1 = 0;
+  }
+  p.num_msgs += 1;
+  if (c.ev == kEvAlt13) {
+    const int alt = dec_ac13(dec_field(c.a, c.b, 19, 13));
+    if (alt != -1) { p.altitude = alt; p.present |= kHasAltitude; }
+  } else if (c.ev == kEvIdent) {
+    static constexpr char lut[65] = "_ABCDEFGHIJKLMNOPQRSTUVWXYZ_____ _______________0123456789______";
+    unsigned long long cs = 0;
+    int q = 0;
+    for (int s = 0; s < 8; ++s) {
+      const char ch = lut[dec_field(c.a, c.b, 40 + 6 * s, 6)];
+      if (ch != '_') cs |= (unsigned long long)(unsigned char)ch << (8 * q++);
+    }
+    p.callsign = cs;
+    p.present |= kHasCallsign;
+  } else if (c.ev == kEvPos) {
+    const long long now = (long long)ts;
+    const int odd = (int)dec_field(c.a, c.b, 53, 1);
+    const int clat = (int)dec_field(c.a, c.b, 54, 17), clon = (int)dec_field(c.a, c.b, 71, 17);
+    if (odd) { p.cpr_lat1 = clat; p.cpr_lon1 = clon; p.cpr_t1 = now; p.present |= kHasOdd; }
+    else { p.cpr_lat0 = clat; p.cpr_lon0 = clon; p.cpr_t0 = now; p.present |= kHasEven; }
+    double lat = __builtin_nan(""), lon = lat;
+    if ((p.present & kHasEven) && (p.present & kHasOdd) && now - p.cpr_t0 < 30 && now - p.cpr_t1 < 30) {
+      double a_, b_;
+      if (dec_cpr(p, a_, b_)) { lat = a_; lon = b_; }
+    }
+    if ((lat - p.lat) < 0.1) port = kDecDecoded;                    // NaN on either side: not published
+    p.altitude = dec_ac12(dec_field(c.a, c.b, 40, 12));
+    p.present |= kHasAltitude;
+    if (lat == lat && lon == lon) { p.lat = lat; p.lon = lon; }
+  } else if (c.ev == kEvVel) {
+    int vwe = (int)dec_field(c.a, c.b, 46, 10) - 1, vsn = (int)dec_field(c.a, c.b, 57, 10) - 1;
+    int vr = ((int)dec_field(c.a, c.b, 69, 9) - 1) * 64;
+    if (dec_field(c.a, c.b, 45, 1)) vwe = -vwe;
+    if (dec_field(c.a, c.b, 56, 1)) vsn = -vsn;
+    if (dec_field(c.a, c.b, 68, 1)) vr = -vr;
+    p.vwe = vwe; p.vsn = vsn; p.vr = vr;
+    p.present |= kHasVelocity;
+  }
+  return fresh;
+}
+
 // Stage 3, one lane per address segment of the sorted keys: the plane's events in list order, a row after each
 __global__ void __launch_bounds__(kThreads) k_dec_fold(DecArgs d) {
   if (dec_skip(d)) return;
@@ -2726,52 +2797,7 @@ __global__ void __launch_bounds__(kThreads) k_dec_fold(DecArgs d) {
       unsigned port = c.port;
       if (c.ev > kEvSnap) {
         dirty = true;
-        if (!(p.present & kHasPlane)) {                                  // update_plane: a new entry (reset_plane_altimetry)
-          p.epoch = d.epoch; p.present = kHasPlane; p.num_msgs = 0; p.altitude = 0;
-          p.callsign = 0;
-          p.vwe = p.vsn = p.vr = 0;
-          p.lat = p.lon = __builtin_nan("");
-          p.cpr_lat0 = p.cpr_lat1 = p.cpr_lon0 = p.cpr_lon1 = 0; p.pad = 0;
-          p.cpr_t0 = p.cpr_t1 = 0;
-        }
-        p.num_msgs += 1;
-        if (c.ev == kEvAlt13) {
-          const int alt = dec_ac13(dec_field(c.a, c.b, 19, 13));
-          if (alt != -1) { p.altitude = alt; p.present |= kHasAltitude; }
-        } else if (c.ev == kEvIdent) {
-          static constexpr char lut[65] = "_ABCDEFGHIJKLMNOPQRSTUVWXYZ_____ _______________0123456789______";
-          unsigned long long cs = 0;
-          int q = 0;
-          for (int s = 0; s < 8; ++s) {
-            const char ch = lut[dec_field(c.a, c.b, 40 + 6 * s, 6)];
-            if (ch != '_') cs |= (unsigned long long)(unsigned char)ch << (8 * q++);
-          }
-          p.callsign = cs;
-          p.present |= kHasCallsign;
-        } else if (c.ev == kEvPos) {
-          const long long now = (long long)ts;
-          const int odd = (int)dec_field(c.a, c.b, 53, 1);
-          const int clat = (int)dec_field(c.a, c.b, 54, 17), clon = (int)dec_field(c.a, c.b, 71, 17);
-          if (odd) { p.cpr_lat1 = clat; p.cpr_lon1 = clon; p.cpr_t1 = now; p.present |= kHasOdd; }
-          else { p.cpr_lat0 = clat; p.cpr_lon0 = clon; p.cpr_t0 = now; p.present |= kHasEven; }
-          double lat = __builtin_nan(""), lon = lat;
-          if ((p.present & kHasEven) && (p.present & kHasOdd) && now - p.cpr_t0 < 30 && now - p.cpr_t1 < 30) {
-            double a_, b_;
-            if (dec_cpr(p, a_, b_)) { lat = a_; lon = b_; }
-          }
-          if ((lat - p.lat) < 0.1) port = kDecDecoded;                    // NaN on either side: not published
-          p.altitude = dec_ac12(dec_field(c.a, c.b, 40, 12));
-          p.present |= kHasAltitude;
-          if (lat == lat && lon == lon) { p.lat = lat; p.lon = lon; }
-        } else if (c.ev == kEvVel) {
-          int vwe = (int)dec_field(c.a, c.b, 46, 10) - 1, vsn = (int)dec_field(c.a, c.b, 57, 10) - 1;
-          int vr = ((int)dec_field(c.a, c.b, 69, 9) - 1) * 64;
-          if (dec_field(c.a, c.b, 45, 1)) vwe = -vwe;
-          if (dec_field(c.a, c.b, 56, 1)) vsn = -vsn;
-          if (dec_field(c.a, c.b, 68, 1)) vr = -vr;
-          p.vwe = vwe; p.vsn = vsn; p.vr = vr;
-          p.present |= kHasVelocity;
-        }
+        dec_apply(p, c, ts, d.epoch, port);
       }
       dec_row(&d.rows[t], c, port, (p.present & kHasPlane) ? &p : nullptr);
     }
@@ -2848,6 +2874,222 @@ __global__ void __launch_bounds__(kThreads) k_stream_save(const StreamSave* __re
     st.kept = kept[b];
     st.flags = s ? s->flags : 0u;
     status[b] = st;
+  }
+}
+
+
+// ---- opt-in per-stream decoders (ADSB_FLAG_STREAM_DECODE): one decoder behind every receiver stream ------------------------
+// The table step and the decode step above for the final record list of ONE adsb_process_stream_batch* call, every stream
+// with its own plane_dict (decoder.py:325-352 behind each receiver's demod, examples/adsb_rx.py).  The dense per-address
+// arrays of one decoder (2^24 keys, 2^24 planes) become ONE sparse store for the whole fleet: open addressing with linear
+// probing over a power-of-two number of slots, at most half of them taken, at most 2^27 (a sort key's bits 32..59 are the slot
+// index, and kDecNoKey's are all ones: it has to sort behind every slot).  A slot's key is
+//   generation (20 bits) << 44 | stream (20 bits) << 24 | address (24 bits)
+// claimed once with ADSB_FLEET_CAS and never released: a reset stream moves to its next generation, so its old slots match
+// no look-up any more and are dropped by the next k_fleet_rehash.  Beside the key a slot holds what table[AA] and
+// planes[AA] hold for one decoder: the ordering key (call << 32 | position in the call's list) of the address's first
+// announcement, kAirEmpty if none, and the Plane (present == 0: no plane).  104 bytes per slot.
+// Only an announcement takes a slot (k_fleet_announce, k_fleet_cond); every record that reaches update_plane has announced
+// its address by then (air_classify / dec_classify), so verdicts, the classify stage and the fold only look slots up.
+// An item's records are contiguous in the list and in stream order, so positions order a stream's records; streams share
+// nothing, so the conditional step runs one wavefront per item.
+constexpr unsigned long long kFleetEmpty = ~0ull;
+constexpr unsigned kFleetNone = ~0u;
+constexpr int kFleetAddrBits = 24, kFleetStreamBits = 20, kFleetGenBits = 20;
+constexpr unsigned kFleetGenMax = (1u << kFleetGenBits) - 2u;      // (the generation of all ones belongs to kFleetEmpty)
+struct FleetItem {
+  int first;                 // the item's records: [first, next item's first); entry n_items: first = n
+  int stream;
+  unsigned long long base;   // generation << 44 | stream << 24
+  double start;              // the stream's start timestamp: a record's PDU timestamp = start + (double)offset / fs
+};
+struct FleetCount { int slots, planes; };   // what an item's records claimed / created in this call
+struct FleetStore {
+  unsigned long long* keys;  // [cap], kFleetEmpty
+  unsigned long long* ann;   // [cap], kAirEmpty
+  Plane* planes;             // [cap], zero
+  unsigned mask;             // cap - 1
+};
+struct FleetArgs {
+  Rec* recs;                 // the call's final list: verdict flags are set in place
+  int n, n_items;
+  const FleetItem* items;    // [n_items + 1]
+  FleetCount* count;         // [n_items], zero before the step
+  int* ncond;                // [n_items + 1] candidates of the conditional step per item, their total last; zero before
+  int* error;                // set when the store's invariants do not hold (a full store, a plane without a slot)
+  FleetStore s;
+  unsigned long long call;   // ordering key of position 0 of this call
+  int fec, all;
+  double fs;
+  unsigned long long* keys;  // [n]: slot << 32 | position, kDecNoKey
+  const unsigned long long* sorted;
+  double* ts;                // [n]: the PDU timestamps of the records that have a key (k_fleet_classify)
+  DecRow* rows;              // [n]
+};
+
+__device__ __forceinline__ unsigned fleet_hash(unsigned long long k) {
+  k ^= k >> 33; k *= 0xFF51AFD7ED558CCDull; k ^= k >> 33; k *= 0xC4CEB9FE1A85EC53ull; k ^= k >> 33;
+  return (unsigned)k;
+}
+// the slot of `key`, or kFleetNone; claim: take the first empty slot of its probe sequence when it has none (*claimed)
+__device__ __forceinline__ unsigned fleet_slot(const FleetStore& s, unsigned long long key, bool claim, bool* claimed) {
+  unsigned h = fleet_hash(key) & s.mask;
+  for (unsigned probe = 0; probe <= s.mask; ++probe, h = (h + 1u) & s.mask) {
+    unsigned long long k = ADSB_AIR_LOAD(&s.keys[h]);
+    if (k == kFleetEmpty) {
+      if (!claim) return kFleetNone;
+      k = ADSB_FLEET_CAS(&s.keys[h], kFleetEmpty, key);
+      if (k == kFleetEmpty) { *claimed = true; return h; }
+    }
+    if (k == key) return h;
+  }
+  return kFleetNone;
+}
+// the item of record t: the last one whose first record is not behind t (empty items in front of it share its `first`)
+__device__ __forceinline__ int fleet_item_of(const FleetArgs& a, int t) {
+  int lo = 0, hi = a.n_items - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (a.items[mid].first <= t) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+__device__ __forceinline__ void fleet_set(const FleetArgs& a, int t, unsigned long long w3, unsigned fl) {
+  a.recs[t].w[3] = (w3 & 0xFFFFFFFFFFFFull) | ((unsigned long long)fl << 48);
+}
+// an announcement of `addr` by the record at position t of item `item`
+__device__ __forceinline__ void fleet_announce(const FleetArgs& a, int item, int addr, int t) {
+  bool claimed = false;
+  const unsigned h = fleet_slot(a.s, a.items[item].base | (unsigned)addr, true, &claimed);
+  if (h == kFleetNone) { ADSB_AIR_STORE(a.error, 1); return; }
+  if (claimed) atomicAdd(&a.count[item].slots, 1);
+  ADSB_AIR_MIN(&a.s.ann[h], a.call | (unsigned)t);
+}
+__device__ __forceinline__ bool fleet_known(const FleetArgs& a, int item, int addr, int t) {
+  bool claimed = false;
+  const unsigned h = fleet_slot(a.s, a.items[item].base | (unsigned)addr, false, &claimed);
+  return h != kFleetNone && ADSB_AIR_LOAD(&a.s.ann[h]) < (a.call | (unsigned)t);
+}
+
+// Step 1 (k_air_announce): every unconditional announcement of the call
+__global__ void __launch_bounds__(kThreads) k_fleet_announce(FleetArgs a) {
+  for (int t = (int)(blockIdx.x * kThreads + threadIdx.x); t < a.n; t += (int)(gridDim.x * kThreads)) {
+    int ap, ann, cann;
+    bool rep;
+    air_classify(a.recs[t].w[2], a.recs[t].w[3], a.fec != 0, ap, ann, rep, cann);
+    if (ann >= 0) fleet_announce(a, fleet_item_of(a, t), ann, t);
+  }
+}
+
+// Steps 2 and 4 (k_air_verdict): the verdict of every AP reply; again: only in items whose conditional step had work
+__global__ void __launch_bounds__(kThreads) k_fleet_verdict(FleetArgs a, int again) {
+  if (again && ADSB_AIR_LOAD(&a.ncond[a.n_items]) == 0) return;
+  for (int t = (int)(blockIdx.x * kThreads + threadIdx.x); t < a.n; t += (int)(gridDim.x * kThreads)) {
+    const unsigned long long w2 = a.recs[t].w[2], w3 = a.recs[t].w[3];
+    int ap, ann, cann;
+    bool rep;
+    air_classify(w2, w3, a.fec != 0, ap, ann, rep, cann);
+    if (ap < 0 || (again && rep)) continue;
+    const int item = fleet_item_of(a, t);
+    if (again && ADSB_AIR_LOAD(&a.ncond[item]) == 0) continue;
+    const unsigned fl = (unsigned)(w3 >> 48);
+    const bool known = fleet_known(a, item, ap, t);
+    unsigned nf = (fl & ~(kApKnown | kApFec)) | (known ? kApKnown : 0u);
+    if (!known && rep) {
+      nf |= kApFec;
+      atomicAdd(&a.ncond[item], 1);
+      atomicAdd(&a.ncond[a.n_items], 1);
+    }
+    if (nf != fl) fleet_set(a, t, w3, nf);
+  }
+}
+
+// Step 3 (k_air_cond), one wavefront per item: its candidates in list order
+__global__ void __launch_bounds__(64) k_fleet_cond(FleetArgs a) {
+  const int item = (int)blockIdx.x, lane = (int)threadIdx.x;
+  if (ADSB_AIR_LOAD(&a.ncond[item]) == 0) return;
+  const int lo = a.items[item].first, hi = a.items[item + 1].first;
+  for (int base = lo; base < hi; base += 64) {
+    const int t = base + lane;
+    bool cand = false;
+    if (t < hi) cand = ((unsigned)(a.recs[t].w[3] >> 48) & (kDemod | kApFec)) == (kDemod | kApFec);
+    unsigned long long m = __ballot(cand);
+    if (lane == 0)
+      while (m) {
+        const int u = base + __builtin_ctzll(m);
+        m &= m - 1;
+        const unsigned long long w2 = a.recs[u].w[2], w3 = a.recs[u].w[3];
+        int ap, ann, cann;
+        bool rep;
+        air_classify(w2, w3, a.fec != 0, ap, ann, rep, cann);
+        if (ap < 0 || !rep) continue;
+        if (fleet_known(a, item, ap, u)) fleet_set(a, u, w3, ((unsigned)(w3 >> 48) & ~kApFec) | kApKnown);
+        else if (cann >= 0) fleet_announce(a, item, cann, u);
+      }
+  }
+}
+
+// Stage 1 of the decode step (k_dec_classify): the sort key slot << 32 | position and the PDU's timestamp, or the row at once
+__global__ void __launch_bounds__(kThreads) k_fleet_classify(FleetArgs a) {
+  for (int t = (int)(blockIdx.x * kThreads + threadIdx.x); t < a.n; t += (int)(gridDim.x * kThreads)) {
+    const DecClass c = dec_classify(a.recs[t].w[2], a.recs[t].w[3], a.all != 0, a.fec != 0);
+    unsigned long long key = kDecNoKey;
+    if (c.fold && c.ev >= 0) {
+      bool claimed = false;
+      const FleetItem it = a.items[fleet_item_of(a, t)];
+      const unsigned h = fleet_slot(a.s, it.base | (unsigned)c.addr, false, &claimed);
+      if (h != kFleetNone) {
+        key = ((unsigned long long)h << 32) | (unsigned)t;
+        a.ts[t] = it.start + (double)(long long)a.recs[t].w[0] / a.fs;
+      } else if (c.ev > kEvSnap) ADSB_AIR_STORE(a.error, 1);     // (update_plane without an announcement: never)
+    }
+    if (key == kDecNoKey) dec_row(&a.rows[t], c, c.port, nullptr);   // rejected, filed under "", or an address without a slot
+    a.keys[t] = key;
+  }
+}
+
+// Stage 3 (k_dec_fold), one lane per slot segment of the sorted keys (one thread per key: the grid covers the list)
+__global__ void __launch_bounds__(kThreads) k_fleet_fold(FleetArgs a) {
+  const int i = (int)(blockIdx.x * kThreads + threadIdx.x);
+  if (i >= a.n) return;
+  const unsigned long long k0 = a.sorted[i];
+  if (k0 == kDecNoKey) return;
+  const unsigned h = (unsigned)(k0 >> 32);
+  if (i > 0 && (unsigned)(a.sorted[i - 1] >> 32) == h) return;
+  Plane p = a.s.planes[h];
+  bool dirty = false, fresh = false;
+  for (int j = i; j < a.n; ++j) {
+    const unsigned long long k = a.sorted[j];
+    if (k == kDecNoKey || (unsigned)(k >> 32) != h) break;
+    const int t = (int)(unsigned)k;
+    const DecClass c = dec_classify(a.recs[t].w[2], a.recs[t].w[3], a.all != 0, a.fec != 0);
+    unsigned port = c.port;
+    if (c.ev > kEvSnap) {
+      dirty = true;
+      fresh |= dec_apply(p, c, a.ts[t], 0u, port);
+    }
+    dec_row(&a.rows[t], c, port, (p.present & kHasPlane) ? &p : nullptr);
+  }
+  if (dirty) a.s.planes[h] = p;
+  if (fresh) atomicAdd(&a.count[fleet_item_of(a, (int)(unsigned)k0)].planes, 1);      // (a slot's records are one stream's)
+}
+
+// Growth, purge: the live slots of the old store (their stream still in the key's generation) into the new, empty one.
+// renumber: every announcement made so far gets ordering key 0 -- they all precede the calls to come, and only "earlier
+// than this record" is ever asked -- so that the host can start its call numbers over (at 1) before they run out.
+__global__ void __launch_bounds__(kThreads) k_fleet_rehash(FleetStore from, FleetStore to, const unsigned* gen, int n_streams, int renumber,
+                                                           int* error) {
+  for (unsigned i = blockIdx.x * kThreads + threadIdx.x; i <= from.mask; i += gridDim.x * kThreads) {
+    const unsigned long long key = from.keys[i];
+    if (key == kFleetEmpty) continue;
+    const unsigned stream = (unsigned)(key >> kFleetAddrBits) & ((1u << kFleetStreamBits) - 1u);
+    if (stream >= (unsigned)n_streams || gen[stream] != (unsigned)(key >> (kFleetAddrBits + kFleetStreamBits))) continue;
+    bool claimed = false;
+    const unsigned h = fleet_slot(to, key, true, &claimed);
+    if (h == kFleetNone || !claimed) { ADSB_AIR_STORE(error, 1); continue; }
+    const unsigned long long ann = from.ann[i];
+    to.ann[h] = (renumber && ann != kAirEmpty) ? 0ull : ann;
+    to.planes[h] = from.planes[i];
   }
 }
 

@@ -292,6 +292,26 @@ struct StreamBufs {
   PinnedBuf h_status;            // device-visible: StreamStatus[n_items] (k_stream_save)
 };
 
+// ADSB_FLAG_STREAM_DECODE: the decoders of the context's streams (adsb_device.h: the k_fleet_* kernels).  Host state per
+// stream (start timestamp, generation, the slots and planes it holds), the store, and the buffers of one call's decode step.
+struct FleetDec {
+  bool open = false;
+  int all = 1;                                  // msg_filter "All Messages"
+  std::vector<double> start;
+  std::vector<unsigned> gen;
+  std::vector<long long> slots, planes;         // live, per stream
+  long long cap = 0;                            // slots of the store
+  long long used = 0;                           // slots taken since the store was built (those of reset streams included)
+  long long live_slots = 0, live_planes = 0, grows = 0;
+  unsigned long long call = 0;                  // number of the next delivered call with records (ordering keys: number << 32 | position)
+  DevBuf d_store;                               // keys[cap] | ann[cap] | planes[cap]
+  DevBuf d_recs, d_items, d_cnt, d_keys, d_sorted, d_tmp, d_ts, d_rows, d_gen;
+  PinnedBuf h_recs, h_rows, h_items, h_cnt;
+  int32_t n_rows = 0;                           // rows of the last delivered call
+};
+constexpr long long kFleetMinCap = 256, kFleetDefaultCap = 1ll << 16, kFleetMaxCap = 1ll << 27;    // (slot index 2^28 - 1 would sort with kDecNoKey)
+constexpr size_t kFleetSlotBytes = 16 + sizeof(Plane);
+
 }  // namespace
 
 // Host threads that copy a pageable source into the pinned staging ring of a host-fed submission: one host core moves
@@ -449,6 +469,7 @@ struct adsb_ctx {
   PinnedBuf h_pdu;                    // adsb_decode_pdus' staging (device-visible)
   BatchBufs bt;                       // adsb_process_batch*
   StreamBufs sb;                      // adsb_process_stream_batch*
+  FleetDec fd;                        // ... and their decoders (ADSB_FLAG_STREAM_DECODE)
   char err[256] = {0};
   __attribute__((visibility("hidden"))) ~adsb_ctx() = default;   // (the library's exported names stay its C entry points)
 };
@@ -1550,6 +1571,171 @@ int upload_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_i
   return upload_chunks(c, d, ch);
 }
 
+// ---- ADSB_FLAG_STREAM_DECODE: one decoder per receiver stream, one sparse store for all of them (adsb_device.h) ---------------
+FleetStore fleet_view(void* p, long long cap) {
+  FleetStore v;
+  v.keys = (unsigned long long*)p;
+  v.ann = v.keys + cap;
+  v.planes = (Plane*)(v.ann + cap);
+  v.mask = (unsigned)(cap - 1);
+  return v;
+}
+// an empty store of cap slots (a power of two), ready behind what is queued on the context's stream
+int fleet_new_store(adsb_ctx* c, DevBuf& b, long long cap) {
+  const size_t bytes = (size_t)cap * kFleetSlotBytes;
+  if (hipMalloc(&b.p, bytes) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return fail(c, -ENOMEM, "stream decoders: no device memory for the store"); }
+  b.cap = bytes;
+  HIPCHK(c, hipMemsetAsync(b.p, 0xFF, (size_t)cap * 16, c->stream));
+  HIPCHK(c, hipMemsetAsync((char*)b.p + (size_t)cap * 16, 0, (size_t)cap * sizeof(Plane), c->stream));
+  return 0;
+}
+int fleet_take_store(adsb_ctx* c, DevBuf& fresh, long long cap) {
+  FleetDec& F = c->fd;
+  HIPCHK(c, F.d_store.release());
+  F.d_store.p = fresh.p; F.d_store.cap = fresh.cap;
+  fresh.p = nullptr; fresh.cap = 0;
+  F.cap = cap;
+  return 0;
+}
+// The live slots into a store of new_cap slots (growth, or the purge of a stream whose generations are used up): blocking.
+int fleet_rehash(adsb_ctx* c, long long new_cap, bool renumber = false) {
+  FleetDec& F = c->fd;
+  const hipStream_t st = c->stream;
+  const size_t ns = F.gen.size();
+  int r;
+  DevBuf fresh;
+  if ((r = ensure(c, F.d_gen, ns * sizeof(unsigned) + sizeof(int)))) return r;
+  if ((r = fleet_new_store(c, fresh, new_cap))) return r;
+  int* const d_err = (int*)((unsigned*)F.d_gen.p + ns);
+  HIPCHK(c, hipMemcpyAsync(F.d_gen.p, F.gen.data(), ns * sizeof(unsigned), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(d_err, 0, sizeof(int), st));
+  hipLaunchKernelGGL(k_fleet_rehash, dim3(step_grid(F.cap, kThreads)), dim3(kThreads), 0, st, fleet_view(F.d_store.p, F.cap),
+                     fleet_view(fresh.p, new_cap), (const unsigned*)F.d_gen.p, (int)ns, renumber ? 1 : 0, d_err);
+  HIPCHK(c, hipGetLastError());
+  int err = 0;
+  HIPCHK(c, hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (err) return fail(c, -EIO, "stream decoders: the rehash step found the store inconsistent");
+  if ((r = fleet_take_store(c, fresh, new_cap))) return r;
+  F.used = F.live_slots;
+  if (renumber) F.call = 1;
+  return 0;
+}
+// a fresh decoder for stream s: its slots stay behind under the old generation until the next rehash
+int fleet_reset_stream(adsb_ctx* c, size_t s) {
+  FleetDec& F = c->fd;
+  F.live_slots -= F.slots[s]; F.live_planes -= F.planes[s];
+  F.slots[s] = F.planes[s] = 0;
+  if (F.gen[s] < kFleetGenMax) { ++F.gen[s]; return 0; }
+  F.gen[s] = ~0u;                               // (no key holds it: the rehash drops every slot of the stream)
+  HIPCHK(c, hipSetDevice(c->device));
+  const int r = fleet_rehash(c, F.cap);
+  F.gen[s] = 0;
+  return r;
+}
+int fleet_open(adsb_ctx* c, size_t n) {
+  FleetDec& F = c->fd;
+  DevBuf fresh;
+  int r;
+  if ((r = fleet_new_store(c, fresh, kFleetDefaultCap)) || (r = fleet_take_store(c, fresh, kFleetDefaultCap))) return r;
+  F.start.assign(n, 0.0); F.gen.assign(n, 0u); F.slots.assign(n, 0); F.planes.assign(n, 0);
+  F.used = F.live_slots = F.live_planes = F.grows = 0;
+  F.call = 0; F.n_rows = 0; F.all = 1;
+  F.open = true;
+  return 0;
+}
+int fleet_close(adsb_ctx* c) {
+  FleetDec& F = c->fd;
+  F.open = false; F.cap = 0; F.n_rows = 0;
+  F.start.clear(); F.gen.clear(); F.slots.clear(); F.planes.clear();
+  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen}) HIPCHK(c, b->release());
+  for (PinnedBuf* b : {&F.h_recs, &F.h_rows, &F.h_items, &F.h_cnt}) HIPCHK(c, b->release());
+  return 0;
+}
+
+// The decode step of one delivered call: recs[0 .. n) is its final list (item i: [item_first[i], item_first[i + 1])).  The
+// records come back in F.h_recs with their verdict flags, the rows in F.h_rows.  Everything that can fail for want of
+// memory happens before the first kernel that touches the store.
+int fleet_step(adsb_ctx* c, const adsb_stream_item* items, int32_t n_items, const int32_t* item_first, const adsb_burst* recs, int32_t n) {
+  FleetDec& F = c->fd;
+  const hipStream_t st = c->stream;
+  if (n == 0) { F.n_rows = 0; return 0; }
+  int r;
+  const size_t nn = (size_t)n, ni = (size_t)n_items;
+  const int nblk = (int)((nn + kSortTile - 1) / kSortTile);
+  const size_t cnt_bytes = ni * sizeof(FleetCount) + (ni + 2) * sizeof(int);
+  if ((r = ensure(c, F.d_recs, nn * sizeof(Rec))) || (r = ensure(c, F.d_items, (ni + 1) * sizeof(FleetItem))) ||
+      (r = ensure(c, F.d_cnt, cnt_bytes)) || (r = ensure(c, F.d_keys, nn * 8)) || (r = ensure(c, F.d_sorted, nn * 8)) ||
+      (r = ensure(c, F.d_tmp, (size_t)nblk * 16 * sizeof(unsigned))) || (r = ensure(c, F.d_ts, nn * 8)) || (r = ensure(c, F.d_rows, nn * sizeof(DecRow))) ||
+      (r = ensure_pinned(c, F.h_recs, nn * sizeof(Rec))) || (r = ensure_pinned(c, F.h_rows, nn * sizeof(DecRow))) ||
+      (r = ensure_pinned(c, F.h_items, (ni + 1) * sizeof(FleetItem))) || (r = ensure_pinned(c, F.h_cnt, cnt_bytes)))
+    return r;
+  // Room for one slot per record with at most half the store taken, or a rehash first: it drops the slots reset streams left
+  // behind, into a store that is larger only if the LIVE slots need it (a growth).  The call numbers of the ordering keys
+  // start over at such a rehash before they run out.
+  const bool renumber = F.call >= 0xFFFFFFFEull;
+  if ((F.used + n) * 2 > F.cap || renumber) {
+    const long long old_cap = F.cap;
+    long long cap = old_cap;
+    while ((F.live_slots + n) * 2 > cap) cap *= 2;
+    if (cap > kFleetMaxCap) return fail(c, -ENOMEM, "stream decoders: the store would exceed 2^27 slots");
+    if ((r = fleet_rehash(c, cap, renumber))) return r;
+    if (cap > old_cap) F.grows++;
+  }
+  FleetItem* const hi = (FleetItem*)F.h_items.p;
+  for (int32_t i = 0; i < n_items; ++i) {
+    const size_t s = (size_t)items[i].stream;
+    hi[i].first = item_first[i];
+    hi[i].stream = items[i].stream;
+    hi[i].base = ((unsigned long long)F.gen[s] << (kFleetAddrBits + kFleetStreamBits)) | ((unsigned long long)s << kFleetAddrBits);
+    hi[i].start = F.start[s];
+  }
+  hi[n_items].first = n; hi[n_items].stream = -1; hi[n_items].base = 0; hi[n_items].start = 0;
+  memcpy(F.h_recs.p, recs, nn * sizeof(Rec));
+  HIPCHK(c, hipMemcpyAsync(F.d_recs.p, F.h_recs.p, nn * sizeof(Rec), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(F.d_items.p, hi, (ni + 1) * sizeof(FleetItem), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(F.d_cnt.p, 0, cnt_bytes, st));
+  FleetArgs a{};
+  a.recs = (Rec*)F.d_recs.p; a.n = n; a.n_items = n_items; a.items = (const FleetItem*)F.d_items.p;
+  a.count = (FleetCount*)F.d_cnt.p; a.ncond = (int*)(a.count + ni); a.error = a.ncond + ni + 1;
+  a.s = fleet_view(F.d_store.p, F.cap);
+  a.call = F.call << 32;
+  a.fec = (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) ? 1 : 0; a.all = F.all; a.fs = c->fs;
+  a.keys = (unsigned long long*)F.d_keys.p; a.sorted = (const unsigned long long*)F.d_sorted.p; a.rows = (DecRow*)F.d_rows.p;
+  a.ts = (double*)F.d_ts.p;
+  const unsigned g = step_grid(n, kThreads);
+  hipLaunchKernelGGL(k_fleet_announce, dim3(g), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(k_fleet_verdict, dim3(g), dim3(kThreads), 0, st, a, 0);
+  hipLaunchKernelGGL(k_fleet_cond, dim3((unsigned)n_items), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(k_fleet_verdict, dim3(g), dim3(kThreads), 0, st, a, 1);
+  hipLaunchKernelGGL(k_fleet_classify, dim3(g), dim3(kThreads), 0, st, a);
+  unsigned long long* in = (unsigned long long*)F.d_keys.p;
+  unsigned long long* out = (unsigned long long*)F.d_sorted.p;
+  for (int shift = 32; shift < 60; shift += 4) {          // as launch_dec: seven passes, the result ends in d_sorted
+    hipLaunchKernelGGL(k_dec_sort_hist, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, (int)n, shift, (unsigned*)F.d_tmp.p);
+    hipLaunchKernelGGL(k_dec_sort_scan, dim3(1), dim3(kThreads), 0, st, (unsigned*)F.d_tmp.p, nblk * 16);
+    hipLaunchKernelGGL(k_dec_sort_scatter, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, out, (int)n, shift,
+                       (const unsigned*)F.d_tmp.p);
+    unsigned long long* x = in; in = out; out = x;
+  }
+  hipLaunchKernelGGL(k_fleet_fold, dim3((unsigned)((nn + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, a);     // one thread per key
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(F.h_recs.p, F.d_recs.p, nn * sizeof(Rec), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(F.h_rows.p, F.d_rows.p, nn * sizeof(DecRow), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(F.h_cnt.p, F.d_cnt.p, cnt_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const FleetCount* const hc = (const FleetCount*)F.h_cnt.p;
+  if (((const int*)(hc + ni))[ni + 1] != 0) return fail(c, -EIO, "stream decoders: the decode step found the store inconsistent");
+  for (int32_t i = 0; i < n_items; ++i) {
+    const size_t s = (size_t)items[i].stream;
+    F.slots[s] += hc[i].slots; F.planes[s] += hc[i].planes;
+    F.live_slots += hc[i].slots; F.live_planes += hc[i].planes; F.used += hc[i].slots;
+  }
+  F.call++;
+  F.n_rows = n;
+  return 0;
+}
+
 // ---- adsb_process_stream_batch*: receiver streams carried across batch calls -------------------------------------------------
 // One call pushes the next chunk of any subset of the context's streams through ONE k_batch launch: item i is one overlapped
 // time shard of its stream (adsb_plan.h: plan_stream_item) whose gate starts from the stream's carried end-of-burst offset.
@@ -1589,7 +1775,7 @@ int run_stream_batch(adsb_ctx* c, int fmt, const adsb_stream_item* items, int32_
   *n_out = 0;
   item_first[0] = 0;
   if (n_fallback) *n_fallback = 0;
-  if (n_items == 0) return 0;
+  if (n_items == 0) { c->fd.n_rows = 0; return 0; }
   HIPCHK(c, hipSetDevice(c->device));
   StreamBufs& S = c->sb;
   const hipStream_t st = c->stream;
@@ -1665,7 +1851,12 @@ int run_stream_batch(adsb_ctx* c, int fmt, const adsb_stream_item* items, int32_
   item_first[n_items] = (int32_t)tot;
   *n_out = (int32_t)tot;
   if (tot > cap) return fail(c, -ENOSPC, "output array too small");
-  if (tot > 0) memcpy(out, keep.data(), (size_t)tot * sizeof(adsb_burst));
+  const adsb_burst* fin = keep.data();
+  if (c->flags & ADSB_FLAG_STREAM_DECODE) {      // the call is delivered: every stream's decoder takes its records
+    if ((r = fleet_step(c, items, n_items, item_first, keep.data(), (int32_t)tot))) return r;
+    fin = (const adsb_burst*)c->fd.h_recs.p;
+  }
+  if (tot > 0) memcpy(out, fin, (size_t)tot * sizeof(adsb_burst));
   for (int32_t i = 0; i < n_items; ++i) S.st[(size_t)items[i].stream] = next[(size_t)i];
   return 0;
 }
@@ -1814,6 +2005,7 @@ float adsb_snr_db(float peak, float median) {
 
 int adsb_create(double fs, float threshold, int device, uint32_t flags, adsb_ctx** out) {
   if ((flags & ADSB_FLAG_DECODE) && !(flags & ADSB_FLAG_AIRCRAFT_TABLE)) return -EINVAL;   // the decode step follows the table's
+  if ((flags & ADSB_FLAG_STREAM_DECODE) && (flags & (ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE | ADSB_FLAG_CONFIDENCE))) return -EINVAL;
   if (!out) return -EINVAL;
   *out = nullptr;
   if (!(fs > 0) || fmod(fs, 1e6) != 0.0) return -EINVAL;        // framer.py:44, demod.py:42
@@ -1977,6 +2169,10 @@ int adsb_reset(adsb_ctx* c) {
   c->st = FramerState();
   c->n_ext = 0;           // a fresh stream starts without remembered producers
   for (StreamState& s : c->sb.st) stream_make_fresh(s);
+  if (c->fd.open) {
+    for (size_t s = 0; s < c->fd.gen.size(); ++s) { const int r = fleet_reset_stream(c, s); if (r) return r; }
+    c->fd.call = 0;          // (no slot of an earlier generation is looked up again)
+  }
   return 0;
 }
 
@@ -2065,7 +2261,10 @@ int adsb_streams_open(adsb_ctx* c, int32_t n_streams) {
   HIPCHK(c, hipSetDevice(c->device));
   StreamBufs& S = c->sb;
   S.slot_bytes = ((size_t)stream_carry_max(c->sps) * 8 + 255) & ~(size_t)255;
+  if ((c->flags & ADSB_FLAG_STREAM_DECODE) && n_streams > (1 << kFleetStreamBits))
+    return fail(c, -EINVAL, "adsb_streams_open: at most 2^20 streams with ADSB_FLAG_STREAM_DECODE");
   if ((rc = ensure(c, S.d_carry, (size_t)n_streams * 2 * S.slot_bytes))) return rc;
+  if ((c->flags & ADSB_FLAG_STREAM_DECODE) && (rc = fleet_open(c, (size_t)n_streams))) return rc;
   S.st.assign((size_t)n_streams, StreamState());
   return 0;
 }
@@ -2080,6 +2279,10 @@ int adsb_streams_close(adsb_ctx* c) {
   S.slot_bytes = 0;
   for (DevBuf* b : {&S.d_carry, &S.d_stage, &S.d_tab}) HIPCHK(c, b->release());
   for (PinnedBuf* b : {&S.h_tab, &S.h_status}) HIPCHK(c, b->release());
+  if (c->fd.open) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return fleet_close(c);
+  }
   return 0;
 }
 
@@ -2105,6 +2308,62 @@ int adsb_stream_reset(adsb_ctx* c, int32_t stream) {
   if (!c) return -EINVAL;
   if (stream < 0 || (size_t)stream >= c->sb.st.size()) return fail(c, -EINVAL, "adsb_stream_reset: no such stream");
   stream_make_fresh(c->sb.st[(size_t)stream]);
+  if (c->fd.open) return fleet_reset_stream(c, (size_t)stream);
+  return 0;
+}
+
+int adsb_streams_set_decoder(adsb_ctx* c, int32_t msg_filter) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE");
+  if (!c->fd.open) return fail(c, -EINVAL, "adsb_streams_set_decoder: no streams (adsb_streams_open first)");
+  if (msg_filter != ADSB_DEC_ALL_MESSAGES && msg_filter != ADSB_DEC_EXTENDED_SQUITTER_ONLY) return fail(c, -EINVAL, "msg_filter");
+  c->fd.all = msg_filter == ADSB_DEC_ALL_MESSAGES;
+  return 0;
+}
+
+int adsb_stream_set_start(adsb_ctx* c, int32_t stream, double start_timestamp) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE");
+  if (stream < 0 || (size_t)stream >= c->fd.start.size()) return fail(c, -EINVAL, "adsb_stream_set_start: no such stream");
+  if (c->sb.st[(size_t)stream].pos != 0) return fail(c, -EINVAL, "adsb_stream_set_start: the stream is not fresh");
+  c->fd.start[(size_t)stream] = start_timestamp;
+  return 0;
+}
+
+int adsb_stream_last_decoded(adsb_ctx* c, const adsb_decoded** rows, int32_t* n) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE");
+  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_last_decoded: no streams (adsb_streams_open first)");
+  if (rows) *rows = c->fd.n_rows > 0 ? (const adsb_decoded*)c->fd.h_rows.p : nullptr;
+  if (n) *n = c->fd.n_rows;
+  return 0;
+}
+
+int adsb_stream_decoder_reserve(adsb_ctx* c, int64_t slots) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE");
+  FleetDec& F = c->fd;
+  if (!F.open) return fail(c, -EINVAL, "adsb_stream_decoder_reserve: no streams (adsb_streams_open first)");
+  if (F.live_slots != 0) return fail(c, -EINVAL, "adsb_stream_decoder_reserve: the store holds live planes");
+  if (slots < 0 || slots > kFleetMaxCap) return fail(c, -EINVAL, "adsb_stream_decoder_reserve: 0 .. 2^27 slots");
+  long long cap = kFleetMinCap;
+  while (cap < slots) cap *= 2;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  DevBuf fresh;
+  int r;
+  if ((r = fleet_new_store(c, fresh, cap)) || (r = fleet_take_store(c, fresh, cap))) return r;
+  F.used = 0;
+  return 0;
+}
+
+int adsb_stream_decoder_stats(adsb_ctx* c, int64_t* planes, int64_t* capacity, int64_t* grows) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE");
+  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_decoder_stats: no streams (adsb_streams_open first)");
+  if (planes) *planes = c->fd.live_planes;
+  if (capacity) *capacity = c->fd.cap;
+  if (grows) *grows = c->fd.grows;
   return 0;
 }
 

@@ -150,9 +150,10 @@ class FrontEnd:
         return self.ctx.last_batch_fallbacks
 
     # -- many receivers that go on: streams carried across batch calls -----------------------------------
-    def receivers(self, n, fmt=None):
-        """n receiver streams on this context (Receivers below).  fmt: one of _native.FMT_*, or None: by the arrays' dtype."""
-        return Receivers(self.ctx, n, fmt)
+    def receivers(self, n, fmt=None, starts=None, msg_filter=None):
+        """n receiver streams on this context (Receivers below).  fmt: one of _native.FMT_*, or None: by the arrays' dtype.
+        starts / msg_filter: FLAG_STREAM_DECODE contexts, the streams' start timestamps and their decoders' msg_filter."""
+        return Receivers(self.ctx, n, fmt, starts, msg_filter)
 
     def shard_tensor(self, t, origin, own_lo, own_hi, stream_len, fmt=0, head_cands=0):
         _after_torch(self.ctx, t)
@@ -183,20 +184,37 @@ class Receivers:
     through one device pass (adsb_process_stream_batch), seam-exact: a stream's records over all pushes and its finish() are
     those of process_format over the concatenation of its chunks, delayed by the look-ahead of 256 + 121 * sps samples.
     .overlong counts, over all streams, what the bounded carry made it leave out (pulses still high at the end of a call's
-    buffer).  One set of streams per context; close() releases it."""
+    buffer).  One set of streams per context; close() releases it.
+    On a FLAG_STREAM_DECODE context every stream has a decoder of its own: after push() / finish(), .rows holds the list of
+    DECODED_DTYPE row arrays that matches the returned record arrays (row t of a stream belongs to its record t;
+    _native.decoded_pdu turns a row into the reference's published PDU).  starts: the streams' start timestamps (a record's
+    PDU timestamp is start + offset / fs), msg_filter: "All Messages" (default) or "Extended Squitter Only"."""
 
-    def __init__(self, ctx, n, fmt=None):
+    def __init__(self, ctx, n, fmt=None, starts=None, msg_filter=None):
         self.ctx, self.n, self.fmt = ctx, int(n), fmt
+        self.decode = bool(getattr(ctx, "flags", 0) & _native.FLAG_STREAM_DECODE)
+        self.rows = []
+        if not self.decode and (starts is not None or msg_filter is not None):      # (before any stream is opened)
+            raise ValueError("starts / msg_filter need a FLAG_STREAM_DECODE context")
         ctx.open_streams(self.n)
+        if self.decode:
+            if msg_filter is not None:
+                ctx.set_streams_decoder(msg_filter)
+            for i, t in enumerate(starts if starts is not None else []):
+                ctx.set_stream_start(i, t)
 
     def _run(self, arrays, ids, thresholds, end):
         ids = list(range(len(arrays))) if ids is None else [int(i) for i in ids]
         assert len(ids) == len(arrays)
         if not ids:
+            self.rows = []
             return []
         arrays = [np.asarray(a) for a in arrays]
         fmt = self._last_fmt = self.fmt if self.fmt is not None else _FMT_OF_DTYPE[arrays[0].dtype]
         recs, first = self.ctx.process_stream_batch(fmt, ids, arrays, thresholds, end)
+        if self.decode:
+            rows = self.ctx.last_stream_decoded()
+            self.rows = [rows[first[i]:first[i + 1]] for i in range(len(ids))]
         return [recs[first[i]:first[i + 1]] for i in range(len(ids))]
 
     def push(self, arrays, ids=None, thresholds=None):
@@ -217,6 +235,9 @@ class Receivers:
             thr = None if thresholds is None else [thresholds[ids.index(i)] for i in live]
             for i, r in zip(live, self._run([np.zeros(0, dtype=dt)] * len(live), live, thr, True)):
                 out[i] = r
+        if self.decode:
+            rows = dict(zip(live, self.rows)) if live else {}
+            self.rows = [rows.get(i, np.zeros(0, dtype=_native.DECODED_DTYPE)) for i in ids]
         return [out[i] for i in ids]
 
     def state(self, i):

@@ -123,6 +123,14 @@ extern "C" {
  * adsb_framer_work, adsb_demod_work and the sharded entry points return -EINVAL.  Without the flag nothing is allocated or
  * launched. */
 #define ADSB_FLAG_DECODE 512u
+/* Opt-in, for receiver streams (adsb_streams_open): ONE DECODER BEHIND EVERY STREAM, the reference's topology of one decoder
+ * block behind each receiver's demod (examples/adsb_rx.py, decoder.py:325-352), for the whole fleet in one device step per
+ * adsb_process_stream_batch* call -- see STREAM DECODERS below.  -EINVAL together with ADSB_FLAG_AIRCRAFT_TABLE, _DECODE or
+ * _CONFIDENCE; combines with ADSB_FLAG_FEC_CONSERVATIVE (error_corr "Conservative", else "None") and
+ * ADSB_FLAG_LONG_AWARE_GATE.  Nothing is allocated at create; every entry point other than the stream ones behaves as on a
+ * context without the flag (adsb_last_decoded, adsb_decode_pdus and adsb_set_decoder: -EINVAL).  Without the flag nothing
+ * is allocated or launched and no byte changes. */
+#define ADSB_FLAG_STREAM_DECODE 1024u
 
 /* adsb_burst.flags */
 #define ADSB_BURST_DEMOD 1u /* eob inside the demod input: bits[] valid, a PDU is published (demod.py:82) */
@@ -508,6 +516,42 @@ int adsb_process_stream_batch(adsb_ctx* ctx, int format, const adsb_stream_item*
                               int32_t cap, int32_t* item_first, int32_t* n_out, int32_t* n_fallback);
 int adsb_process_stream_batch_device(adsb_ctx* ctx, int format, const adsb_stream_item* items, int32_t n_items, adsb_burst* out,
                                      int32_t cap, int32_t* item_first, int32_t* n_out, int32_t* n_fallback);
+/* STREAM DECODERS (ADSB_FLAG_STREAM_DECODE).  adsb_streams_open also gives every stream a decoder of its own -- what
+ * ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE is for one receiver -- and adsb_streams_close releases them.  Their state is ONE
+ * sparse store on the device, keyed by (stream, address): open addressing over a power-of-two number of 104-byte slots (the
+ * key, the address's first announcement, the 88-byte plane), at most half of them taken, at most 2^27.  Only a reply that
+ * announces its address takes a slot -- every reply that reaches update_plane does --; address/parity replies with unheard
+ * addresses (noise) take none.  Before a call's decode step the store holds room for one slot per record of the call, or it
+ * is rehashed: the live slots move to a new store, the slots of reset streams are dropped, the old store is freed.  The new
+ * store has the same size unless the LIVE slots plus the call's records would take more than half of it; then it is doubled
+ * until they do not, which is a growth (counted: adsb_stream_decoder_stats).  A rehash changes no row.  The store never
+ * shrinks.  Nothing runs out in a long-lived fleet: the call numbers that order announcements start over at a rehash
+ * before 2^32 calls are reached, with every announcement made so far kept as "earlier".
+ * CONTRACT: for every stream s -- any chunking, any subset of streams per call, n == 0 and END items included -- the
+ * concatenation of its records over all calls is byte-identical to what an ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE context
+ * with the same ADSB_FLAG_FEC_CONSERVATIVE / _LONG_AWARE_GATE flags, format scale and adsb_set_decoder(msg_filter, start_s)
+ * writes for ONE adsb_process_format call over the concatenation of s's chunks (ADSB_BURST_AP_KNOWN / _AP_FEC included), and
+ * the concatenation of its rows is byte-identical to that context's adsb_last_decoded (records left out as n_overlong are
+ * left out of both).  Streams never see each other's aircraft, whatever addresses they share.  Publication order inside a
+ * stream is call order, within a call the order of its records.  A record's PDU timestamp is
+ * start_s + (double)offset / fs with the record's offset (the stream's base included); the decoder's clock is
+ * (long long)timestamp as for ADSB_FLAG_DECODE.
+ * The decode step runs on the call's final record list (the records of items that took the ordinary pass included), and only
+ * once the call is known to be delivered: a call that returns -ENOSPC or any other error has changed no decoder state.
+ * adsb_stream_reset also makes that stream's decoder fresh (a new generation in the store's key: O(1) on the host; every
+ * 2^20 - 2 resets of one stream the store is rehashed); adsb_reset does so for every stream; an ADSB_STREAM_END item does
+ * NOT: the aircraft are still there when the receiver reconnects.  At most 2^20 streams. */
+int adsb_streams_set_decoder(adsb_ctx* ctx, int32_t msg_filter);   /* ADSB_DEC_*, for all streams; default ADSB_DEC_ALL_MESSAGES */
+int adsb_stream_set_start(adsb_ctx* ctx, int32_t stream, double start_timestamp);   /* fresh streams only; default 0 */
+/* Row t belongs to out[t] of the last DELIVERED adsb_process_stream_batch[_device] call (*n = that call's *n_out; *rows NULL
+ * when 0).  Pinned memory of the context, valid until the next stream-batch call. */
+int adsb_stream_last_decoded(adsb_ctx* ctx, const adsb_decoded** rows, int32_t* n);
+/* The store's capacity in slots: rounded up to a power of two that is at least 256 (65536 after adsb_streams_open).  Allowed
+ * while streams are open and no slot is live (-EINVAL otherwise, and above 2^27). */
+int adsb_stream_decoder_reserve(adsb_ctx* ctx, int64_t slots);
+/* planes: plane_dict entries of all streams' decoders together (exact: a reset stream's are gone at once); capacity: slots;
+ * grows: growths since adsb_streams_open.  Any pointer may be NULL.  -EINVAL without the flag or without open streams. */
+int adsb_stream_decoder_stats(adsb_ctx* ctx, int64_t* planes, int64_t* capacity, int64_t* grows);
 /* Device memory on the context's device for callers that do not link HIP (a C or ctypes client of the *_device entry
  * points): hipMalloc / hipFree / a blocking hipMemcpy host -> device.  16-byte alignment is guaranteed.  No reference
  * counterpart (the reference never leaves host memory). */
