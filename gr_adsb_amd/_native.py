@@ -77,7 +77,7 @@ EXPORTS = [
     "adsb_streams_open", "adsb_streams_close", "adsb_stream_set_base", "adsb_stream_state", "adsb_stream_reset",
     "adsb_process_stream_batch", "adsb_process_stream_batch_device",
     "adsb_streams_set_decoder", "adsb_stream_set_start", "adsb_stream_last_decoded", "adsb_stream_decoder_reserve",
-    "adsb_stream_decoder_stats",
+    "adsb_stream_decoder_stats", "adsb_planes", "adsb_stream_planes",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
 ]
 
@@ -181,6 +181,8 @@ def load():
     lib.adsb_stream_last_decoded.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
     lib.adsb_stream_decoder_reserve.argtypes = [vp, i64]
     lib.adsb_stream_decoder_stats.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
+    lib.adsb_planes.argtypes = [vp, vp, i32, c.POINTER(i32)]
+    lib.adsb_stream_planes.argtypes = [vp, vp, i32, vp, i32, vp, c.POINTER(i32)]
     lib.adsb_device_alloc.argtypes = [vp, c.POINTER(vp), c.c_size_t]
     lib.adsb_device_free.argtypes = [vp, vp]
     lib.adsb_device_upload.argtypes = [vp, vp, vp, c.c_size_t]
@@ -330,6 +332,45 @@ class Context:
                                             len(b), rows.ctypes.data_as(ctypes.c_void_p)))
         return rows
 
+    def _snapshot(self, call, cap):
+        """call(rows pointer, cap, n_out) -> rc; the buffer starts at cap rows and is sized by the count the call reports when
+        that was too small (-ENOSPC), once."""
+        n = ctypes.c_int32(0)
+        for _ in range(2):
+            rows = np.zeros(max(int(cap), 0), dtype=DECODED_DTYPE)
+            rc = call(ctypes.c_void_p(rows.ctypes.data) if len(rows) else None, len(rows), ctypes.byref(n))
+            if rc != -28:
+                break
+            cap = n.value
+        self._chk(rc)
+        return rows[:n.value]
+
+    def planes(self, cap=None):
+        """FLAG_DECODE contexts: a snapshot of the decoder's plane table (adsb_planes) -> DECODED_DTYPE rows, one per aircraft in
+        ascending address order (port DEC_NONE, df 0, bits zero; plane_entry turns one into the reference's plane_dict entry).
+        cap: the first buffer's rows (None: a count query first)."""
+        return self._snapshot(lambda r, k, n: self.lib.adsb_planes(self._h, r, k, n), 0 if cap is None else cap)
+
+    def stream_planes(self, streams=None, cap=None):
+        """FLAG_STREAM_DECODE contexts: a snapshot of the streams' plane tables (adsb_stream_planes) -> (rows, first): rows
+        ordered by (stream, address), first[i]:first[i + 1] those of the i-th selected stream.  streams: strictly ascending
+        stream indices, None: all of them.  cap: the first buffer's rows (None: stream_decoder_stats' plane count)."""
+        if streams is None:
+            sel, k = None, 0
+            first = np.zeros(self._n_streams() + 1, dtype=np.int32)
+        else:
+            sel = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+            check_stream_selection(sel, self._n_streams())
+            k = len(sel)
+            first = np.zeros(k + 1, dtype=np.int32)
+        sp = None if sel is None else ctypes.c_void_p(sel.ctypes.data) if k else ctypes.c_void_p(first.ctypes.data)
+        rows = self._snapshot(lambda r, c_, n: self.lib.adsb_stream_planes(self._h, sp, k, r, c_, ctypes.c_void_p(first.ctypes.data), n),
+                              self.stream_decoder_stats()[0] if cap is None else cap)
+        return rows, first
+
+    def _n_streams(self):
+        return getattr(self, "_streams_open", 0)
+
     def submit_format_host(self, fmt, data, abs_offset=0):
         """Host-fed pipelined submission (adsb_submit_format_host): data = host array in the format's layout; a
         page-locked one (PinnedArray, torch pin_memory) is DMA'd where it lies and must stay alive until wait()."""
@@ -405,9 +446,11 @@ class Context:
     # Receiver streams carried across batch calls (adsb_process_stream_batch*; include/adsb_hip.h has the contract)
     def open_streams(self, n_streams):
         self._chk(self.lib.adsb_streams_open(self._h, int(n_streams)))
+        self._streams_open = int(n_streams)
 
     def close_streams(self):
         self._chk(self.lib.adsb_streams_close(self._h))
+        self._streams_open = 0
 
     def set_stream_base(self, stream, abs_offset):
         self._chk(self.lib.adsb_stream_set_base(self._h, int(stream), int(abs_offset)))
@@ -934,6 +977,29 @@ def decoded_pdu(row, meta):
     vec = unpack_bits(np.asarray(row["bits"], dtype=np.uint8)).reshape(112)
     if port == DEC_UNKNOWN:
         return "unknown", ({"timestamp": ts, "datetime": dt, "df": int(row["df"]), "snr": meta["snr"]}, vec)
+    d = plane_entry(row)
+    d["timestamp"] = ts
+    d["datetime"] = dt
+    d["icao"] = "{:06x}".format(int(row["icao"]))
+    d["df"] = int(row["df"])
+    d["snr"] = meta["snr"]
+    return "decoded", (d, vec)
+
+
+def check_stream_selection(streams, n_streams):
+    """adsb_stream_planes' rule for a selection: indices in 0 .. n_streams - 1, strictly ascending (ValueError otherwise)."""
+    sel = [int(x) for x in streams]
+    if any(x < 0 or x >= n_streams for x in sel):
+        raise ValueError("stream indices have to be in 0 .. %d: %r" % (n_streams - 1, sel))
+    if any(b <= a for a, b in zip(sel, sel[1:])):
+        raise ValueError("stream indices have to be strictly ascending: %r" % (sel,))
+
+
+def plane_entry(row):
+    """One snapshot row (Context.planes / stream_planes) -> the reference's plane_dict entry (decoder.py:413-449) without
+    "cpr" and "last_seen": callsign (None or str), altitude, speed, heading, vertical_rate, latitude, longitude, num_msgs,
+    with decoded_pdu's conversions and Python types (speed and heading with NumPy from the integer components, NaN where the
+    plane has no value)."""
     pr = int(row["present"])
     nan = float("nan")
     d = {"callsign": bytes(row["callsign"]).rstrip(b"\0").decode() if pr & DEC_HAS_CALLSIGN else None,
@@ -948,9 +1014,22 @@ def decoded_pdu(row, meta):
     d["latitude"] = float(row["latitude"])
     d["longitude"] = float(row["longitude"])
     d["num_msgs"] = int(row["num_msgs"])
-    d["timestamp"] = ts
-    d["datetime"] = dt
-    d["icao"] = "{:06x}".format(int(row["icao"]))
-    d["df"] = int(row["df"])
-    d["snr"] = meta["snr"]
-    return "decoded", (d, vec)
+    return d
+
+
+def plane_table(rows, timestamp):
+    """The lines print_planes (decoder.py:455-506) draws for these snapshot rows at PDU timestamp `timestamp`: one string per
+    plane, in the rows' order."""
+    import datetime
+    seen = datetime.datetime.utcfromtimestamp(timestamp).strftime("%H:%M:%S")
+    out = []
+    for row in rows:
+        p = plane_entry(row)
+        num = lambda v, f, w: f.format(v) if not np.isnan(v) else " " * w     # noqa: E731
+        out.append("{:8s} {:6s} {} {} {} {} {} {} {} {}".format(
+            seen, "{:06x}".format(int(row["icao"])),
+            "{:8s}".format(p["callsign"]) if p["callsign"] is not None else " " * 8,
+            num(p["altitude"], "{:5.0f}", 5), num(p["vertical_rate"], "{:5.0f}", 5), num(p["speed"], "{:5.0f}", 5),
+            num(p["heading"], "{:5.0f}", 5), num(p["latitude"], "{:11.7f}", 11), num(p["longitude"], "{:11.7f}", 11),
+            "{:4d}".format(p["num_msgs"])))
+    return out

@@ -598,8 +598,9 @@ class decoder(gr.sync_block):
     int(time.time()), the same when it decodes in real time with zero latency.
 
     A PDU on which the reference raises (DF 18 CF 2/3/5, TC 19 ST 0/5/6/7: decode_packet raises before it publishes) is
-    counted in `self.raised` and publishes nothing.  print_level: any value is accepted, nothing is printed (the curses
-    table and the log lines are not reproduced).  error_corr "Brute Force" behaves as "None", like the reference's branch."""
+    counted in `self.raised` and publishes nothing.  print_level: any value is accepted, nothing is printed (no curses
+    screen and no log lines; plane_table() returns the "Brief" table's text).  error_corr "Brute Force" behaves as "None",
+    like the reference's branch."""
 
     def __init__(self, msg_filter, error_corr, print_level="None", device=0):
         if error_corr not in _ERROR_CORR:
@@ -639,6 +640,19 @@ class decoder(gr.sync_block):
             if out is not None:
                 port, (d, vec) = out
                 self.message_port_pub(self._dec if port == "decoded" else self._unk, pmt.cons(pmt.to_pmt(d), pmt.to_pmt(vec)))
+
+    @property
+    def plane_dict(self):
+        """The reference's plane_dict (decoder.py:413-449) from a fresh snapshot of the device's table (adsb_planes):
+        {"%06x" % icao: _native.plane_entry(row)}.  Read-only -- a new dict every time, nothing written to it reaches the
+        decoder.  Two deviations from the reference's attribute: the keys come in ascending address order, not in the order
+        the aircraft were first heard, and an entry has no "cpr" and no "last_seen"."""
+        return {"{:06x}".format(int(r["icao"])): _native.plane_entry(r) for r in self._ctx.planes()}
+
+    def plane_table(self, timestamp):
+        """The lines print_planes (decoder.py:455-506) would draw after a PDU with this timestamp: one string per plane of a
+        fresh snapshot, in ascending address order.  Nothing is printed and no screen is opened."""
+        return _native.plane_table(self._ctx.planes(), timestamp)
 
     def reset(self):
         """Forget every plane (adsb_reset)."""

@@ -3093,6 +3093,154 @@ __global__ void __launch_bounds__(kThreads) k_fleet_rehash(FleetStore from, Flee
   }
 }
 
+// ---- snapshots of the decoders' plane tables (adsb_planes, adsb_stream_planes): plane_dict read back -------------------------
+// Read-only: nothing here writes a table, a store or a plane.  A snapshot row is dec_row's conversion of the Plane, with no
+// PDU around it: port kDecNone, df 0, bits zero, icao = the address.
+//
+// One decoder (ADSB_FLAG_DECODE): the rows come out in address order without a ticket -- k_planes_tally counts the live planes
+// of every chunk of kPlanesChunk contiguous addresses (one wavefront per chunk), k_dec_sort_scan turns the counts into each
+// chunk's first row (and, one entry behind the last chunk, the total), k_planes_emit writes row base + rank, the rank from
+// wave ballots.  Both scan the 8-byte first-announcement table, not the 88-byte planes, and read planes[a] only where
+// table[a] is not empty.  That finds every live plane: an entry becomes a plane only in dec_apply, reached from k_dec_fold
+// for a record with c.ev > kEvSnap filed under c.addr, and dec_classify gives such a verdict only where the table step of
+// the same call has announced c.addr before the fold runs (launch_air queues k_air_announce .. k_air_verdict in front of
+// launch_dec on one stream, for a pass's list and for adsb_decode_pdus' slices alike; the two share air_skip):
+//   * an AP reply with kApKnown: k_air_verdict set it because table[AA] < its key, and c.addr is that AA;
+//   * an AP reply with kApFec: k_air_cond left the flag only where it made the announcement `cann` -- the AA when the repaired
+//     DF is 0/4/5/16/20/21 (c.addr stays the AA), air_announce of the repaired reply when it became DF 11/17/18/19 (c.addr is
+//     its AA field, and c.ev > kEvSnap exactly for the type codes air_announce lists); a repaired DF 24 has c.ev == kEvSnap;
+//   * DF 11/17/18/19 with kParityOk, or kFecDf and a repair: air_classify's `ann` under the same two conditions, by the same
+//     type codes; msg_filter only removes records from dec_classify's side.
+// adsb_reset empties the table and moves the epoch on together, so an empty entry never hides a plane of the current epoch.
+// The converse does not hold (an announced address whose records the msg_filter rejects has no plane): hence the second look.
+constexpr int kPlanesChunk = 2048;         // addresses per wavefront: 16 iterations of 64 lanes x two 8-byte keys
+constexpr int kPlanesStep = 128;           // addresses per iteration
+struct PlanesDense {
+  const unsigned long long* table;         // indexed by address
+  const Plane* planes;
+  unsigned epoch;
+  unsigned lo, hi;                         // addresses [lo, hi): lo a multiple of kPlanesChunk, hi even (the product: 0, 2^24)
+};
+__device__ __forceinline__ unsigned planes_chunks(const PlanesDense& a) { return (a.hi - a.lo + kPlanesChunk - 1u) / kPlanesChunk; }
+__device__ __forceinline__ bool planes_live(const PlanesDense& a, unsigned long long key, unsigned addr) {
+  if (key == kAirEmpty) return false;
+  const Plane* p = &a.planes[addr];
+  return p->epoch == a.epoch && (p->present & kHasPlane) != 0;
+}
+__device__ __forceinline__ void planes_row(DecRow* rows, int cap, unsigned j, const Plane* src, unsigned addr) {
+  if (j >= (unsigned)cap) return;
+  const Plane p = *src;
+  DecClass c{};
+  c.addr = (int)addr;
+  dec_row(&rows[j], c, kDecNone, &p);
+}
+
+// counts[chunk] = live planes of the chunk; counts[number of chunks] = 0 (the scan leaves the total there)
+__global__ void __launch_bounds__(kThreads) k_planes_tally(PlanesDense a, unsigned* counts) {
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const unsigned n_chunks = planes_chunks(a);
+  if (blockIdx.x == 0 && threadIdx.x == 0) counts[n_chunks] = 0;
+  for (unsigned c = blockIdx.x * kWaves + (unsigned)wave; c < n_chunks; c += gridDim.x * kWaves) {
+    unsigned n = 0;
+    for (int r = 0; r < kPlanesChunk / kPlanesStep; ++r) {
+      const unsigned addr = a.lo + c * kPlanesChunk + (unsigned)(r * kPlanesStep + 2 * lane);
+      if (addr < a.hi) {
+        const stream_v16 k = *reinterpret_cast<const stream_v16*>(&a.table[addr]);
+        n += (planes_live(a, k[0], addr) ? 1u : 0u) + (planes_live(a, k[1], addr + 1u) ? 1u : 0u);
+      }
+    }
+    for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o);
+    if (lane == 0) counts[c] = n;
+  }
+}
+
+// base = the scanned counts.  A chunk without planes is not read again.  Inside an iteration lane l's two addresses precede
+// lane l + 1's.
+__global__ void __launch_bounds__(kThreads) k_planes_emit(PlanesDense a, const unsigned* base, int cap, DecRow* rows) {
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const unsigned n_chunks = planes_chunks(a);
+  for (unsigned c = blockIdx.x * kWaves + (unsigned)wave; c < n_chunks; c += gridDim.x * kWaves) {
+    unsigned pos = base[c];
+    if (base[c + 1] == pos) continue;
+    for (int r = 0; r < kPlanesChunk / kPlanesStep; ++r) {
+      const unsigned addr = a.lo + c * kPlanesChunk + (unsigned)(r * kPlanesStep + 2 * lane);
+      bool l0 = false, l1 = false;
+      if (addr < a.hi) {
+        const stream_v16 k = *reinterpret_cast<const stream_v16*>(&a.table[addr]);
+        l0 = planes_live(a, k[0], addr);
+        l1 = planes_live(a, k[1], addr + 1u);
+      }
+      const unsigned long long m0 = __ballot(l0), m1 = __ballot(l1);
+      const unsigned j = pos + (unsigned)__popcll(m0 & lt) + (unsigned)__popcll(m1 & lt);
+      if (l0) planes_row(rows, cap, j, &a.planes[addr], addr);
+      if (l1) planes_row(rows, cap, j + (l0 ? 1u : 0u), &a.planes[addr + 1u], addr + 1u);
+      pos += (unsigned)__popcll(m0) + (unsigned)__popcll(m1);
+    }
+  }
+}
+
+// The fleet (ADSB_FLAG_STREAM_DECODE): k_planes_store_keys scans the store's keys and compacts the 44-bit stream << 24 |
+// address of every slot that is live -- its generation is its stream's current one, so a reset stream's stale slots are not
+// -- selected, and holds a plane; the order the wavefronts' tickets give does not matter, because the keys are unique and the
+// library's radix sort (k_dec_sort_*, eleven nibbles from bit 0) follows.  k_planes_store_emit looks row j's slot up again
+// and derives first[] from the sorted keys.
+struct PlanesFleet {
+  FleetStore s;
+  const unsigned* gen;                     // [n_streams]: the streams' current generations
+  const unsigned* sel_bits;                // bit `stream` set: selected; null: every stream
+  int n_streams;
+};
+constexpr unsigned long long kPlanesKeyMask = (1ull << (kFleetAddrBits + kFleetStreamBits)) - 1ull;
+__global__ void __launch_bounds__(kThreads) k_planes_store_keys(PlanesFleet a, unsigned long long* keys, int cap, int* count) {
+  const int lane = (int)(threadIdx.x & 63);
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  // (the store has a power of two >= 256 slots: a wavefront's 64 slots all exist)
+  for (unsigned w0 = blockIdx.x * kThreads + (threadIdx.x & ~63u); w0 <= a.s.mask; w0 += gridDim.x * kThreads) {
+    const unsigned i = w0 + (unsigned)lane;
+    const unsigned long long key = a.s.keys[i];
+    bool keep = false;
+    if (key != kFleetEmpty) {
+      const unsigned stream = (unsigned)(key >> kFleetAddrBits) & ((1u << kFleetStreamBits) - 1u);
+      keep = stream < (unsigned)a.n_streams && a.gen[stream] == (unsigned)(key >> (kFleetAddrBits + kFleetStreamBits)) &&
+             (!a.sel_bits || ((a.sel_bits[stream >> 5] >> (stream & 31u)) & 1u)) && (a.s.planes[i].present & kHasPlane) != 0;
+    }
+    const unsigned long long m = __ballot(keep);
+    if (m == 0) continue;
+    int b0 = 0;
+    if (lane == 0) b0 = atomicAdd(count, __popcll(m));
+    b0 = __shfl(b0, 0);
+    const int j = b0 + __popcll(m & lt);
+    if (keep && j < cap) keys[j] = key & kPlanesKeyMask;
+  }
+}
+
+// sel: the selected streams in ascending order (null: stream i is the i-th); first[i] = the first row whose key is not below
+// sel[i] << 24, first[n_sel] = n
+__global__ void __launch_bounds__(kThreads) k_planes_store_emit(PlanesFleet a, const unsigned long long* sorted, int n, const int* sel,
+                                                                int n_sel, DecRow* rows, int* first, int* error) {
+  const int t0 = (int)(blockIdx.x * kThreads + threadIdx.x), step = (int)(gridDim.x * kThreads);
+  for (int j = t0; j < n; j += step) {
+    const unsigned long long key = sorted[j];
+    const unsigned stream = (unsigned)(key >> kFleetAddrBits);
+    bool claimed = false;
+    const unsigned h = fleet_slot(a.s, ((unsigned long long)a.gen[stream] << (kFleetAddrBits + kFleetStreamBits)) | key, false, &claimed);
+    if (h == kFleetNone) { ADSB_AIR_STORE(error, 1); continue; }
+    planes_row(rows, n, (unsigned)j, &a.s.planes[h], (unsigned)key & ((1u << kFleetAddrBits) - 1u));
+  }
+  for (int i = t0; first && i <= n_sel; i += step) {
+    int lo = 0, hi = n;
+    if (i < n_sel) {
+      const unsigned long long want = (unsigned long long)(unsigned)(sel ? sel[i] : i) << kFleetAddrBits;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sorted[mid] < want) lo = mid + 1; else hi = mid;
+      }
+    } else lo = n;
+    first[i] = lo;
+  }
+}
+
 }  // namespace adsb
 
 // Stage 2 of the decode step.  Outside adsb, in an unnamed namespace: the three kernels are the including unit's own, so the

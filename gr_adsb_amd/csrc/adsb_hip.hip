@@ -306,6 +306,7 @@ struct FleetDec {
   unsigned long long call = 0;                  // number of the next delivered call with records (ordering keys: number << 32 | position)
   DevBuf d_store;                               // keys[cap] | ann[cap] | planes[cap]
   DevBuf d_recs, d_items, d_cnt, d_keys, d_sorted, d_tmp, d_ts, d_rows, d_gen;
+  DevBuf d_snap;                                // adsb_stream_planes: generations | selection bitmap | selection list | first[] | count, error
   PinnedBuf h_recs, h_rows, h_items, h_cnt;
   int32_t n_rows = 0;                           // rows of the last delivered call
 };
@@ -467,6 +468,7 @@ struct adsb_ctx {
   double dec_start = 0;
   DevBuf d_dec_keys, d_dec_sorted, d_dec_tmp;
   PinnedBuf h_pdu;                    // adsb_decode_pdus' staging (device-visible)
+  DevBuf d_snap_cnt, d_snap_rows;     // adsb_planes: the chunks' counts / first rows, and the snapshot's rows
   BatchBufs bt;                       // adsb_process_batch*
   StreamBufs sb;                      // adsb_process_stream_batch*
   FleetDec fd;                        // ... and their decoders (ADSB_FLAG_STREAM_DECODE)
@@ -1648,7 +1650,7 @@ int fleet_close(adsb_ctx* c) {
   FleetDec& F = c->fd;
   F.open = false; F.cap = 0; F.n_rows = 0;
   F.start.clear(); F.gen.clear(); F.slots.clear(); F.planes.clear();
-  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen}) HIPCHK(c, b->release());
+  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen, &F.d_snap}) HIPCHK(c, b->release());
   for (PinnedBuf* b : {&F.h_recs, &F.h_rows, &F.h_items, &F.h_cnt}) HIPCHK(c, b->release());
   return 0;
 }
@@ -2511,6 +2513,117 @@ int adsb_decode_pdus(adsb_ctx* c, const uint8_t* bits14, const double* timestamp
   if (he == hipSuccess) he = hipGetLastError();
   if (he != hipSuccess) return fail(c, -EIO, "decode step", he);
   memcpy(rows, h, nt * sizeof(adsb_decoded));
+  return 0;
+}
+
+// ---- snapshots of the plane tables (include/adsb_hip.h PLANE SNAPSHOTS; adsb_device.h: the k_planes_* kernels) --------------
+// Both run on the context's stream behind the event of the last table / decode step and return when the rows are in the
+// caller's memory; they write no state of the decoders.
+static int planes_args(adsb_ctx* c, const adsb_decoded* rows, int32_t cap, const int32_t* n_out) {
+  if (!c) return -EINVAL;
+  if (!n_out || cap < 0 || (cap > 0 && !rows)) return fail(c, -EINVAL, "plane snapshot: n_out, or rows for cap > 0, missing");
+  return 0;
+}
+
+int adsb_planes(adsb_ctx* c, adsb_decoded* rows, int32_t cap, int32_t* n_out) {
+  int rc = planes_args(c, rows, cap, n_out);
+  if (rc) return rc;
+  if (!(c->flags & ADSB_FLAG_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_DECODE");
+  if ((rc = require_idle(c, kCallPending))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = c->stream;
+  PlanesDense a{};
+  a.table = c->d_air; a.planes = c->d_planes; a.epoch = c->dec_epoch; a.lo = 0u; a.hi = 1u << 24;
+  const unsigned n_chunks = (a.hi - a.lo) / kPlanesChunk;
+  if ((rc = ensure(c, c->d_snap_cnt, ((size_t)n_chunks + 1) * sizeof(unsigned)))) return rc;
+  unsigned* const cnt = (unsigned*)c->d_snap_cnt.p;
+  const unsigned g = step_grid(n_chunks, kWaves);
+  HIPCHK(c, hipStreamWaitEvent(st, c->air_ev, 0));
+  hipLaunchKernelGGL(k_planes_tally, dim3(g), dim3(kThreads), 0, st, a, cnt);
+  hipLaunchKernelGGL(k_dec_sort_scan, dim3(1), dim3(kThreads), 0, st, cnt, (int)n_chunks + 1);
+  HIPCHK(c, hipGetLastError());
+  unsigned total = 0;
+  HIPCHK(c, hipMemcpyAsync(&total, cnt + n_chunks, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  *n_out = (int32_t)total;
+  if ((long long)total > (long long)cap) return fail(c, -ENOSPC, "adsb_planes: cap is smaller than the number of planes (*n_out)");
+  if (total == 0) return 0;
+  if ((rc = ensure(c, c->d_snap_rows, (size_t)total * sizeof(DecRow)))) return rc;
+  hipLaunchKernelGGL(k_planes_emit, dim3(g), dim3(kThreads), 0, st, a, (const unsigned*)cnt, (int)total, (DecRow*)c->d_snap_rows.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(rows, c->d_snap_rows.p, (size_t)total * sizeof(DecRow), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return 0;
+}
+
+int adsb_stream_planes(adsb_ctx* c, const int32_t* streams, int32_t n_sel, adsb_decoded* rows, int32_t cap, int32_t* first,
+                       int32_t* n_out) {
+  int rc = planes_args(c, rows, cap, n_out);
+  if (rc) return rc;
+  if (!(c->flags & ADSB_FLAG_STREAM_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE");
+  FleetDec& F = c->fd;
+  if (!F.open) return fail(c, -EINVAL, "adsb_stream_planes: no streams (adsb_streams_open first)");
+  const size_t ns = F.gen.size();
+  if (!streams) n_sel = (int32_t)ns;
+  if (n_sel < 0) return fail(c, -EINVAL, "adsb_stream_planes: n_sel < 0");
+  for (int32_t i = 0; streams && i < n_sel; ++i)
+    if (streams[i] < 0 || (size_t)streams[i] >= ns || (i > 0 && streams[i] <= streams[i - 1]))
+      return fail(c, -EINVAL, "adsb_stream_planes: stream indices have to be in range and strictly ascending");
+  if ((rc = require_idle(c, kCallPending))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = c->stream;
+  // the staging block: generations | selection bitmap | selection list | first[] | count, error
+  const size_t nw = (ns + 31) / 32, nsel = (size_t)n_sel;
+  const size_t o_bits = ns, o_sel = o_bits + nw, o_first = o_sel + nsel, o_cnt = o_first + nsel + 1, words = o_cnt + 2;
+  std::vector<unsigned> h(words, 0u);
+  for (size_t s = 0; s < ns; ++s) h[s] = F.gen[s];
+  for (int32_t i = 0; streams && i < n_sel; ++i) {
+    h[o_bits + (size_t)streams[i] / 32] |= 1u << ((unsigned)streams[i] & 31u);
+    h[o_sel + (size_t)i] = (unsigned)streams[i];
+  }
+  const long long key_cap = F.live_planes;                     // every live plane is counted there (fleet_step)
+  if ((rc = ensure(c, F.d_snap, words * sizeof(unsigned))) || (rc = ensure(c, F.d_keys, (size_t)key_cap * 8)) ||
+      (rc = ensure(c, F.d_sorted, (size_t)key_cap * 8)))
+    return rc;
+  unsigned* const d = (unsigned*)F.d_snap.p;
+  HIPCHK(c, hipMemcpyAsync(d, h.data(), words * sizeof(unsigned), hipMemcpyHostToDevice, st));
+  PlanesFleet a{};
+  a.s = fleet_view(F.d_store.p, F.cap); a.gen = d; a.sel_bits = streams ? d + o_bits : nullptr; a.n_streams = (int)ns;
+  int* const d_cnt = (int*)(d + o_cnt);
+  hipLaunchKernelGGL(k_planes_store_keys, dim3(step_grid(F.cap, kThreads)), dim3(kThreads), 0, st, a, (unsigned long long*)F.d_keys.p,
+                     (int)key_cap, d_cnt);
+  HIPCHK(c, hipGetLastError());
+  int got[2] = {0, 0};
+  HIPCHK(c, hipMemcpyAsync(got, d_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const int n = got[0];
+  if ((long long)n > key_cap) return fail(c, -EIO, "stream decoders: the store holds more planes than the streams count");
+  *n_out = n;
+  if (n > cap) return fail(c, -ENOSPC, "adsb_stream_planes: cap is smaller than the number of planes (*n_out)");
+  if (n == 0) {
+    if (first) memset(first, 0, (nsel + 1) * sizeof(int32_t));
+    return 0;
+  }
+  const int nblk = (n + kSortTile - 1) / kSortTile;
+  if ((rc = ensure(c, F.d_tmp, (size_t)nblk * 16 * sizeof(unsigned))) || (rc = ensure(c, F.d_rows, (size_t)n * sizeof(DecRow)))) return rc;
+  unsigned long long* in = (unsigned long long*)F.d_keys.p;
+  unsigned long long* out = (unsigned long long*)F.d_sorted.p;
+  for (int shift = 0; shift < kFleetAddrBits + kFleetStreamBits; shift += 4) {          // eleven passes: the result ends in d_sorted
+    hipLaunchKernelGGL(k_dec_sort_hist, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, n, shift, (unsigned*)F.d_tmp.p);
+    hipLaunchKernelGGL(k_dec_sort_scan, dim3(1), dim3(kThreads), 0, st, (unsigned*)F.d_tmp.p, nblk * 16);
+    hipLaunchKernelGGL(k_dec_sort_scatter, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, out, n, shift,
+                       (const unsigned*)F.d_tmp.p);
+    unsigned long long* x = in; in = out; out = x;
+  }
+  hipLaunchKernelGGL(k_planes_store_emit, dim3(step_grid(std::max((long long)n, (long long)nsel + 1), kThreads)), dim3(kThreads), 0, st, a,
+                     (const unsigned long long*)F.d_sorted.p, n, streams ? (const int*)(d + o_sel) : (const int*)nullptr, (int)n_sel,
+                     (DecRow*)F.d_rows.p, first ? (int*)(d + o_first) : (int*)nullptr, d_cnt + 1);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(rows, F.d_rows.p, (size_t)n * sizeof(DecRow), hipMemcpyDeviceToHost, st));
+  if (first) HIPCHK(c, hipMemcpyAsync(first, d + o_first, (nsel + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(got, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (got[1]) return fail(c, -EIO, "stream decoders: the snapshot found a plane without a slot");
   return 0;
 }
 

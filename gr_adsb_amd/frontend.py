@@ -240,6 +240,15 @@ class Receivers:
             self.rows = [rows.get(i, np.zeros(0, dtype=_native.DECODED_DTYPE)) for i in ids]
         return [out[i] for i in ids]
 
+    def planes(self, ids=None):
+        """FLAG_STREAM_DECODE contexts: what each receiver sees now -- a list of DECODED_DTYPE row arrays, one per stream of
+        `ids` (strictly ascending; None: every stream), each in ascending address order, from one device snapshot of the
+        decoders' store (adsb_stream_planes; _native.plane_entry turns a row into the reference's plane_dict entry)."""
+        if not self.decode:
+            raise ValueError("planes() needs a FLAG_STREAM_DECODE context")
+        rows, first = self.ctx.stream_planes(ids)
+        return [rows[first[i]:first[i + 1]] for i in range(len(first) - 1)]
+
     def state(self, i):
         """(pos, eob, n_overlong) of stream i"""
         return self.ctx.stream_state(i)

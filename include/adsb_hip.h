@@ -552,6 +552,32 @@ int adsb_stream_decoder_reserve(adsb_ctx* ctx, int64_t slots);
 /* planes: plane_dict entries of all streams' decoders together (exact: a reset stream's are gone at once); capacity: slots;
  * grows: growths since adsb_streams_open.  Any pointer may be NULL.  -EINVAL without the flag or without open streams. */
 int adsb_stream_decoder_stats(adsb_ctx* ctx, int64_t* planes, int64_t* capacity, int64_t* grows);
+/* PLANE SNAPSHOTS: the decoders' plane_dict (decoder.py:413-449) read back from the device, for one decoder (adsb_planes:
+ * ADSB_FLAG_DECODE contexts, -EINVAL on others) and for a fleet (adsb_stream_planes: ADSB_FLAG_STREAM_DECODE contexts with open
+ * streams, -EINVAL otherwise).  Entry points only: nothing runs unless a caller asks, and ADSB_ABI_VERSION is unchanged.
+ * A snapshot row is an adsb_decoded row: port = ADSB_DEC_NONE, df = 0, bits and every pad byte zero, icao = the address;
+ * present (always with ADSB_DEC_HAS_PLANE), callsign, altitude, velocity_we, velocity_sn, vertical_rate, latitude, longitude
+ * and num_msgs hold exactly what the row of a record that touches the plane would show at this moment.  The CPR frames
+ * (plane_dict's "cpr") and last_seen are NOT part of a snapshot: the device keeps no last_seen, and print_planes
+ * (decoder.py:452-509) prints neither.
+ * adsb_planes: every address whose plane exists in the context's current epoch, in ascending address order; nothing after
+ * adsb_reset; an address that was announced but has no plane is not returned.
+ * adsb_stream_planes: streams == NULL selects all n_streams streams (n_sel is ignored and counts as n_streams); otherwise
+ * streams[0 .. n_sel) are stream indices in strictly ascending order (-EINVAL when out of range or not ascending).  Rows are
+ * ordered by (stream, address).  first may be NULL; else first[i] .. first[i + 1] are the rows of the i-th selected stream
+ * (n_sel + 1 entries, first[n_sel] == *n_out: item_first's convention).  A stream's planes are those of its current
+ * generation: adsb_stream_reset removes them at once (its slots stay in the store until the next rehash), an ADSB_STREAM_END
+ * item does not, and streams never show each other's aircraft.
+ * Both: cap smaller than the number of planes is -ENOSPC with *n_out = the number needed and nothing written (rows == NULL
+ * with cap == 0 is a count query); -EBUSY while submitted tickets are pending.  A snapshot is taken behind the last queued
+ * table or decode step (it waits on their event chain), so it reflects every delivered call and every adsb_decode_pdus call
+ * that returned before it, and nothing else.  It changes no state: rows decoded after it are byte-identical to rows
+ * decoded without it, two snapshots with nothing between them are byte-identical, and adsb_last_result, adsb_last_decoded,
+ * adsb_stream_last_decoded and the framer state are untouched.  No reference counterpart as a call: the reference's
+ * plane_dict is a host dict. */
+int adsb_planes(adsb_ctx* ctx, adsb_decoded* rows, int32_t cap, int32_t* n_out);
+int adsb_stream_planes(adsb_ctx* ctx, const int32_t* streams, int32_t n_sel, adsb_decoded* rows, int32_t cap, int32_t* first,
+                       int32_t* n_out);
 /* Device memory on the context's device for callers that do not link HIP (a C or ctypes client of the *_device entry
  * points): hipMalloc / hipFree / a blocking hipMemcpy host -> device.  16-byte alignment is guaranteed.  No reference
  * counterpart (the reference never leaves host memory). */
