@@ -26,6 +26,7 @@ FLAG_FEC_CONSERVATIVE = 128  # opt-in: the decoder's "Conservative" 1-2-bit burs
 FLAG_AIRCRAFT_TABLE = 256    # opt-in: the decoder's aircraft table on the device: verdicts for address/parity replies
 FLAG_DECODE = 512            # opt-in (with FLAG_AIRCRAFT_TABLE): the decoder's message decoding and plane fields on the device
 FLAG_STREAM_DECODE = 1024    # opt-in: one decoder behind every receiver stream (open_streams), one device step per stream-batch call
+FLAG_PLANE_AGES = 2048       # opt-in, with FLAG_DECODE or FLAG_STREAM_DECODE: plane_dict's last_seen on the device (planes(seen=True), expire_*)
 # include/adsb_hip.h adsb_decoded: one row per delivered record of a FLAG_DECODE context
 DECODED_DTYPE = np.dtype([("port", "u1"), ("df", "u1"), ("present", "u1"), ("pad0", "u1"), ("icao", "<i4"), ("bits", "u1", (14,)),
                           ("callsign", "S8"), ("pad1", "u1", (2,)), ("altitude", "<i4"), ("velocity_we", "<i4"),
@@ -78,6 +79,7 @@ EXPORTS = [
     "adsb_process_stream_batch", "adsb_process_stream_batch_device",
     "adsb_streams_set_decoder", "adsb_stream_set_start", "adsb_stream_last_decoded", "adsb_stream_decoder_reserve",
     "adsb_stream_decoder_stats", "adsb_planes", "adsb_stream_planes",
+    "adsb_planes_seen", "adsb_stream_planes_seen", "adsb_planes_expire", "adsb_stream_planes_expire",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
 ]
 
@@ -183,6 +185,10 @@ def load():
     lib.adsb_stream_decoder_stats.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
     lib.adsb_planes.argtypes = [vp, vp, i32, c.POINTER(i32)]
     lib.adsb_stream_planes.argtypes = [vp, vp, i32, vp, i32, vp, c.POINTER(i32)]
+    lib.adsb_planes_seen.argtypes = [vp, vp, vp, i32, c.POINTER(i32)]
+    lib.adsb_stream_planes_seen.argtypes = [vp, vp, i32, vp, vp, i32, vp, c.POINTER(i32)]
+    lib.adsb_planes_expire.argtypes = [vp, c.c_int64, c.POINTER(c.c_int64)]
+    lib.adsb_stream_planes_expire.argtypes = [vp, vp, i32, vp, c.POINTER(c.c_int64)]
     lib.adsb_device_alloc.argtypes = [vp, c.POINTER(vp), c.c_size_t]
     lib.adsb_device_free.argtypes = [vp, vp]
     lib.adsb_device_upload.argtypes = [vp, vp, vp, c.c_size_t]
@@ -332,29 +338,64 @@ class Context:
                                             len(b), rows.ctypes.data_as(ctypes.c_void_p)))
         return rows
 
-    def _snapshot(self, call, cap):
+    def _snapshot(self, call, cap, seen=False):
         """call(rows pointer, cap, n_out) -> rc; the buffer starts at cap rows and is sized by the count the call reports when
-        that was too small (-ENOSPC), once."""
+        that was too small (-ENOSPC), once.  seen: call(rows pointer, last_seen pointer, cap, n_out) -> (rows, last_seen)."""
         n = ctypes.c_int32(0)
         for _ in range(2):
             rows = np.zeros(max(int(cap), 0), dtype=DECODED_DTYPE)
-            rc = call(ctypes.c_void_p(rows.ctypes.data) if len(rows) else None, len(rows), ctypes.byref(n))
+            rp = ctypes.c_void_p(rows.ctypes.data) if len(rows) else None
+            if seen:
+                ages = np.zeros(len(rows), dtype=np.int64)
+                rc = call(rp, ctypes.c_void_p(ages.ctypes.data) if len(rows) else None, len(rows), ctypes.byref(n))
+            else:
+                rc = call(rp, len(rows), ctypes.byref(n))
             if rc != -28:
                 break
             cap = n.value
         self._chk(rc)
-        return rows[:n.value]
+        return (rows[:n.value], ages[:n.value]) if seen else rows[:n.value]
 
-    def planes(self, cap=None):
+    def planes(self, cap=None, seen=False):
         """FLAG_DECODE contexts: a snapshot of the decoder's plane table (adsb_planes) -> DECODED_DTYPE rows, one per aircraft in
         ascending address order (port DEC_NONE, df 0, bits zero; plane_entry turns one into the reference's plane_dict entry).
-        cap: the first buffer's rows (None: a count query first)."""
+        cap: the first buffer's rows (None: a count query first).  seen (FLAG_PLANE_AGES contexts; adsb_planes_seen):
+        (rows, last_seen), last_seen[j] the int64 clock of rows[j]'s last update_plane."""
+        if seen:
+            return self._snapshot(lambda r, a, k, n: self.lib.adsb_planes_seen(self._h, r, a, k, n), 0 if cap is None else cap, True)
         return self._snapshot(lambda r, k, n: self.lib.adsb_planes(self._h, r, k, n), 0 if cap is None else cap)
 
-    def stream_planes(self, streams=None, cap=None):
+    def expire_planes(self, cutoff):
+        """FLAG_DECODE | FLAG_PLANE_AGES contexts: remove every plane with last_seen < cutoff as `del plane_dict[key]` does
+        (adsb_planes_expire) -> the number removed."""
+        n = ctypes.c_int64(0)
+        self._chk(self.lib.adsb_planes_expire(self._h, int(cutoff), ctypes.byref(n)))
+        return n.value
+
+    def expire_stream_planes(self, cutoffs, streams=None):
+        """FLAG_STREAM_DECODE | FLAG_PLANE_AGES contexts: remove every plane of the i-th selected stream (streams: strictly
+        ascending indices, None: all) with last_seen < cutoffs[i] (adsb_stream_planes_expire) -> the number removed."""
+        cut = np.ascontiguousarray(cutoffs, dtype=np.int64).reshape(-1)
+        if streams is None:
+            sp, k = None, 0
+            want = self._n_streams()
+        else:
+            sel = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+            check_stream_selection(sel, self._n_streams())
+            want = k = len(sel)
+            sp = ctypes.c_void_p(sel.ctypes.data) if k else ctypes.c_void_p(cut.ctypes.data)
+        if len(cut) != want:
+            raise ValueError("one cutoff per selected stream: %d for %d" % (len(cut), want))
+        n = ctypes.c_int64(0)
+        self._chk(self.lib.adsb_stream_planes_expire(self._h, sp, k, ctypes.c_void_p(cut.ctypes.data) if len(cut) else None,
+                                                     ctypes.byref(n)))
+        return n.value
+
+    def stream_planes(self, streams=None, cap=None, seen=False):
         """FLAG_STREAM_DECODE contexts: a snapshot of the streams' plane tables (adsb_stream_planes) -> (rows, first): rows
         ordered by (stream, address), first[i]:first[i + 1] those of the i-th selected stream.  streams: strictly ascending
-        stream indices, None: all of them.  cap: the first buffer's rows (None: stream_decoder_stats' plane count)."""
+        stream indices, None: all of them.  cap: the first buffer's rows (None: stream_decoder_stats' plane count).
+        seen (FLAG_PLANE_AGES contexts; adsb_stream_planes_seen): (rows, last_seen, first)."""
         if streams is None:
             sel, k = None, 0
             first = np.zeros(self._n_streams() + 1, dtype=np.int32)
@@ -364,8 +405,12 @@ class Context:
             k = len(sel)
             first = np.zeros(k + 1, dtype=np.int32)
         sp = None if sel is None else ctypes.c_void_p(sel.ctypes.data) if k else ctypes.c_void_p(first.ctypes.data)
-        rows = self._snapshot(lambda r, c_, n: self.lib.adsb_stream_planes(self._h, sp, k, r, c_, ctypes.c_void_p(first.ctypes.data), n),
-                              self.stream_decoder_stats()[0] if cap is None else cap)
+        fp = ctypes.c_void_p(first.ctypes.data)
+        cap = self.stream_decoder_stats()[0] if cap is None else cap
+        if seen:
+            rows, ages = self._snapshot(lambda r, a, c_, n: self.lib.adsb_stream_planes_seen(self._h, sp, k, r, a, c_, fp, n), cap, True)
+            return rows, ages, first
+        rows = self._snapshot(lambda r, c_, n: self.lib.adsb_stream_planes(self._h, sp, k, r, c_, fp, n), cap)
         return rows, first
 
     def _n_streams(self):
@@ -995,11 +1040,12 @@ def check_stream_selection(streams, n_streams):
         raise ValueError("stream indices have to be strictly ascending: %r" % (sel,))
 
 
-def plane_entry(row):
+def plane_entry(row, last_seen=None):
     """One snapshot row (Context.planes / stream_planes) -> the reference's plane_dict entry (decoder.py:413-449) without
     "cpr" and "last_seen": callsign (None or str), altitude, speed, heading, vertical_rate, latitude, longitude, num_msgs,
     with decoded_pdu's conversions and Python types (speed and heading with NumPy from the integer components, NaN where the
-    plane has no value)."""
+    plane has no value).  last_seen (planes(seen=True)): the entry's "last_seen" too, an int behind num_msgs as the
+    reference has it."""
     pr = int(row["present"])
     nan = float("nan")
     d = {"callsign": bytes(row["callsign"]).rstrip(b"\0").decode() if pr & DEC_HAS_CALLSIGN else None,
@@ -1014,6 +1060,8 @@ def plane_entry(row):
     d["latitude"] = float(row["latitude"])
     d["longitude"] = float(row["longitude"])
     d["num_msgs"] = int(row["num_msgs"])
+    if last_seen is not None:
+        d["last_seen"] = int(last_seen)
     return d
 
 

@@ -8,6 +8,7 @@ gr.sync_block; without it they subclass grshim.sync_block so tests can drive the
 """
 import collections
 import datetime
+import math
 import threading
 
 import numpy as np
@@ -600,9 +601,14 @@ class decoder(gr.sync_block):
     A PDU on which the reference raises (DF 18 CF 2/3/5, TC 19 ST 0/5/6/7: decode_packet raises before it publishes) is
     counted in `self.raised` and publishes nothing.  print_level: any value is accepted, nothing is printed (no curses
     screen and no log lines; plane_table() returns the "Brief" table's text).  error_corr "Brute Force" behaves as "None",
-    like the reference's branch."""
+    like the reference's branch.
 
-    def __init__(self, msg_filter, error_corr, print_level="None", device=0):
+    plane_timeout (seconds; None, the default: planes stay for ever, as in the reference as it stands): in front of every
+    handled PDU the planes with last_seen < int(timestamp) - plane_timeout are removed, as the sweep the reference carries
+    commented out would (decoder.py:435-439 `del self.plane_dict[key]`, on the device: adsb_planes_expire), and plane_dict's
+    entries carry "last_seen"."""
+
+    def __init__(self, msg_filter, error_corr, print_level="None", device=0, plane_timeout=None):
         if error_corr not in _ERROR_CORR:
             raise ValueError("error_corr must be one of %s, not %r" % (", ".join(_ERROR_CORR), error_corr))
         if msg_filter not in _MSG_FILTER:
@@ -610,9 +616,12 @@ class decoder(gr.sync_block):
         gr.sync_block.__init__(self, name="ADS-B Decoder", in_sig=None, out_sig=None)
         self.msg_filter, self.error_corr, self.print_level = msg_filter, error_corr, print_level
         self.raised = 0
+        self.plane_timeout = plane_timeout
         fl = _native.FLAG_AIRCRAFT_TABLE | _native.FLAG_DECODE
         if error_corr == "Conservative":
             fl |= _native.FLAG_FEC_CONSERVATIVE
+        if plane_timeout is not None:
+            fl |= _native.FLAG_PLANE_AGES
         # any valid rate: the context only decodes PDUs that were published already (adsb_decode_pdus)
         self._ctx = _native.Context(2e6, 0.0, device=device, flags=fl)
         self._ctx.set_decoder(msg_filter, 0.0)
@@ -626,9 +635,17 @@ class decoder(gr.sync_block):
         self.decode_pdus([pdu])
 
     def decode_pdus(self, pdus):
-        """Several PDUs (meta . u8vector of 112 bits) in one device call, published in order."""
+        """Several PDUs (meta . u8vector of 112 bits) in one device call, published in order.  With plane_timeout every PDU is
+        a call of its own behind its sweep."""
         if not pdus:
             return
+        if self.plane_timeout is not None and len(pdus) > 1:
+            for p in pdus:
+                self.decode_pdus([p])
+            return
+        if self.plane_timeout is not None:
+            # (last_seen is whole seconds: last_seen < x iff last_seen < ceil(x))
+            self._ctx.expire_planes(math.ceil(int(pmt.to_python(pmt.car(pdus[0]))["timestamp"]) - self.plane_timeout))
         metas = [pmt.to_python(pmt.car(p)) for p in pdus]
         bits = np.array([np.packbits(np.asarray(pmt.to_python(pmt.cdr(p)), dtype=np.uint8)[:112]) for p in pdus], dtype=np.uint8)
         rows = self._ctx.decode_pdus(bits, np.array([m["timestamp"] for m in metas], dtype=np.float64))
@@ -646,7 +663,10 @@ class decoder(gr.sync_block):
         """The reference's plane_dict (decoder.py:413-449) from a fresh snapshot of the device's table (adsb_planes):
         {"%06x" % icao: _native.plane_entry(row)}.  Read-only -- a new dict every time, nothing written to it reaches the
         decoder.  Two deviations from the reference's attribute: the keys come in ascending address order, not in the order
-        the aircraft were first heard, and an entry has no "cpr" and no "last_seen"."""
+        the aircraft were first heard, and an entry has no "cpr" and, unless the block has a plane_timeout, no "last_seen"."""
+        if self.plane_timeout is not None:
+            rows, seen = self._ctx.planes(seen=True)
+            return {"{:06x}".format(int(r["icao"])): _native.plane_entry(r, t) for r, t in zip(rows, seen)}
         return {"{:06x}".format(int(r["icao"])): _native.plane_entry(r) for r in self._ctx.planes()}
 
     def plane_table(self, timestamp):

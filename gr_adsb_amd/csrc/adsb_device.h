@@ -2542,7 +2542,7 @@ struct DecRow {
   unsigned num_msgs, pad2;
 };
 static_assert(sizeof(DecRow) == 72, "adsb_decoded is 72 bytes");
-// plane_dict[address] without last_seen (never read back): one dense entry per 24-bit address, valid iff epoch matches
+// plane_dict[address] without last_seen (kept beside it, DecArgs::seen): one dense entry per 24-bit address, valid iff epoch matches
 // (named fields, no arrays: the fold keeps an entry in registers)
 struct Plane {
   unsigned epoch, num_msgs, present;
@@ -2565,6 +2565,7 @@ struct DecArgs {
   unsigned long long* keys;  // [cap]: address << 32 | position, kDecNoKey
   const unsigned long long* sorted;
   DecRow* rows;              // [cap]
+  long long* seen;           // ADSB_FLAG_PLANE_AGES: 2^24 last_seen clocks beside the planes (k_ages_fold); null: none kept
 };
 
 __device__ __forceinline__ unsigned dec_field(unsigned long long a, unsigned long long b, int lo, int n) {
@@ -2775,8 +2776,12 @@ __device__ __forceinline__ bool dec_apply(Plane& p, const DecClass& c, double ts
   return fresh;
 }
 
-// Stage 3, one lane per address segment of the sorted keys: the plane's events in list order, a row after each
-__global__ void __launch_bounds__(kThreads) k_dec_fold(DecArgs d) {
+// Stage 3, one lane per address segment of the sorted keys: the plane's events in list order, a row after each.  AGES
+// (ADSB_FLAG_PLANE_AGES: k_ages_fold, d.seen set): the segment's last event also leaves its clock in d.seen -- an instance
+// of its own, so that k_dec_fold is the code it was (the loop has no scalar register to spare: k_ages_fold parks the pointer's
+// two in a vector register's lanes outside the loop -- two SGPR spills, no scratch).
+template <bool AGES>
+__device__ __forceinline__ void dec_fold_body(const DecArgs& d) {
   if (dec_skip(d)) return;
   for (int i = (int)(blockIdx.x * kThreads + threadIdx.x); i < d.air.cap; i += (int)(gridDim.x * kThreads)) {
     const unsigned long long k0 = d.sorted[i];
@@ -2786,6 +2791,7 @@ __global__ void __launch_bounds__(kThreads) k_dec_fold(DecArgs d) {
     Plane p = d.planes[addr];
     if (p.epoch != d.epoch) p.present = 0;
     bool dirty = false;
+    double seen = 0;            // update_plane's last_seen = int(time.time()): the clock of the segment's last event
     for (int j = i; j < d.air.cap; ++j) {
       const unsigned long long k = d.sorted[j];
       if (k == kDecNoKey || (unsigned)(k >> 32) != addr) break;
@@ -2797,13 +2803,19 @@ __global__ void __launch_bounds__(kThreads) k_dec_fold(DecArgs d) {
       unsigned port = c.port;
       if (c.ev > kEvSnap) {
         dirty = true;
+        if (AGES) seen = ts;
         dec_apply(p, c, ts, d.epoch, port);
       }
       dec_row(&d.rows[t], c, port, (p.present & kHasPlane) ? &p : nullptr);
     }
-    if (dirty) d.planes[addr] = p;
+    if (dirty) {
+      d.planes[addr] = p;
+      if (AGES) d.seen[addr] = (long long)seen;
+    }
   }
 }
+__global__ void __launch_bounds__(kThreads) k_dec_fold(DecArgs d) { dec_fold_body<false>(d); }
+__global__ void __launch_bounds__(kThreads) k_ages_fold(DecArgs d) { dec_fold_body<true>(d); }
 
 // adsb_decode_pdus: the ok[] bytes of already-published PDUs (kDemod | the parity pre-filter bits), as k_slice sets them
 __global__ void __launch_bounds__(kThreads) k_dec_pdu_flags(const unsigned char* bits14, unsigned char* ok, int n) {
@@ -2925,6 +2937,7 @@ struct FleetArgs {
   const unsigned long long* sorted;
   double* ts;                // [n]: the PDU timestamps of the records that have a key (k_fleet_classify)
   DecRow* rows;              // [n]
+  long long* seen;           // ADSB_FLAG_PLANE_AGES: [cap] last_seen clocks beside the store's slots; null: none kept
 };
 
 __device__ __forceinline__ unsigned fleet_hash(unsigned long long k) {
@@ -3058,6 +3071,7 @@ __global__ void __launch_bounds__(kThreads) k_fleet_fold(FleetArgs a) {
   if (i > 0 && (unsigned)(a.sorted[i - 1] >> 32) == h) return;
   Plane p = a.s.planes[h];
   bool dirty = false, fresh = false;
+  double seen = 0;
   for (int j = i; j < a.n; ++j) {
     const unsigned long long k = a.sorted[j];
     if (k == kDecNoKey || (unsigned)(k >> 32) != h) break;
@@ -3066,11 +3080,15 @@ __global__ void __launch_bounds__(kThreads) k_fleet_fold(FleetArgs a) {
     unsigned port = c.port;
     if (c.ev > kEvSnap) {
       dirty = true;
+      seen = a.ts[t];
       fresh |= dec_apply(p, c, a.ts[t], 0u, port);
     }
     dec_row(&a.rows[t], c, port, (p.present & kHasPlane) ? &p : nullptr);
   }
-  if (dirty) a.s.planes[h] = p;
+  if (dirty) {
+    a.s.planes[h] = p;
+    if (a.seen) a.seen[h] = (long long)seen;
+  }
   if (fresh) atomicAdd(&a.count[fleet_item_of(a, (int)(unsigned)k0)].planes, 1);      // (a slot's records are one stream's)
 }
 
@@ -3227,6 +3245,145 @@ __global__ void __launch_bounds__(kThreads) k_planes_store_emit(PlanesFleet a, c
     const unsigned h = fleet_slot(a.s, ((unsigned long long)a.gen[stream] << (kFleetAddrBits + kFleetStreamBits)) | key, false, &claimed);
     if (h == kFleetNone) { ADSB_AIR_STORE(error, 1); continue; }
     planes_row(rows, n, (unsigned)j, &a.s.planes[h], (unsigned)key & ((1u << kFleetAddrBits) - 1u));
+  }
+  for (int i = t0; first && i <= n_sel; i += step) {
+    int lo = 0, hi = n;
+    if (i < n_sel) {
+      const unsigned long long want = (unsigned long long)(unsigned)(sel ? sel[i] : i) << kFleetAddrBits;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sorted[mid] < want) lo = mid + 1; else hi = mid;
+      }
+    } else lo = n;
+    first[i] = lo;
+  }
+}
+
+// ---- plane ages (ADSB_FLAG_PLANE_AGES): last_seen read back, and expiry by last-seen age --------------------------------------
+// update_plane sets last_seen = int(time.time()) (decoder.py:424,433); the folds above keep that clock, per address or per
+// slot, in an int64 array BESIDE the planes (Plane and the 104-byte slot keep their layout).  An entry is written by the fold
+// that creates its plane and read only where a plane is live, so it is never cleared.  Expiry is the sweep the decoder
+// carries commented out (decoder.py:435-439), `del self.plane_dict[key]` for every plane with last_seen < cutoff: the plane
+// is gone AND its address is announced no longer, so an address/parity reply to it is unknown until a later reply announces
+// it, and that reply's update_plane starts a new entry.  An announced address without a plane (the snapshot comment above)
+// has no last_seen and is left alone.  The host runs these behind the last table / decode step, never beside one.
+//
+// One decoder: one scan in k_planes_tally's access pattern.  A stale plane's first-announcement key becomes kAirEmpty and its
+// entry's epoch 0 (no decoder has epoch 0: no plane); removed: one atomic per wavefront that removed any.
+struct PlanesExpire {
+  unsigned long long* table;               // indexed by address
+  Plane* planes;
+  const long long* seen;
+  unsigned epoch;
+  unsigned lo, hi;                         // as PlanesDense
+  long long cutoff;
+};
+__device__ __forceinline__ bool planes_stale(const PlanesExpire& a, unsigned long long key, unsigned addr) {
+  if (key == kAirEmpty) return false;
+  const Plane* p = &a.planes[addr];
+  return p->epoch == a.epoch && (p->present & kHasPlane) != 0 && a.seen[addr] < a.cutoff;
+}
+__global__ void __launch_bounds__(kThreads) k_ages_expire(PlanesExpire a, unsigned long long* removed) {
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const unsigned n_chunks = (a.hi - a.lo + kPlanesChunk - 1u) / kPlanesChunk;
+  for (unsigned c = blockIdx.x * kWaves + (unsigned)wave; c < n_chunks; c += gridDim.x * kWaves) {
+    unsigned n = 0;
+    for (int r = 0; r < kPlanesChunk / kPlanesStep; ++r) {
+      const unsigned addr = a.lo + c * kPlanesChunk + (unsigned)(r * kPlanesStep + 2 * lane);
+      if (addr < a.hi) {
+        const stream_v16 k = *reinterpret_cast<const stream_v16*>(&a.table[addr]);
+        for (unsigned q = 0; q < 2u; ++q)
+          if (planes_stale(a, k[q], addr + q)) {
+            a.table[addr + q] = kAirEmpty;
+            a.planes[addr + q].epoch = 0u;
+            ++n;
+          }
+      }
+    }
+    for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o);
+    if (lane == 0 && n) atomicAdd(removed, (unsigned long long)n);
+  }
+}
+
+// k_planes_emit with the planes' last_seen: seen_out[j] belongs to rows[j]; either output may be null
+__global__ void __launch_bounds__(kThreads) k_ages_emit(PlanesDense a, const unsigned* base, int cap, DecRow* rows,
+                                                        const long long* seen, long long* seen_out) {
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const unsigned n_chunks = planes_chunks(a);
+  for (unsigned c = blockIdx.x * kWaves + (unsigned)wave; c < n_chunks; c += gridDim.x * kWaves) {
+    unsigned pos = base[c];
+    if (base[c + 1] == pos) continue;
+    for (int r = 0; r < kPlanesChunk / kPlanesStep; ++r) {
+      const unsigned addr = a.lo + c * kPlanesChunk + (unsigned)(r * kPlanesStep + 2 * lane);
+      bool l0 = false, l1 = false;
+      if (addr < a.hi) {
+        const stream_v16 k = *reinterpret_cast<const stream_v16*>(&a.table[addr]);
+        l0 = planes_live(a, k[0], addr);
+        l1 = planes_live(a, k[1], addr + 1u);
+      }
+      const unsigned long long m0 = __ballot(l0), m1 = __ballot(l1);
+      const unsigned j0 = pos + (unsigned)__popcll(m0 & lt) + (unsigned)__popcll(m1 & lt), j1 = j0 + (l0 ? 1u : 0u);
+      if (l0) {
+        if (rows) planes_row(rows, cap, j0, &a.planes[addr], addr);
+        if (seen_out && j0 < (unsigned)cap) seen_out[j0] = seen[addr];
+      }
+      if (l1) {
+        if (rows) planes_row(rows, cap, j1, &a.planes[addr + 1u], addr + 1u);
+        if (seen_out && j1 < (unsigned)cap) seen_out[j1] = seen[addr + 1u];
+      }
+      pos += (unsigned)__popcll(m0) + (unsigned)__popcll(m1);
+    }
+  }
+}
+
+// The fleet: open addressing with linear probing cannot delete in place, so expiry is k_fleet_rehash with a predicate, into
+// an empty store of the SAME size; a flagged context's growth / purge / renumbering rehash is the same kernel without
+// cutoffs, so that last_seen moves with its slot.  cutoffs[stream] (LLONG_MIN where a stream is not selected: nothing is
+// below it); a dropped slot is counted in removed[stream] (slots and planes: one each), which the host takes off the stream's
+// books.  A reset stream's stale slots are dropped as in every rehash.
+struct FleetAges {
+  const long long* from_seen;              // [from.mask + 1]
+  long long* to_seen;                      // [to.mask + 1]
+  const long long* cutoffs;                // [n_streams]; null: no expiry
+  FleetCount* removed;                     // [n_streams], zero before; null iff cutoffs is
+};
+__global__ void __launch_bounds__(kThreads) k_ages_rehash(FleetStore from, FleetStore to, const unsigned* gen, int n_streams,
+                                                          int renumber, int* error, FleetAges g) {
+  for (unsigned i = blockIdx.x * kThreads + threadIdx.x; i <= from.mask; i += gridDim.x * kThreads) {
+    const unsigned long long key = from.keys[i];
+    if (key == kFleetEmpty) continue;
+    const unsigned stream = (unsigned)(key >> kFleetAddrBits) & ((1u << kFleetStreamBits) - 1u);
+    if (stream >= (unsigned)n_streams || gen[stream] != (unsigned)(key >> (kFleetAddrBits + kFleetStreamBits))) continue;
+    const bool plane = (from.planes[i].present & kHasPlane) != 0;
+    if (plane && g.cutoffs && g.from_seen[i] < g.cutoffs[stream]) {
+      atomicAdd(&g.removed[stream].slots, 1);
+      atomicAdd(&g.removed[stream].planes, 1);
+      continue;
+    }
+    bool claimed = false;
+    const unsigned h = fleet_slot(to, key, true, &claimed);
+    if (h == kFleetNone || !claimed) { ADSB_AIR_STORE(error, 1); continue; }
+    const unsigned long long ann = from.ann[i];
+    to.ann[h] = (renumber && ann != kAirEmpty) ? 0ull : ann;
+    to.planes[h] = from.planes[i];
+    if (plane) g.to_seen[h] = g.from_seen[i];
+  }
+}
+
+// k_planes_store_emit with the planes' last_seen (seen: beside the store's slots); rows or seen_out may be null
+__global__ void __launch_bounds__(kThreads) k_ages_store_emit(PlanesFleet a, const unsigned long long* sorted, int n,
+                                                              const int* sel, int n_sel, DecRow* rows, int* first, int* error,
+                                                              const long long* seen, long long* seen_out) {
+  const int t0 = (int)(blockIdx.x * kThreads + threadIdx.x), step = (int)(gridDim.x * kThreads);
+  for (int j = t0; j < n; j += step) {
+    const unsigned long long key = sorted[j];
+    const unsigned stream = (unsigned)(key >> kFleetAddrBits);
+    bool claimed = false;
+    const unsigned h = fleet_slot(a.s, ((unsigned long long)a.gen[stream] << (kFleetAddrBits + kFleetStreamBits)) | key, false, &claimed);
+    if (h == kFleetNone) { ADSB_AIR_STORE(error, 1); continue; }
+    if (rows) planes_row(rows, n, (unsigned)j, &a.s.planes[h], (unsigned)key & ((1u << kFleetAddrBits) - 1u));
+    if (seen_out) seen_out[j] = seen[h];
   }
   for (int i = t0; first && i <= n_sel; i += step) {
     int lo = 0, hi = n;

@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -304,7 +305,8 @@ struct FleetDec {
   long long used = 0;                           // slots taken since the store was built (those of reset streams included)
   long long live_slots = 0, live_planes = 0, grows = 0;
   unsigned long long call = 0;                  // number of the next delivered call with records (ordering keys: number << 32 | position)
-  DevBuf d_store;                               // keys[cap] | ann[cap] | planes[cap]
+  DevBuf d_store;                               // keys[cap] | ann[cap] | planes[cap] (| last_seen[cap]: ADSB_FLAG_PLANE_AGES)
+  DevBuf d_ages;                                // adsb_stream_planes_expire: cutoffs[n_streams] | removed[n_streams]; _seen: last_seen[n]
   DevBuf d_recs, d_items, d_cnt, d_keys, d_sorted, d_tmp, d_ts, d_rows, d_gen;
   DevBuf d_snap;                                // adsb_stream_planes: generations | selection bitmap | selection list | first[] | count, error
   PinnedBuf h_recs, h_rows, h_items, h_cnt;
@@ -469,6 +471,8 @@ struct adsb_ctx {
   DevBuf d_dec_keys, d_dec_sorted, d_dec_tmp;
   PinnedBuf h_pdu;                    // adsb_decode_pdus' staging (device-visible)
   DevBuf d_snap_cnt, d_snap_rows;     // adsb_planes: the chunks' counts / first rows, and the snapshot's rows
+  DevPtr<long long> d_seen;           // ADSB_FLAG_PLANE_AGES: 2^24 last_seen clocks beside d_planes (adsb_device.h: plane ages)
+  DevBuf d_snap_seen;                 // adsb_planes_seen: the snapshot's last_seen
   BatchBufs bt;                       // adsb_process_batch*
   StreamBufs sb;                      // adsb_process_stream_batch*
   FleetDec fd;                        // ... and their decoders (ADSB_FLAG_STREAM_DECODE)
@@ -711,7 +715,7 @@ int launch_dec(adsb_ctx* c, hipStream_t st, const AirArgs& a, unsigned g, DecRow
   }
   DecArgs d{};
   d.air = a; d.ts = ts; d.start = c->dec_start; d.fs = c->fs; d.planes = c->d_planes; d.epoch = c->dec_epoch; d.all = c->dec_all;
-  d.keys = (unsigned long long*)c->d_dec_keys.p; d.sorted = (const unsigned long long*)c->d_dec_sorted.p; d.rows = rows;
+  d.keys = (unsigned long long*)c->d_dec_keys.p; d.sorted = (const unsigned long long*)c->d_dec_sorted.p; d.rows = rows; d.seen = c->d_seen;
   hipLaunchKernelGGL(k_dec_classify, dim3(g), dim3(kThreads), 0, st, d);
   unsigned long long* in = (unsigned long long*)c->d_dec_keys.p;
   unsigned long long* out = (unsigned long long*)c->d_dec_sorted.p;
@@ -723,7 +727,8 @@ int launch_dec(adsb_ctx* c, hipStream_t st, const AirArgs& a, unsigned g, DecRow
                        (const unsigned*)c->d_dec_tmp.p);
     unsigned long long* x = in; in = out; out = x;
   }
-  hipLaunchKernelGGL(k_dec_fold, dim3(g), dim3(kThreads), 0, st, d);
+  if (d.seen) hipLaunchKernelGGL(k_ages_fold, dim3(g), dim3(kThreads), 0, st, d);
+  else hipLaunchKernelGGL(k_dec_fold, dim3(g), dim3(kThreads), 0, st, d);
   return 0;
 }
 
@@ -1583,8 +1588,12 @@ FleetStore fleet_view(void* p, long long cap) {
   return v;
 }
 // an empty store of cap slots (a power of two), ready behind what is queued on the context's stream
+// the last_seen clocks behind the planes of a flagged context's store; null without the flag
+long long* fleet_seen(const adsb_ctx* c, void* p, long long cap) {
+  return (c->flags & ADSB_FLAG_PLANE_AGES) ? (long long*)((char*)p + (size_t)cap * kFleetSlotBytes) : nullptr;
+}
 int fleet_new_store(adsb_ctx* c, DevBuf& b, long long cap) {
-  const size_t bytes = (size_t)cap * kFleetSlotBytes;
+  const size_t bytes = (size_t)cap * (kFleetSlotBytes + ((c->flags & ADSB_FLAG_PLANE_AGES) ? sizeof(long long) : 0));
   if (hipMalloc(&b.p, bytes) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return fail(c, -ENOMEM, "stream decoders: no device memory for the store"); }
   b.cap = bytes;
   HIPCHK(c, hipMemsetAsync(b.p, 0xFF, (size_t)cap * 16, c->stream));
@@ -1600,25 +1609,51 @@ int fleet_take_store(adsb_ctx* c, DevBuf& fresh, long long cap) {
   return 0;
 }
 // The live slots into a store of new_cap slots (growth, or the purge of a stream whose generations are used up): blocking.
-int fleet_rehash(adsb_ctx* c, long long new_cap, bool renumber = false) {
+// ADSB_FLAG_PLANE_AGES: k_ages_rehash, which moves last_seen with its slot; cutoffs ([n_streams], LLONG_MIN: keep all):
+// adsb_stream_planes_expire's predicate, the dropped planes taken off the streams' books and counted in *n_removed.
+int fleet_rehash(adsb_ctx* c, long long new_cap, bool renumber = false, const long long* cutoffs = nullptr, long long* n_removed = nullptr) {
   FleetDec& F = c->fd;
   const hipStream_t st = c->stream;
   const size_t ns = F.gen.size();
   int r;
   DevBuf fresh;
   if ((r = ensure(c, F.d_gen, ns * sizeof(unsigned) + sizeof(int)))) return r;
+  if (cutoffs && (r = ensure(c, F.d_ages, ns * (sizeof(long long) + sizeof(FleetCount))))) return r;
   if ((r = fleet_new_store(c, fresh, new_cap))) return r;
   int* const d_err = (int*)((unsigned*)F.d_gen.p + ns);
   HIPCHK(c, hipMemcpyAsync(F.d_gen.p, F.gen.data(), ns * sizeof(unsigned), hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemsetAsync(d_err, 0, sizeof(int), st));
-  hipLaunchKernelGGL(k_fleet_rehash, dim3(step_grid(F.cap, kThreads)), dim3(kThreads), 0, st, fleet_view(F.d_store.p, F.cap),
-                     fleet_view(fresh.p, new_cap), (const unsigned*)F.d_gen.p, (int)ns, renumber ? 1 : 0, d_err);
-  HIPCHK(c, hipGetLastError());
+  std::vector<FleetCount> removed;
+  if (c->flags & ADSB_FLAG_PLANE_AGES) {
+    FleetAges g{};
+    g.from_seen = fleet_seen(c, F.d_store.p, F.cap); g.to_seen = fleet_seen(c, fresh.p, new_cap);
+    if (cutoffs) {
+      g.cutoffs = (const long long*)F.d_ages.p; g.removed = (FleetCount*)((long long*)F.d_ages.p + ns);
+      HIPCHK(c, hipMemcpyAsync(F.d_ages.p, cutoffs, ns * sizeof(long long), hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemsetAsync(g.removed, 0, ns * sizeof(FleetCount), st));
+      removed.resize(ns);
+    }
+    hipLaunchKernelGGL(k_ages_rehash, dim3(step_grid(F.cap, kThreads)), dim3(kThreads), 0, st, fleet_view(F.d_store.p, F.cap),
+                       fleet_view(fresh.p, new_cap), (const unsigned*)F.d_gen.p, (int)ns, renumber ? 1 : 0, d_err, g);
+    HIPCHK(c, hipGetLastError());
+    if (cutoffs) HIPCHK(c, hipMemcpyAsync(removed.data(), g.removed, ns * sizeof(FleetCount), hipMemcpyDeviceToHost, st));
+  } else {
+    hipLaunchKernelGGL(k_fleet_rehash, dim3(step_grid(F.cap, kThreads)), dim3(kThreads), 0, st, fleet_view(F.d_store.p, F.cap),
+                       fleet_view(fresh.p, new_cap), (const unsigned*)F.d_gen.p, (int)ns, renumber ? 1 : 0, d_err);
+    HIPCHK(c, hipGetLastError());
+  }
   int err = 0;
   HIPCHK(c, hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   if (err) return fail(c, -EIO, "stream decoders: the rehash step found the store inconsistent");
   if ((r = fleet_take_store(c, fresh, new_cap))) return r;
+  long long total = 0;
+  for (size_t s = 0; s < removed.size(); ++s) {
+    F.slots[s] -= removed[s].slots; F.planes[s] -= removed[s].planes;
+    F.live_slots -= removed[s].slots; F.live_planes -= removed[s].planes;
+    total += removed[s].planes;
+  }
+  if (n_removed) *n_removed = total;
   F.used = F.live_slots;
   if (renumber) F.call = 1;
   return 0;
@@ -1650,7 +1685,7 @@ int fleet_close(adsb_ctx* c) {
   FleetDec& F = c->fd;
   F.open = false; F.cap = 0; F.n_rows = 0;
   F.start.clear(); F.gen.clear(); F.slots.clear(); F.planes.clear();
-  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen, &F.d_snap}) HIPCHK(c, b->release());
+  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen, &F.d_snap, &F.d_ages}) HIPCHK(c, b->release());
   for (PinnedBuf* b : {&F.h_recs, &F.h_rows, &F.h_items, &F.h_cnt}) HIPCHK(c, b->release());
   return 0;
 }
@@ -1704,7 +1739,7 @@ int fleet_step(adsb_ctx* c, const adsb_stream_item* items, int32_t n_items, cons
   a.call = F.call << 32;
   a.fec = (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) ? 1 : 0; a.all = F.all; a.fs = c->fs;
   a.keys = (unsigned long long*)F.d_keys.p; a.sorted = (const unsigned long long*)F.d_sorted.p; a.rows = (DecRow*)F.d_rows.p;
-  a.ts = (double*)F.d_ts.p;
+  a.ts = (double*)F.d_ts.p; a.seen = fleet_seen(c, F.d_store.p, F.cap);
   const unsigned g = step_grid(n, kThreads);
   hipLaunchKernelGGL(k_fleet_announce, dim3(g), dim3(kThreads), 0, st, a);
   hipLaunchKernelGGL(k_fleet_verdict, dim3(g), dim3(kThreads), 0, st, a, 0);
@@ -2008,6 +2043,7 @@ float adsb_snr_db(float peak, float median) {
 int adsb_create(double fs, float threshold, int device, uint32_t flags, adsb_ctx** out) {
   if ((flags & ADSB_FLAG_DECODE) && !(flags & ADSB_FLAG_AIRCRAFT_TABLE)) return -EINVAL;   // the decode step follows the table's
   if ((flags & ADSB_FLAG_STREAM_DECODE) && (flags & (ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE | ADSB_FLAG_CONFIDENCE))) return -EINVAL;
+  if ((flags & ADSB_FLAG_PLANE_AGES) && !(flags & (ADSB_FLAG_DECODE | ADSB_FLAG_STREAM_DECODE))) return -EINVAL;   // no planes to age
   if (!out) return -EINVAL;
   *out = nullptr;
   if (!(fs > 0) || fmod(fs, 1e6) != 0.0) return -EINVAL;        // framer.py:44, demod.py:42
@@ -2060,6 +2096,10 @@ int adsb_create(double fs, float threshold, int device, uint32_t flags, adsb_ctx
     const size_t pb = ((size_t)1 << 24) * sizeof(Plane);
     if (hipMalloc((void**)&c->d_planes.p, pb) != hipSuccess) { (void)hipGetLastError(); adsb_destroy(c); return -ENOMEM; }
     if (hipMemsetAsync(c->d_planes, 0, pb, c->stream) != hipSuccess) { adsb_destroy(c); return -EIO; }
+    // last_seen: written by the fold that creates the plane, read only beside a live plane -- never cleared
+    if ((flags & ADSB_FLAG_PLANE_AGES) && hipMalloc((void**)&c->d_seen.p, ((size_t)1 << 24) * sizeof(long long)) != hipSuccess) {
+      (void)hipGetLastError(); adsb_destroy(c); return -ENOMEM;
+    }
   }
   if (flags & ADSB_FLAG_AIRCRAFT_TABLE) {
     if (hipMalloc((void**)&c->d_air.p, ((size_t)1 << 24) * sizeof(unsigned long long)) != hipSuccess ||
@@ -2519,14 +2559,17 @@ int adsb_decode_pdus(adsb_ctx* c, const uint8_t* bits14, const double* timestamp
 // ---- snapshots of the plane tables (include/adsb_hip.h PLANE SNAPSHOTS; adsb_device.h: the k_planes_* kernels) --------------
 // Both run on the context's stream behind the event of the last table / decode step and return when the rows are in the
 // caller's memory; they write no state of the decoders.
-static int planes_args(adsb_ctx* c, const adsb_decoded* rows, int32_t cap, const int32_t* n_out) {
+// ages: the _seen variant (rows or last_seen may be missing, not both; the context has ADSB_FLAG_PLANE_AGES)
+static int planes_args(adsb_ctx* c, const adsb_decoded* rows, int32_t cap, const int32_t* n_out, bool ages = false,
+                       const int64_t* last_seen = nullptr) {
   if (!c) return -EINVAL;
-  if (!n_out || cap < 0 || (cap > 0 && !rows)) return fail(c, -EINVAL, "plane snapshot: n_out, or rows for cap > 0, missing");
+  if (ages && !(c->flags & ADSB_FLAG_PLANE_AGES)) return fail(c, -EINVAL, "context created without ADSB_FLAG_PLANE_AGES");
+  if (!n_out || cap < 0 || (cap > 0 && !rows && !last_seen)) return fail(c, -EINVAL, "plane snapshot: n_out, or rows for cap > 0, missing");
   return 0;
 }
 
-int adsb_planes(adsb_ctx* c, adsb_decoded* rows, int32_t cap, int32_t* n_out) {
-  int rc = planes_args(c, rows, cap, n_out);
+static int planes_dense(adsb_ctx* c, adsb_decoded* rows, int64_t* last_seen, bool ages, int32_t cap, int32_t* n_out) {
+  int rc = planes_args(c, rows, cap, n_out, ages, last_seen);
   if (rc) return rc;
   if (!(c->flags & ADSB_FLAG_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_DECODE");
   if ((rc = require_idle(c, kCallPending))) return rc;
@@ -2548,17 +2591,55 @@ int adsb_planes(adsb_ctx* c, adsb_decoded* rows, int32_t cap, int32_t* n_out) {
   *n_out = (int32_t)total;
   if ((long long)total > (long long)cap) return fail(c, -ENOSPC, "adsb_planes: cap is smaller than the number of planes (*n_out)");
   if (total == 0) return 0;
-  if ((rc = ensure(c, c->d_snap_rows, (size_t)total * sizeof(DecRow)))) return rc;
-  hipLaunchKernelGGL(k_planes_emit, dim3(g), dim3(kThreads), 0, st, a, (const unsigned*)cnt, (int)total, (DecRow*)c->d_snap_rows.p);
+  if (rows && (rc = ensure(c, c->d_snap_rows, (size_t)total * sizeof(DecRow)))) return rc;
+  if (last_seen && (rc = ensure(c, c->d_snap_seen, (size_t)total * sizeof(long long)))) return rc;
+  if (!ages)
+    hipLaunchKernelGGL(k_planes_emit, dim3(g), dim3(kThreads), 0, st, a, (const unsigned*)cnt, (int)total, (DecRow*)c->d_snap_rows.p);
+  else
+    hipLaunchKernelGGL(k_ages_emit, dim3(g), dim3(kThreads), 0, st, a, (const unsigned*)cnt, (int)total,
+                       rows ? (DecRow*)c->d_snap_rows.p : (DecRow*)nullptr, (const long long*)c->d_seen.p,
+                       last_seen ? (long long*)c->d_snap_seen.p : (long long*)nullptr);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(rows, c->d_snap_rows.p, (size_t)total * sizeof(DecRow), hipMemcpyDeviceToHost, st));
+  if (rows) HIPCHK(c, hipMemcpyAsync(rows, c->d_snap_rows.p, (size_t)total * sizeof(DecRow), hipMemcpyDeviceToHost, st));
+  if (last_seen) HIPCHK(c, hipMemcpyAsync(last_seen, c->d_snap_seen.p, (size_t)total * sizeof(long long), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   return 0;
 }
 
-int adsb_stream_planes(adsb_ctx* c, const int32_t* streams, int32_t n_sel, adsb_decoded* rows, int32_t cap, int32_t* first,
-                       int32_t* n_out) {
-  int rc = planes_args(c, rows, cap, n_out);
+int adsb_planes(adsb_ctx* c, adsb_decoded* rows, int32_t cap, int32_t* n_out) { return planes_dense(c, rows, nullptr, false, cap, n_out); }
+int adsb_planes_seen(adsb_ctx* c, adsb_decoded* rows, int64_t* last_seen, int32_t cap, int32_t* n_out) {
+  return planes_dense(c, rows, last_seen, true, cap, n_out);
+}
+
+// del plane_dict[key] for every plane with last_seen < cutoff (adsb_device.h: plane ages), behind the last table / decode step
+int adsb_planes_expire(adsb_ctx* c, int64_t cutoff, int64_t* n_removed) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_DECODE");
+  if (!(c->flags & ADSB_FLAG_PLANE_AGES)) return fail(c, -EINVAL, "context created without ADSB_FLAG_PLANE_AGES");
+  int rc = require_idle(c, kCallPending);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = c->stream;
+  PlanesExpire a{};
+  a.table = c->d_air; a.planes = c->d_planes; a.seen = c->d_seen; a.epoch = c->dec_epoch; a.lo = 0u; a.hi = 1u << 24;
+  a.cutoff = (long long)cutoff;
+  const unsigned n_chunks = (a.hi - a.lo) / kPlanesChunk;
+  if ((rc = ensure(c, c->d_snap_cnt, ((size_t)n_chunks + 1) * sizeof(unsigned)))) return rc;
+  unsigned long long* const d_n = (unsigned long long*)c->d_snap_cnt.p;      // (the snapshot's counts: no snapshot is at work)
+  HIPCHK(c, hipStreamWaitEvent(st, c->air_ev, 0));
+  HIPCHK(c, hipMemsetAsync(d_n, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_ages_expire, dim3(step_grid(n_chunks, kWaves)), dim3(kThreads), 0, st, a, d_n);
+  HIPCHK(c, hipGetLastError());
+  unsigned long long n = 0;
+  HIPCHK(c, hipMemcpyAsync(&n, d_n, sizeof(n), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (n_removed) *n_removed = (int64_t)n;
+  return 0;
+}
+
+static int planes_fleet(adsb_ctx* c, const int32_t* streams, int32_t n_sel, adsb_decoded* rows, int64_t* last_seen, bool ages,
+                        int32_t cap, int32_t* first, int32_t* n_out) {
+  int rc = planes_args(c, rows, cap, n_out, ages, last_seen);
   if (rc) return rc;
   if (!(c->flags & ADSB_FLAG_STREAM_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE");
   FleetDec& F = c->fd;
@@ -2605,7 +2686,9 @@ int adsb_stream_planes(adsb_ctx* c, const int32_t* streams, int32_t n_sel, adsb_
     return 0;
   }
   const int nblk = (n + kSortTile - 1) / kSortTile;
-  if ((rc = ensure(c, F.d_tmp, (size_t)nblk * 16 * sizeof(unsigned))) || (rc = ensure(c, F.d_rows, (size_t)n * sizeof(DecRow)))) return rc;
+  if ((rc = ensure(c, F.d_tmp, (size_t)nblk * 16 * sizeof(unsigned))) || (rows && (rc = ensure(c, F.d_rows, (size_t)n * sizeof(DecRow)))) ||
+      (last_seen && (rc = ensure(c, F.d_ages, (size_t)n * sizeof(long long)))))
+    return rc;
   unsigned long long* in = (unsigned long long*)F.d_keys.p;
   unsigned long long* out = (unsigned long long*)F.d_sorted.p;
   for (int shift = 0; shift < kFleetAddrBits + kFleetStreamBits; shift += 4) {          // eleven passes: the result ends in d_sorted
@@ -2615,15 +2698,56 @@ int adsb_stream_planes(adsb_ctx* c, const int32_t* streams, int32_t n_sel, adsb_
                        (const unsigned*)F.d_tmp.p);
     unsigned long long* x = in; in = out; out = x;
   }
-  hipLaunchKernelGGL(k_planes_store_emit, dim3(step_grid(std::max((long long)n, (long long)nsel + 1), kThreads)), dim3(kThreads), 0, st, a,
-                     (const unsigned long long*)F.d_sorted.p, n, streams ? (const int*)(d + o_sel) : (const int*)nullptr, (int)n_sel,
-                     (DecRow*)F.d_rows.p, first ? (int*)(d + o_first) : (int*)nullptr, d_cnt + 1);
+  const unsigned eg = step_grid(std::max((long long)n, (long long)nsel + 1), kThreads);
+  if (!ages)
+    hipLaunchKernelGGL(k_planes_store_emit, dim3(eg), dim3(kThreads), 0, st, a,
+                       (const unsigned long long*)F.d_sorted.p, n, streams ? (const int*)(d + o_sel) : (const int*)nullptr, (int)n_sel,
+                       (DecRow*)F.d_rows.p, first ? (int*)(d + o_first) : (int*)nullptr, d_cnt + 1);
+  else
+    hipLaunchKernelGGL(k_ages_store_emit, dim3(eg), dim3(kThreads), 0, st, a,
+                       (const unsigned long long*)F.d_sorted.p, n, streams ? (const int*)(d + o_sel) : (const int*)nullptr, (int)n_sel,
+                       rows ? (DecRow*)F.d_rows.p : (DecRow*)nullptr, first ? (int*)(d + o_first) : (int*)nullptr, d_cnt + 1,
+                       (const long long*)fleet_seen(c, F.d_store.p, F.cap), last_seen ? (long long*)F.d_ages.p : (long long*)nullptr);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(rows, F.d_rows.p, (size_t)n * sizeof(DecRow), hipMemcpyDeviceToHost, st));
+  if (rows) HIPCHK(c, hipMemcpyAsync(rows, F.d_rows.p, (size_t)n * sizeof(DecRow), hipMemcpyDeviceToHost, st));
+  if (last_seen) HIPCHK(c, hipMemcpyAsync(last_seen, F.d_ages.p, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost, st));
   if (first) HIPCHK(c, hipMemcpyAsync(first, d + o_first, (nsel + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipMemcpyAsync(got, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   if (got[1]) return fail(c, -EIO, "stream decoders: the snapshot found a plane without a slot");
+  return 0;
+}
+
+int adsb_stream_planes(adsb_ctx* c, const int32_t* streams, int32_t n_sel, adsb_decoded* rows, int32_t cap, int32_t* first,
+                       int32_t* n_out) {
+  return planes_fleet(c, streams, n_sel, rows, nullptr, false, cap, first, n_out);
+}
+int adsb_stream_planes_seen(adsb_ctx* c, const int32_t* streams, int32_t n_sel, adsb_decoded* rows, int64_t* last_seen, int32_t cap,
+                            int32_t* first, int32_t* n_out) {
+  return planes_fleet(c, streams, n_sel, rows, last_seen, true, cap, first, n_out);
+}
+
+// The fleet's expiry: a rehash with a predicate into a store of the same size (adsb_device.h: plane ages)
+int adsb_stream_planes_expire(adsb_ctx* c, const int32_t* streams, int32_t n_sel, const int64_t* cutoffs, int64_t* n_removed) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE");
+  if (!(c->flags & ADSB_FLAG_PLANE_AGES)) return fail(c, -EINVAL, "context created without ADSB_FLAG_PLANE_AGES");
+  FleetDec& F = c->fd;
+  if (!F.open) return fail(c, -EINVAL, "adsb_stream_planes_expire: no streams (adsb_streams_open first)");
+  const size_t ns = F.gen.size();
+  if (!streams) n_sel = (int32_t)ns;
+  if (n_sel < 0 || (n_sel > 0 && !cutoffs)) return fail(c, -EINVAL, "adsb_stream_planes_expire: n_sel < 0, or cutoffs missing");
+  for (int32_t i = 0; streams && i < n_sel; ++i)
+    if (streams[i] < 0 || (size_t)streams[i] >= ns || (i > 0 && streams[i] <= streams[i - 1]))
+      return fail(c, -EINVAL, "adsb_stream_planes_expire: stream indices have to be in range and strictly ascending");
+  int rc = require_idle(c, kCallPending);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<long long> cut(ns, LLONG_MIN);                       // (nothing is below it: an unselected stream loses nothing)
+  for (int32_t i = 0; i < n_sel; ++i) cut[streams ? (size_t)streams[i] : (size_t)i] = (long long)cutoffs[i];
+  long long total = 0;
+  if ((rc = fleet_rehash(c, F.cap, false, cut.data(), &total))) return rc;
+  if (n_removed) *n_removed = (int64_t)total;
   return 0;
 }
 

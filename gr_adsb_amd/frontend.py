@@ -150,10 +150,11 @@ class FrontEnd:
         return self.ctx.last_batch_fallbacks
 
     # -- many receivers that go on: streams carried across batch calls -----------------------------------
-    def receivers(self, n, fmt=None, starts=None, msg_filter=None):
+    def receivers(self, n, fmt=None, starts=None, msg_filter=None, ages=False):
         """n receiver streams on this context (Receivers below).  fmt: one of _native.FMT_*, or None: by the arrays' dtype.
-        starts / msg_filter: FLAG_STREAM_DECODE contexts, the streams' start timestamps and their decoders' msg_filter."""
-        return Receivers(self.ctx, n, fmt, starts, msg_filter)
+        starts / msg_filter: FLAG_STREAM_DECODE contexts, the streams' start timestamps and their decoders' msg_filter.
+        ages: the context also has FLAG_PLANE_AGES (ValueError otherwise): .planes(seen=True) and .expire(cutoffs)."""
+        return Receivers(self.ctx, n, fmt, starts, msg_filter, ages)
 
     def shard_tensor(self, t, origin, own_lo, own_hi, stream_len, fmt=0, head_cands=0):
         _after_torch(self.ctx, t)
@@ -190,10 +191,13 @@ class Receivers:
     _native.decoded_pdu turns a row into the reference's published PDU).  starts: the streams' start timestamps (a record's
     PDU timestamp is start + offset / fs), msg_filter: "All Messages" (default) or "Extended Squitter Only"."""
 
-    def __init__(self, ctx, n, fmt=None, starts=None, msg_filter=None):
+    def __init__(self, ctx, n, fmt=None, starts=None, msg_filter=None, ages=False):
         self.ctx, self.n, self.fmt = ctx, int(n), fmt
         self.decode = bool(getattr(ctx, "flags", 0) & _native.FLAG_STREAM_DECODE)
+        self.ages = bool(ages)
         self.rows = []
+        if self.ages and not (self.decode and getattr(ctx, "flags", 0) & _native.FLAG_PLANE_AGES):
+            raise ValueError("ages needs a FLAG_STREAM_DECODE | FLAG_PLANE_AGES context")
         if not self.decode and (starts is not None or msg_filter is not None):      # (before any stream is opened)
             raise ValueError("starts / msg_filter need a FLAG_STREAM_DECODE context")
         ctx.open_streams(self.n)
@@ -240,14 +244,30 @@ class Receivers:
             self.rows = [rows.get(i, np.zeros(0, dtype=_native.DECODED_DTYPE)) for i in ids]
         return [out[i] for i in ids]
 
-    def planes(self, ids=None):
+    def planes(self, ids=None, seen=False):
         """FLAG_STREAM_DECODE contexts: what each receiver sees now -- a list of DECODED_DTYPE row arrays, one per stream of
         `ids` (strictly ascending; None: every stream), each in ascending address order, from one device snapshot of the
-        decoders' store (adsb_stream_planes; _native.plane_entry turns a row into the reference's plane_dict entry)."""
+        decoders' store (adsb_stream_planes; _native.plane_entry turns a row into the reference's plane_dict entry).
+        seen (receivers(ages=True)): a list of (rows, last_seen) pairs, last_seen the int64 clocks of the rows."""
         if not self.decode:
             raise ValueError("planes() needs a FLAG_STREAM_DECODE context")
+        if seen:
+            if not self.ages:
+                raise ValueError("planes(seen=True) needs receivers(ages=True)")
+            rows, ages, first = self.ctx.stream_planes(ids, seen=True)
+            return [(rows[first[i]:first[i + 1]], ages[first[i]:first[i + 1]]) for i in range(len(first) - 1)]
         rows, first = self.ctx.stream_planes(ids)
         return [rows[first[i]:first[i + 1]] for i in range(len(first) - 1)]
+
+    def expire(self, cutoffs, ids=None):
+        """receivers(ages=True): every stream of `ids` (strictly ascending; None: all) forgets its planes with
+        last_seen < its cutoff, as `del plane_dict[key]` (adsb_stream_planes_expire) -> the number removed.  cutoffs: one per
+        stream of `ids`, or a scalar for all of them (streams do not share a clock: a scalar suits equal start timestamps)."""
+        if not self.ages:
+            raise ValueError("expire() needs receivers(ages=True)")
+        k = self.n if ids is None else len(ids)
+        cut = np.full(k, int(cutoffs), dtype=np.int64) if np.ndim(cutoffs) == 0 else np.asarray(cutoffs, dtype=np.int64)
+        return self.ctx.expire_stream_planes(cut, ids)
 
     def state(self, i):
         """(pos, eob, n_overlong) of stream i"""

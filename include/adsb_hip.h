@@ -103,7 +103,7 @@ extern "C" {
  * slices with ok != 0) in order.  Every such record that the decoder would accept and that reaches update_plane announces
  * its address (adsb_mode_s_aircraft states the per-PDU rule); an AP reply is flagged ADSB_BURST_AP_KNOWN when its AA was
  * announced earlier.  The table lives as long as the context (128 MiB of device memory, allocated only with the flag):
- * adsb_reset clears it; addresses never time out, as in the decoder.  Applies to adsb_process_*, adsb_submit_* and
+ * adsb_reset clears it; addresses never time out, as in the decoder (unless the caller expires them: PLANE AGES).  Applies to adsb_process_*, adsb_submit_* and
  * adsb_demod_work; adsb_framer_work ignores it (its records are not what is published); the sharded entry points
  * (adsb_shard_*, adsb_submit_shard_device, adsb_process_sharded_*) return -EINVAL: their stitch decides publication after
  * the device has run.  Without the flag nothing is allocated or launched and no byte changes. */
@@ -131,6 +131,11 @@ extern "C" {
  * context without the flag (adsb_last_decoded, adsb_decode_pdus and adsb_set_decoder: -EINVAL).  Without the flag nothing
  * is allocated or launched and no byte changes. */
 #define ADSB_FLAG_STREAM_DECODE 1024u
+/* Opt-in, only together with ADSB_FLAG_DECODE or ADSB_FLAG_STREAM_DECODE (adsb_create: -EINVAL otherwise): the decoders keep
+ * plane_dict's last_seen on the device, so that planes can be read back with their age and expired by it -- see PLANE AGES
+ * below.  One int64 per address beside the planes of one decoder (2^24 entries, 128 MiB), one per slot beside a fleet's
+ * store.  Without the flag nothing is allocated or launched and no byte changes. */
+#define ADSB_FLAG_PLANE_AGES 2048u
 
 /* adsb_burst.flags */
 #define ADSB_BURST_DEMOD 1u /* eob inside the demod input: bits[] valid, a PDU is published (demod.py:82) */
@@ -525,7 +530,7 @@ int adsb_process_stream_batch_device(adsb_ctx* ctx, int format, const adsb_strea
  * is rehashed: the live slots move to a new store, the slots of reset streams are dropped, the old store is freed.  The new
  * store has the same size unless the LIVE slots plus the call's records would take more than half of it; then it is doubled
  * until they do not, which is a growth (counted: adsb_stream_decoder_stats).  A rehash changes no row.  The store never
- * shrinks.  Nothing runs out in a long-lived fleet: the call numbers that order announcements start over at a rehash
+ * shrinks (adsb_stream_planes_expire frees slots, not memory).  Nothing runs out in a long-lived fleet: the call numbers that order announcements start over at a rehash
  * before 2^32 calls are reached, with every announcement made so far kept as "earlier".
  * CONTRACT: for every stream s -- any chunking, any subset of streams per call, n == 0 and END items included -- the
  * concatenation of its records over all calls is byte-identical to what an ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE context
@@ -558,8 +563,8 @@ int adsb_stream_decoder_stats(adsb_ctx* ctx, int64_t* planes, int64_t* capacity,
  * A snapshot row is an adsb_decoded row: port = ADSB_DEC_NONE, df = 0, bits and every pad byte zero, icao = the address;
  * present (always with ADSB_DEC_HAS_PLANE), callsign, altitude, velocity_we, velocity_sn, vertical_rate, latitude, longitude
  * and num_msgs hold exactly what the row of a record that touches the plane would show at this moment.  The CPR frames
- * (plane_dict's "cpr") and last_seen are NOT part of a snapshot: the device keeps no last_seen, and print_planes
- * (decoder.py:452-509) prints neither.
+ * (plane_dict's "cpr") and last_seen are NOT part of a snapshot row (print_planes, decoder.py:452-509, prints neither);
+ * an ADSB_FLAG_PLANE_AGES context returns last_seen beside the rows: adsb_planes_seen, adsb_stream_planes_seen.
  * adsb_planes: every address whose plane exists in the context's current epoch, in ascending address order; nothing after
  * adsb_reset; an address that was announced but has no plane is not returned.
  * adsb_stream_planes: streams == NULL selects all n_streams streams (n_sel is ignored and counts as n_streams); otherwise
@@ -578,6 +583,36 @@ int adsb_stream_decoder_stats(adsb_ctx* ctx, int64_t* planes, int64_t* capacity,
 int adsb_planes(adsb_ctx* ctx, adsb_decoded* rows, int32_t cap, int32_t* n_out);
 int adsb_stream_planes(adsb_ctx* ctx, const int32_t* streams, int32_t n_sel, adsb_decoded* rows, int32_t cap, int32_t* first,
                        int32_t* n_out);
+/* PLANE AGES (ADSB_FLAG_PLANE_AGES): plane_dict's last_seen on the device, and expiry by it.  update_plane sets
+ * last_seen = int(time.time()) (decoder.py:424,433); with the decoder's clock of ADSB_FLAG_DECODE that is
+ * (long long)timestamp of the PDU, and last_seen moves exactly where num_msgs moves.  After a call a plane's last_seen is the
+ * clock of the last PDU of the call, in publication order, that reached update_plane for it -- the last one, not the
+ * largest: adsb_decode_pdus may be given timestamps that go backwards.
+ * adsb_planes_seen / adsb_stream_planes_seen are adsb_planes / adsb_stream_planes with one more output: last_seen[j] belongs
+ * to rows[j] (cap entries each).  Rows, order, first[], the -ENOSPC count query, -EBUSY, the ordering behind the last decode
+ * step and "changes no state" are those of the plain calls, byte for byte; rows or last_seen may be NULL when only the other
+ * is wanted.
+ * adsb_planes_expire / adsb_stream_planes_expire remove every plane with last_seen < cutoff: with cutoff = now - timeout the
+ * decoder's `now - last_seen > timeout` of print_planes (decoder.py:493, PLANE_TIMEOUT_S :259); last_seen == cutoff stays.
+ * Removal is `del self.plane_dict[key]`, the sweep the decoder carries commented out (decoder.py:435-439): the plane is gone,
+ * its address is announced no longer -- an address/parity reply to it is unknown again until a later reply announces it --
+ * and the next reply that reaches update_plane starts a new entry (num_msgs 1, no callsign, NaN altimetry, no CPR frames).
+ * CONTRACT: every record and row decoded after the call is byte-identical to what the reference decoder publishes after the
+ * same keys were deleted from its plane_dict at the same point of the publication order (snapshots and ADSB_BURST_AP_KNOWN /
+ * _AP_FEC included).  An address that is announced but holds no plane has no last_seen and is left alone.
+ * adsb_stream_planes_expire: streams / n_sel as for adsb_stream_planes; cutoffs[i] belongs to the i-th selected stream
+ * (streams do not share a clock); unselected streams lose nothing; adsb_stream_decoder_stats' planes stays exact.  The
+ * store is rehashed into one of the same size (linear probing cannot delete in place); a reset stream's stale slots are
+ * dropped in the same pass.  *n_removed (may be NULL) is the number of planes removed, of all selected streams together.
+ * All four: -EINVAL without the flag; -EBUSY while submitted tickets are pending; ordered behind the last queued table or
+ * decode step.  Expiry changes nothing but the removed planes: adsb_last_result, adsb_last_decoded,
+ * adsb_stream_last_decoded, framer and stream state are untouched, and a call that removes nothing changes no later byte.
+ * ADSB_ABI_VERSION is unchanged: a flag and entry points only. */
+int adsb_planes_seen(adsb_ctx* ctx, adsb_decoded* rows, int64_t* last_seen, int32_t cap, int32_t* n_out);
+int adsb_stream_planes_seen(adsb_ctx* ctx, const int32_t* streams, int32_t n_sel, adsb_decoded* rows, int64_t* last_seen,
+                            int32_t cap, int32_t* first, int32_t* n_out);
+int adsb_planes_expire(adsb_ctx* ctx, int64_t cutoff, int64_t* n_removed);
+int adsb_stream_planes_expire(adsb_ctx* ctx, const int32_t* streams, int32_t n_sel, const int64_t* cutoffs, int64_t* n_removed);
 /* Device memory on the context's device for callers that do not link HIP (a C or ctypes client of the *_device entry
  * points): hipMalloc / hipFree / a blocking hipMemcpy host -> device.  16-byte alignment is guaranteed.  No reference
  * counterpart (the reference never leaves host memory). */

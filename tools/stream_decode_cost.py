@@ -32,6 +32,7 @@ ap.add_argument("--log2n", type=int, default=16)
 ap.add_argument("--calls", type=int, default=16)
 ap.add_argument("--child", choices=["stream", "fleet", "pdus"], default=None)
 ap.add_argument("--lib", default=None)
+ap.add_argument("--extra-flags", type=int, default=0)      # child "fleet": more context flags (tools/expire_cost.py: 2048)
 ap.add_argument("--child-timeout", type=int, default=240)
 a = ap.parse_args()
 
@@ -60,7 +61,7 @@ def child():
     lib.adsb_streams_open.argtypes = [vp, i32]
     lib.adsb_stream_reset.argtypes = [vp, i32]
     h = vp()
-    assert lib.adsb_create(FS, THR, 0, FLAG_STREAM_DECODE if a.child == "fleet" else 0, c.byref(h)) == 0
+    assert lib.adsb_create(FS, THR, 0, (FLAG_STREAM_DECODE | a.extra_flags) if a.child == "fleet" else 0, c.byref(h)) == 0
     assert lib.adsb_set_format_scale(h, FMT_CU8, 2.0 / 255.0) == 0
     assert lib.adsb_streams_open(h, K) == 0
     hd = vp()
