@@ -62,6 +62,11 @@ BATCH_ITEM_MAX = 1 << 22     # ADSB_BATCH_ITEM_MAX: longer items take the ordina
 STREAM_ITEM_DTYPE = np.dtype([("data", "<u8"), ("n", "<i8"), ("stream", "<i4"), ("flags", "<u4"), ("threshold", "<f4"),
                               ("reserved", "<u4")])
 assert STREAM_ITEM_DTYPE.itemsize == 32
+# one entry of adsb_stream_planes_merged's info (adsb_merged): info[j] belongs to rows[j]
+MERGED_DTYPE = np.dtype([("last_seen", "<i8"), ("n_streams", "<i4"), ("src_callsign", "<i4"), ("src_altitude", "<i4"),
+                         ("src_velocity", "<i4"), ("src_position", "<i4"), ("pad", "<i4")])
+assert MERGED_DTYPE.itemsize == 32
+INT64_MIN = -(1 << 63)       # the cutoff that hides nothing
 STREAM_END = 1               # ADSB_STREAM_END: the stream's last item
 STREAM_FRESH_EOB = -(1 << 61)    # the carried end-of-burst offset of a fresh stream
 
@@ -80,6 +85,7 @@ EXPORTS = [
     "adsb_streams_set_decoder", "adsb_stream_set_start", "adsb_stream_last_decoded", "adsb_stream_decoder_reserve",
     "adsb_stream_decoder_stats", "adsb_planes", "adsb_stream_planes",
     "adsb_planes_seen", "adsb_stream_planes_seen", "adsb_planes_expire", "adsb_stream_planes_expire",
+    "adsb_stream_planes_merged",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
 ]
 
@@ -189,6 +195,7 @@ def load():
     lib.adsb_stream_planes_seen.argtypes = [vp, vp, i32, vp, vp, i32, vp, c.POINTER(i32)]
     lib.adsb_planes_expire.argtypes = [vp, c.c_int64, c.POINTER(c.c_int64)]
     lib.adsb_stream_planes_expire.argtypes = [vp, vp, i32, vp, c.POINTER(c.c_int64)]
+    lib.adsb_stream_planes_merged.argtypes = [vp, vp, i32, c.c_int64, vp, vp, i32, c.POINTER(i32)]
     lib.adsb_device_alloc.argtypes = [vp, c.POINTER(vp), c.c_size_t]
     lib.adsb_device_free.argtypes = [vp, vp]
     lib.adsb_device_upload.argtypes = [vp, vp, vp, c.c_size_t]
@@ -412,6 +419,35 @@ class Context:
             return rows, ages, first
         rows = self._snapshot(lambda r, c_, n: self.lib.adsb_stream_planes(self._h, sp, k, r, c_, fp, n), cap)
         return rows, first
+
+    def merged_planes(self, streams=None, cutoff=None, cap=None):
+        """FLAG_STREAM_DECODE | FLAG_PLANE_AGES contexts: the selected streams' plane tables folded into one
+        (adsb_stream_planes_merged) -> (rows, info): one DECODED_DTYPE row per aircraft in ascending address order and its
+        MERGED_DTYPE entry.  Per field group (callsign, altitude, velocity, position) the row shows the entry with the
+        greatest last_seen that has the group (ties: the lowest stream), info["src_*"] names that stream (-1: nobody has it);
+        num_msgs is the sum, info["last_seen"] the largest.  streams: strictly ascending indices, None: all.  cutoff: entries
+        with last_seen < cutoff are hidden (None: INT64_MIN, nothing is).  cap: the first buffer's rows (None: a count query
+        first)."""
+        if streams is None:
+            sel, k, sp = None, 0, None
+        else:
+            sel = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+            check_stream_selection(sel, self._n_streams())
+            k = len(sel)
+        cut = INT64_MIN if cutoff is None else int(cutoff)
+        n = ctypes.c_int32(0)
+        if sel is not None:                   # (an empty selection is still a selection: any non-null pointer)
+            sp = ctypes.c_void_p(sel.ctypes.data) if k else ctypes.c_void_p(ctypes.addressof(n))
+        cap = 0 if cap is None else max(int(cap), 0)
+        for _ in range(2):
+            rows, info = np.zeros(cap, dtype=DECODED_DTYPE), np.zeros(cap, dtype=MERGED_DTYPE)
+            rc = self.lib.adsb_stream_planes_merged(self._h, sp, k, cut, ctypes.c_void_p(rows.ctypes.data) if cap else None,
+                                                    ctypes.c_void_p(info.ctypes.data) if cap else None, cap, ctypes.byref(n))
+            if rc != -28:
+                break
+            cap = n.value
+        self._chk(rc)
+        return rows[:n.value], info[:n.value]
 
     def _n_streams(self):
         return getattr(self, "_streams_open", 0)

@@ -3398,6 +3398,114 @@ __global__ void __launch_bounds__(kThreads) k_ages_store_emit(PlanesFleet a, con
   }
 }
 
+// ---- the fleet's merged picture (adsb_stream_planes_merged): one row per aircraft out of every receiver's plane_dict ----------
+// Read-only, as the snapshots are.  A CONTRIBUTING entry is a live plane of a selected stream's current generation whose
+// last_seen is not below the cutoff.  k_merge_keys is k_planes_store_keys with that predicate and the 44-bit key turned
+// round, address << 20 | stream, so that the library's radix sort (eleven nibbles from bit 0) leaves an aircraft's entries
+// side by side, in ascending stream order.  Row j of the sorted keys is a HEAD when it is the first of its address;
+// k_merge_heads counts the heads of every 64 rows (one wavefront's ballot: no atomic, no LDS), k_dec_sort_scan turns the
+// counts into each 64 rows' first output row and, one entry behind the last, the total; k_merge_emit runs one lane per head:
+// it walks the segment, looks each entry's slot up again, and keeps per field group -- callsign, altitude, velocity, position
+// -- the values of the entry that has the group and the greatest last_seen (a strict >: a tie stays with the lowest stream).
+// last_seen is per plane, not per field: "the freshest entry that has the field", no claim about the field's own age.
+struct MergedInfo {                        // include/adsb_hip.h adsb_merged, byte for byte
+  long long last_seen;
+  int n_streams, src_callsign, src_altitude, src_velocity, src_position, pad;
+};
+static_assert(sizeof(MergedInfo) == 32, "adsb_merged is 32 bytes");
+constexpr int kMergeChunk = 64;            // sorted rows per head count: one wavefront
+__device__ __forceinline__ unsigned merge_addr(unsigned long long key) { return (unsigned)(key >> kFleetStreamBits); }
+__device__ __forceinline__ bool merge_head(const unsigned long long* sorted, int n, int j) {
+  return j < n && (j == 0 || merge_addr(sorted[j - 1]) != merge_addr(sorted[j]));
+}
+
+__global__ void __launch_bounds__(kThreads) k_merge_keys(PlanesFleet a, const long long* seen, long long cutoff,
+                                                         unsigned long long* keys, int cap, int* count) {
+  const int lane = (int)(threadIdx.x & 63);
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  for (unsigned w0 = blockIdx.x * kThreads + (threadIdx.x & ~63u); w0 <= a.s.mask; w0 += gridDim.x * kThreads) {
+    const unsigned i = w0 + (unsigned)lane;
+    const unsigned long long key = a.s.keys[i];
+    unsigned stream = 0;
+    bool keep = false;
+    if (key != kFleetEmpty) {
+      stream = (unsigned)(key >> kFleetAddrBits) & ((1u << kFleetStreamBits) - 1u);
+      keep = stream < (unsigned)a.n_streams && a.gen[stream] == (unsigned)(key >> (kFleetAddrBits + kFleetStreamBits)) &&
+             (!a.sel_bits || ((a.sel_bits[stream >> 5] >> (stream & 31u)) & 1u)) && (a.s.planes[i].present & kHasPlane) != 0 &&
+             seen[i] >= cutoff;
+    }
+    const unsigned long long m = __ballot(keep);
+    if (m == 0) continue;
+    int b0 = 0;
+    if (lane == 0) b0 = atomicAdd(count, __popcll(m));
+    b0 = __shfl(b0, 0);
+    const int j = b0 + __popcll(m & lt);
+    if (keep && j < cap)
+      keys[j] = ((key & ((1ull << kFleetAddrBits) - 1ull)) << kFleetStreamBits) | stream;
+  }
+}
+
+// counts[c] = the heads among rows 64 c .. 64 c + 63; counts[number of chunks] = 0 (the scan leaves the total there)
+__global__ void __launch_bounds__(kThreads) k_merge_heads(const unsigned long long* sorted, int n, unsigned* counts) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int n_chunks = (n + kMergeChunk - 1) / kMergeChunk;
+  if (blockIdx.x == 0 && threadIdx.x == 0) counts[n_chunks] = 0;
+  for (int w0 = (int)(blockIdx.x * kThreads + (threadIdx.x & ~63u)); w0 < n; w0 += (int)(gridDim.x * kThreads)) {
+    const unsigned long long m = __ballot(merge_head(sorted, n, w0 + lane));
+    if (lane == 0) counts[w0 / kMergeChunk] = (unsigned)__popcll(m);
+  }
+}
+
+// base = the scanned counts; rows / info: base[number of chunks] entries each, either may be null
+__global__ void __launch_bounds__(kThreads) k_merge_emit(PlanesFleet a, const unsigned long long* sorted, int n, const unsigned* base,
+                                                         const long long* seen, DecRow* rows, MergedInfo* info, int* error) {
+  const int lane = (int)(threadIdx.x & 63);
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const unsigned total = base[(n + kMergeChunk - 1) / kMergeChunk];
+  for (int w0 = (int)(blockIdx.x * kThreads + (threadIdx.x & ~63u)); w0 < n; w0 += (int)(gridDim.x * kThreads)) {
+    const int j0 = w0 + lane;
+    const bool head = merge_head(sorted, n, j0);
+    const unsigned long long m = __ballot(head);
+    if (!head) continue;
+    const unsigned out = base[w0 / kMergeChunk] + (unsigned)__popcll(m & lt);
+    if (out >= total) { ADSB_AIR_STORE(error, 1); continue; }          // (the counts and this walk disagree: never)
+    const unsigned addr = merge_addr(sorted[j0]);
+    Plane q{};
+    q.present = kHasPlane;
+    q.lat = q.lon = __builtin_nan("");
+    MergedInfo f{};
+    f.src_callsign = f.src_altitude = f.src_velocity = f.src_position = -1;
+    long long t_cs = 0, t_alt = 0, t_vel = 0, t_pos = 0;
+    for (int j = j0; j < n; ++j) {
+      const unsigned long long key = sorted[j];
+      if (merge_addr(key) != addr) break;
+      const unsigned stream = (unsigned)key & ((1u << kFleetStreamBits) - 1u);
+      bool claimed = false;
+      const unsigned h = fleet_slot(a.s, ((unsigned long long)a.gen[stream] << (kFleetAddrBits + kFleetStreamBits)) |
+                                             ((unsigned long long)stream << kFleetAddrBits) | addr, false, &claimed);
+      if (h == kFleetNone) { ADSB_AIR_STORE(error, 1); continue; }
+      const Plane* p = &a.s.planes[h];
+      const long long t = seen[h];
+      const unsigned present = p->present;
+      if (f.n_streams == 0 || t > f.last_seen) f.last_seen = t;
+      f.n_streams += 1;
+      q.num_msgs += p->num_msgs;                                        // uint32: wraps modulo 2^32
+      if ((present & kHasCallsign) && (f.src_callsign < 0 || t > t_cs)) { q.callsign = p->callsign; t_cs = t; f.src_callsign = (int)stream; }
+      if ((present & kHasAltitude) && (f.src_altitude < 0 || t > t_alt)) { q.altitude = p->altitude; t_alt = t; f.src_altitude = (int)stream; }
+      if ((present & kHasVelocity) && (f.src_velocity < 0 || t > t_vel)) {
+        q.vwe = p->vwe; q.vsn = p->vsn; q.vr = p->vr; t_vel = t; f.src_velocity = (int)stream;
+      }
+      const double lat = p->lat;
+      if (lat == lat && (f.src_position < 0 || t > t_pos)) { q.lat = lat; q.lon = p->lon; t_pos = t; f.src_position = (int)stream; }
+    }
+    if (f.src_callsign >= 0) q.present |= kHasCallsign;
+    if (f.src_altitude >= 0) q.present |= kHasAltitude;
+    if (f.src_velocity >= 0) q.present |= kHasVelocity;
+    if (rows) planes_row(rows, (int)total, out, &q, addr);
+    if (info) info[out] = f;
+  }
+}
+
 }  // namespace adsb
 
 // Stage 2 of the decode step.  Outside adsb, in an unnamed namespace: the three kernels are the including unit's own, so the

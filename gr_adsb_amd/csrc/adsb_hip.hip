@@ -309,6 +309,7 @@ struct FleetDec {
   DevBuf d_ages;                                // adsb_stream_planes_expire: cutoffs[n_streams] | removed[n_streams]; _seen: last_seen[n]
   DevBuf d_recs, d_items, d_cnt, d_keys, d_sorted, d_tmp, d_ts, d_rows, d_gen;
   DevBuf d_snap;                                // adsb_stream_planes: generations | selection bitmap | selection list | first[] | count, error
+  DevBuf d_merged;                              // adsb_stream_planes_merged: the adsb_merged entries beside d_rows
   PinnedBuf h_recs, h_rows, h_items, h_cnt;
   int32_t n_rows = 0;                           // rows of the last delivered call
 };
@@ -1685,7 +1686,7 @@ int fleet_close(adsb_ctx* c) {
   FleetDec& F = c->fd;
   F.open = false; F.cap = 0; F.n_rows = 0;
   F.start.clear(); F.gen.clear(); F.slots.clear(); F.planes.clear();
-  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen, &F.d_snap, &F.d_ages}) HIPCHK(c, b->release());
+  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen, &F.d_snap, &F.d_ages, &F.d_merged}) HIPCHK(c, b->release());
   for (PinnedBuf* b : {&F.h_recs, &F.h_rows, &F.h_items, &F.h_cnt}) HIPCHK(c, b->release());
   return 0;
 }
@@ -2748,6 +2749,89 @@ int adsb_stream_planes_expire(adsb_ctx* c, const int32_t* streams, int32_t n_sel
   long long total = 0;
   if ((rc = fleet_rehash(c, F.cap, false, cut.data(), &total))) return rc;
   if (n_removed) *n_removed = (int64_t)total;
+  return 0;
+}
+
+// The fleet's merged picture (adsb_device.h: k_merge_*): planes_fleet's shape with the address-major key, a head count and its
+// scan between the sort and the emit step
+static_assert(sizeof(adsb_merged) == 32 && sizeof(adsb_merged) == sizeof(MergedInfo), "adsb_merged is 32 bytes");
+int adsb_stream_planes_merged(adsb_ctx* c, const int32_t* streams, int32_t n_sel, int64_t cutoff, adsb_decoded* rows, adsb_merged* info,
+                              int32_t cap, int32_t* n_out) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE");
+  if (!(c->flags & ADSB_FLAG_PLANE_AGES)) return fail(c, -EINVAL, "context created without ADSB_FLAG_PLANE_AGES");
+  if (!n_out || cap < 0 || (cap > 0 && !rows && !info)) return fail(c, -EINVAL, "adsb_stream_planes_merged: n_out, or rows / info for cap > 0, missing");
+  FleetDec& F = c->fd;
+  if (!F.open) return fail(c, -EINVAL, "adsb_stream_planes_merged: no streams (adsb_streams_open first)");
+  const size_t ns = F.gen.size();
+  if (!streams) n_sel = (int32_t)ns;
+  if (n_sel < 0) return fail(c, -EINVAL, "adsb_stream_planes_merged: n_sel < 0");
+  for (int32_t i = 0; streams && i < n_sel; ++i)
+    if (streams[i] < 0 || (size_t)streams[i] >= ns || (i > 0 && streams[i] <= streams[i - 1]))
+      return fail(c, -EINVAL, "adsb_stream_planes_merged: stream indices have to be in range and strictly ascending");
+  int rc = require_idle(c, kCallPending);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = c->stream;
+  // the staging block: generations | selection bitmap | count, error
+  const size_t nw = (ns + 31) / 32, o_bits = ns, o_cnt = o_bits + nw, words = o_cnt + 2;
+  std::vector<unsigned> h(words, 0u);
+  for (size_t s = 0; s < ns; ++s) h[s] = F.gen[s];
+  for (int32_t i = 0; streams && i < n_sel; ++i) h[o_bits + (size_t)streams[i] / 32] |= 1u << ((unsigned)streams[i] & 31u);
+  const long long key_cap = F.live_planes;                     // every live plane is counted there (fleet_step)
+  if ((rc = ensure(c, F.d_snap, words * sizeof(unsigned))) || (rc = ensure(c, F.d_keys, (size_t)key_cap * 8)) ||
+      (rc = ensure(c, F.d_sorted, (size_t)key_cap * 8)))
+    return rc;
+  unsigned* const d = (unsigned*)F.d_snap.p;
+  HIPCHK(c, hipMemcpyAsync(d, h.data(), words * sizeof(unsigned), hipMemcpyHostToDevice, st));
+  PlanesFleet a{};
+  a.s = fleet_view(F.d_store.p, F.cap); a.gen = d; a.sel_bits = streams ? d + o_bits : nullptr; a.n_streams = (int)ns;
+  const long long* const seen = fleet_seen(c, F.d_store.p, F.cap);
+  int* const d_cnt = (int*)(d + o_cnt);
+  hipLaunchKernelGGL(k_merge_keys, dim3(step_grid(F.cap, kThreads)), dim3(kThreads), 0, st, a, seen, (long long)cutoff,
+                     (unsigned long long*)F.d_keys.p, (int)key_cap, d_cnt);
+  HIPCHK(c, hipGetLastError());
+  int got[2] = {0, 0};
+  HIPCHK(c, hipMemcpyAsync(got, d_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const int n = got[0];
+  if ((long long)n > key_cap) return fail(c, -EIO, "stream decoders: the store holds more planes than the streams count");
+  if (n == 0) {
+    *n_out = 0;
+    return 0;
+  }
+  const int nblk = (n + kSortTile - 1) / kSortTile, n_chunks = (n + kMergeChunk - 1) / kMergeChunk;
+  if ((rc = ensure(c, F.d_tmp, std::max((size_t)nblk * 16, (size_t)n_chunks + 1) * sizeof(unsigned)))) return rc;
+  unsigned long long* in = (unsigned long long*)F.d_keys.p;
+  unsigned long long* out = (unsigned long long*)F.d_sorted.p;
+  for (int shift = 0; shift < kFleetAddrBits + kFleetStreamBits; shift += 4) {          // eleven passes: the result ends in d_sorted
+    hipLaunchKernelGGL(k_dec_sort_hist, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, n, shift, (unsigned*)F.d_tmp.p);
+    hipLaunchKernelGGL(k_dec_sort_scan, dim3(1), dim3(kThreads), 0, st, (unsigned*)F.d_tmp.p, nblk * 16);
+    hipLaunchKernelGGL(k_dec_sort_scatter, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, out, n, shift,
+                       (const unsigned*)F.d_tmp.p);
+    unsigned long long* x = in; in = out; out = x;
+  }
+  const unsigned eg = step_grid(n, kThreads);
+  hipLaunchKernelGGL(k_merge_heads, dim3(eg), dim3(kThreads), 0, st, (const unsigned long long*)F.d_sorted.p, n, (unsigned*)F.d_tmp.p);
+  hipLaunchKernelGGL(k_dec_sort_scan, dim3(1), dim3(kThreads), 0, st, (unsigned*)F.d_tmp.p, n_chunks + 1);
+  HIPCHK(c, hipGetLastError());
+  unsigned total = 0;
+  HIPCHK(c, hipMemcpyAsync(&total, (unsigned*)F.d_tmp.p + n_chunks, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (total == 0 || total > (unsigned)n) return fail(c, -EIO, "stream decoders: the merged picture's head count is out of range");
+  *n_out = (int32_t)total;
+  if (total > (unsigned)cap) return fail(c, -ENOSPC, "adsb_stream_planes_merged: cap is smaller than the number of aircraft (*n_out)");
+  if ((rows && (rc = ensure(c, F.d_rows, (size_t)total * sizeof(DecRow)))) || (info && (rc = ensure(c, F.d_merged, (size_t)total * sizeof(MergedInfo)))))
+    return rc;
+  hipLaunchKernelGGL(k_merge_emit, dim3(eg), dim3(kThreads), 0, st, a, (const unsigned long long*)F.d_sorted.p, n,
+                     (const unsigned*)F.d_tmp.p, seen, rows ? (DecRow*)F.d_rows.p : (DecRow*)nullptr,
+                     info ? (MergedInfo*)F.d_merged.p : (MergedInfo*)nullptr, d_cnt + 1);
+  HIPCHK(c, hipGetLastError());
+  if (rows) HIPCHK(c, hipMemcpyAsync(rows, F.d_rows.p, (size_t)total * sizeof(DecRow), hipMemcpyDeviceToHost, st));
+  if (info) HIPCHK(c, hipMemcpyAsync(info, F.d_merged.p, (size_t)total * sizeof(MergedInfo), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(got, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (got[1]) return fail(c, -EIO, "stream decoders: the merged picture found a plane without a slot");
   return 0;
 }
 

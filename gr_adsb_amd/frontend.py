@@ -269,6 +269,21 @@ class Receivers:
         cut = np.full(k, int(cutoffs), dtype=np.int64) if np.ndim(cutoffs) == 0 else np.asarray(cutoffs, dtype=np.int64)
         return self.ctx.expire_stream_planes(cut, ids)
 
+    def merged(self, ids=None, cutoff=None):
+        """receivers(ages=True): ONE picture out of every receiver's -- (rows, info), one DECODED_DTYPE row per aircraft any
+        stream of `ids` (strictly ascending; None: all) holds, in ascending address order, and its _native.MERGED_DTYPE entry
+        (adsb_stream_planes_merged).  Callsign, altitude, velocity and position each come from the receiver that has the field
+        and heard the aircraft last (info["src_*"]: which one); num_msgs is the sum, info["last_seen"] the latest clock.
+        cutoff: entries with last_seen < cutoff are left out (None: none is); the streams' clocks have to be comparable, i.e.
+        `starts` real times.  _native.plane_entry(row, last_seen) turns a row into the reference's plane_dict entry."""
+        if not (self.decode and self.ages):
+            raise ValueError("merged() needs receivers(ages=True) on a FLAG_STREAM_DECODE | FLAG_PLANE_AGES context")
+        return self.ctx.merged_planes(ids, cutoff)
+
+    def table(self, timestamp, ids=None, cutoff=None):
+        """The lines the reference's print_planes draws ("Brief") for the merged picture at PDU timestamp `timestamp`."""
+        return _native.plane_table(self.merged(ids, cutoff)[0], timestamp)
+
     def state(self, i):
         """(pos, eob, n_overlong) of stream i"""
         return self.ctx.stream_state(i)

@@ -613,6 +613,44 @@ int adsb_stream_planes_seen(adsb_ctx* ctx, const int32_t* streams, int32_t n_sel
                             int32_t cap, int32_t* first, int32_t* n_out);
 int adsb_planes_expire(adsb_ctx* ctx, int64_t cutoff, int64_t* n_removed);
 int adsb_stream_planes_expire(adsb_ctx* ctx, const int32_t* streams, int32_t n_sel, const int64_t* cutoffs, int64_t* n_removed);
+/* MERGED PICTURE: the fleet's per-receiver plane_dicts folded into one table on the device -- what one decoder feeding one
+ * map shows (web/webserver.py reads one plane_dict), for a fleet whose receivers each hear a part of every aircraft.  The
+ * context must have ADSB_FLAG_STREAM_DECODE | ADSB_FLAG_PLANE_AGES and open streams (-EINVAL otherwise: the rule needs
+ * last_seen).  streams / n_sel as for adsb_stream_planes: NULL selects all streams, otherwise strictly ascending indices in
+ * range (-EINVAL).  -EBUSY while submitted tickets are pending; ordered behind the last queued decode step.
+ * A CONTRIBUTING entry is a live plane of a selected stream's current generation with last_seen >= cutoff: a reset stream's
+ * stale slots and expired planes never contribute, cutoff = INT64_MIN hides nothing.  The cutoff only hides entries; nothing
+ * is removed.  One cutoff for all selected streams presumes that their clocks are comparable, which they are when
+ * adsb_stream_set_start was given real times.
+ * Output: one row per distinct address with at least one contributing entry, in ascending address order.  rows[j] is a
+ * snapshot row as adsb_stream_planes writes it (port ADSB_DEC_NONE, df 0, bits and pad bytes zero, icao the address);
+ * info[j] belongs to rows[j].  num_msgs is the uint32 sum over the contributing entries: it wraps modulo 2^32.
+ * info[j].last_seen is the largest last_seen among them, n_streams their number.
+ * Four field groups are merged, each on its own: callsign (ADSB_DEC_HAS_CALLSIGN), altitude (ADSB_DEC_HAS_ALTITUDE), velocity
+ * (ADSB_DEC_HAS_VELOCITY: velocity_we, velocity_sn and vertical_rate together) and position (latitude is not NaN: latitude
+ * and longitude together).  A group is copied, byte for byte, from the contributing entry that has it and has the greatest
+ * last_seen; ties go to the lowest stream index; src_* names that stream.  A group no contributing entry has is shown as an
+ * empty plane shows it (flag clear, zero callsign / altitude / velocity, NaN position) with src_* = -1.  present is
+ * ADSB_DEC_HAS_PLANE plus the flags of the groups found.  last_seen is per plane, not per field: the rule is "the freshest
+ * entry that has the field", not a claim about the field's own age.
+ * cap smaller than the number of rows is -ENOSPC with *n_out = the number needed and nothing written;
+ * rows == NULL && info == NULL && cap == 0 is a count query; either of rows and info may be NULL when only the other is
+ * wanted.  An empty result returns 0 with *n_out = 0.  The call changes no state: two merged calls with nothing between
+ * them are byte-identical, adsb_stream_planes_seen before and after is byte-identical, and rows decoded afterwards are
+ * byte-identical to rows decoded without it.  With one selected stream and cutoff = INT64_MIN the rows are those of
+ * adsb_stream_planes_seen of that stream, info.last_seen its last_seen, n_streams 1 and every src_* that stream or -1.
+ * CPR frames are not merged across receivers.  ADSB_ABI_VERSION is unchanged: an entry point only. */
+typedef struct adsb_merged {      /* 32 bytes; info[j] belongs to rows[j] */
+  int64_t last_seen;              /* the largest last_seen among the contributing streams */
+  int32_t n_streams;              /* how many contributing streams hold this aircraft (>= 1) */
+  int32_t src_callsign;           /* the stream each field group was taken from; -1: no contributing stream has it */
+  int32_t src_altitude;
+  int32_t src_velocity;
+  int32_t src_position;
+  int32_t pad;                    /* 0 */
+} adsb_merged;
+int adsb_stream_planes_merged(adsb_ctx* ctx, const int32_t* streams, int32_t n_sel, int64_t cutoff,
+                              adsb_decoded* rows, adsb_merged* info, int32_t cap, int32_t* n_out);
 /* Device memory on the context's device for callers that do not link HIP (a C or ctypes client of the *_device entry
  * points): hipMalloc / hipFree / a blocking hipMemcpy host -> device.  16-byte alignment is guaranteed.  No reference
  * counterpart (the reference never leaves host memory). */
