@@ -26,6 +26,7 @@ FLAG_FEC_CONSERVATIVE = 128  # opt-in: the decoder's "Conservative" 1-2-bit burs
 FLAG_AIRCRAFT_TABLE = 256    # opt-in: the decoder's aircraft table on the device: verdicts for address/parity replies
 FLAG_DECODE = 512            # opt-in (with FLAG_AIRCRAFT_TABLE): the decoder's message decoding and plane fields on the device
 FLAG_STREAM_DECODE = 1024    # opt-in: one decoder behind every receiver stream (open_streams), one device step per stream-batch call
+FLAG_STREAM_DECODE_SHARED = 4096   # opt-in, with FLAG_STREAM_DECODE: ONE decoder behind all streams, fed every call's records in time order
 FLAG_PLANE_AGES = 2048       # opt-in, with FLAG_DECODE or FLAG_STREAM_DECODE: plane_dict's last_seen on the device (planes(seen=True), expire_*)
 # include/adsb_hip.h adsb_decoded: one row per delivered record of a FLAG_DECODE context
 DECODED_DTYPE = np.dtype([("port", "u1"), ("df", "u1"), ("present", "u1"), ("pad0", "u1"), ("icao", "<i4"), ("bits", "u1", (14,)),
@@ -85,7 +86,7 @@ EXPORTS = [
     "adsb_streams_set_decoder", "adsb_stream_set_start", "adsb_stream_last_decoded", "adsb_stream_decoder_reserve",
     "adsb_stream_decoder_stats", "adsb_planes", "adsb_stream_planes",
     "adsb_planes_seen", "adsb_stream_planes_seen", "adsb_planes_expire", "adsb_stream_planes_expire",
-    "adsb_stream_planes_merged",
+    "adsb_stream_planes_merged", "adsb_stream_last_order", "adsb_streams_decoder_reset",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
 ]
 
@@ -187,6 +188,8 @@ def load():
     lib.adsb_streams_set_decoder.argtypes = [vp, i32]
     lib.adsb_stream_set_start.argtypes = [vp, i32, c.c_double]
     lib.adsb_stream_last_decoded.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
+    lib.adsb_stream_last_order.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
+    lib.adsb_streams_decoder_reset.argtypes = [vp]
     lib.adsb_stream_decoder_reserve.argtypes = [vp, i64]
     lib.adsb_stream_decoder_stats.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
     lib.adsb_planes.argtypes = [vp, vp, i32, c.POINTER(i32)]
@@ -565,6 +568,21 @@ class Context:
         buf = (ctypes.c_char * (n.value * DECODED_DTYPE.itemsize)).from_address(p.value)
         v = np.frombuffer(buf, dtype=DECODED_DTYPE)
         return v.copy() if copy else v
+
+    # FLAG_STREAM_DECODE_SHARED contexts: one decoder behind all streams (include/adsb_hip.h SHARED DECODER)
+    def last_stream_order(self):
+        """int32[n]: the list position of the r-th record in the publication order -- ascending (timestamp, list position) --
+        of the last delivered stream-batch call (adsb_stream_last_order)."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int32(0)
+        self._chk(self.lib.adsb_stream_last_order(self._h, ctypes.byref(p), ctypes.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=np.int32)
+        return np.frombuffer((ctypes.c_char * (n.value * 4)).from_address(p.value), dtype=np.int32).copy()
+
+    def reset_streams_decoder(self):
+        """A fresh shared decoder; the streams' framing state stays (adsb_streams_decoder_reset)."""
+        self._chk(self.lib.adsb_streams_decoder_reset(self._h))
 
     def stream_decoder_reserve(self, slots):
         """The capacity of the decoders' store, while it holds nothing (adsb_stream_decoder_reserve)."""

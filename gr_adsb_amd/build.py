@@ -7,7 +7,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libadsb_hip.so")
 SOURCES = ["adsb_hip.hip"]
-DEPS = ["adsb_hip.hip", "adsb_device.h", "adsb_plan.h", os.path.join("..", "..", "include", "adsb_hip.h")]
+# ADSB_FLAG_STREAM_DECODE_SHARED's kernels: a translation unit of its own, so that adsb_hip.hip's kernels compile as without it
+SHARED_SOURCE = "adsb_shared.hip"
+DEPS = ["adsb_hip.hip", "adsb_device.h", "adsb_plan.h", os.path.join("..", "..", "include", "adsb_hip.h"),
+        "adsb_shared.hip", "adsb_shared.h", "adsb_shared_device.h"]
 # -ffp-contract=off: |IQ|^2 must be two rounded products and one rounded add
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread"]
 
@@ -27,6 +30,7 @@ def up_to_date():
 
 
 RES = os.path.join(HERE, "kernel_resources.json")
+RES_SHARED = os.path.join(HERE, "kernel_resources_shared.json")
 
 
 def _parse_resources(remarks):
@@ -47,22 +51,51 @@ def _parse_resources(remarks):
     return out
 
 
+def compile_and_link(out, extra_flags=(), verbose=False):
+    """Both translation units, each compiled with FLAGS + extra_flags side by side, linked into the shared library `out`
+    (libadsb_hip.so, or a side copy: tools/kbench.py) -> [the compiler's output per unit, SOURCES first].  The objects live
+    in a temporary directory."""
+    import shutil
+    import tempfile
+    compile_flags = [f for f in FLAGS if f != "-shared"] + list(extra_flags)
+    tmp = tempfile.mkdtemp(prefix="adsb_build_")
+    try:
+        units = [(os.path.join(CSRC, s), os.path.join(tmp, s + ".o")) for s in SOURCES + [SHARED_SOURCE]]
+        jobs = []
+        for src, obj in units:
+            cmd = [hipcc()] + compile_flags + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", obj]
+            if verbose:
+                print(" ".join(cmd))
+            jobs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
+        outs = [(cmd, p.communicate()[0], p.returncode) for cmd, p in jobs]
+        for cmd, text, rc in outs:
+            if rc != 0:
+                sys.stderr.write(text)
+                raise subprocess.CalledProcessError(rc, cmd)
+        cmd = [hipcc()] + FLAGS + list(extra_flags) + [obj for _, obj in units] + ["-o", out]
+        if verbose:
+            print(" ".join(cmd))
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if r.returncode != 0:
+            sys.stderr.write(r.stdout)
+            raise subprocess.CalledProcessError(r.returncode, cmd)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    return [text for _, text, _ in outs]
+
+
 def build(force=False, verbose=False):
     """hipcc -> libadsb_hip.so, and beside it kernel_resources.json: the compiler's per-kernel register / LDS / scratch
-    report (tests/test_abi.py holds the limits the pipeline relies on: k_detect must leave the tail kernels room)."""
-    if not force and up_to_date() and os.path.exists(RES):
+    report (tests/test_abi.py holds the limits the pipeline relies on: k_detect must leave the tail kernels room), and
+    kernel_resources_shared.json: the same for adsb_shared.hip's kernels."""
+    if not force and up_to_date() and os.path.exists(RES) and os.path.exists(RES_SHARED):
         return LIB
-    cmd = [hipcc()] + FLAGS + ["-Rpass-analysis=kernel-resource-usage"] + [os.path.join(CSRC, s) for s in SOURCES] + ["-o", LIB]
-    if verbose:
-        print(" ".join(cmd))
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        sys.stderr.write(r.stdout)
-        raise subprocess.CalledProcessError(r.returncode, cmd)
     import json
-    res = _parse_resources(r.stdout)
-    with open(RES, "w") as f:
-        json.dump(res, f, indent=1, sort_keys=True)
+    remarks = compile_and_link(LIB, verbose=verbose)
+    assert len(SOURCES) == 1
+    for path, text in zip((RES, RES_SHARED), remarks):
+        with open(path, "w") as f:
+            json.dump(_parse_resources(text), f, indent=1, sort_keys=True)
     return LIB
 
 

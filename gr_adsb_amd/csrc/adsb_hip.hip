@@ -28,6 +28,8 @@
 #include <thread>
 #include <vector>
 
+#include "adsb_shared.h"
+
 // wavefront-level ordering point used by adsb_device.h: LDS traffic of one wavefront is executed in
 // program order by the hardware, this only stops the compiler from moving LDS accesses across it
 __device__ __forceinline__ void adsb_wave_sync() {
@@ -310,11 +312,48 @@ struct FleetDec {
   DevBuf d_recs, d_items, d_cnt, d_keys, d_sorted, d_tmp, d_ts, d_rows, d_gen;
   DevBuf d_snap;                                // adsb_stream_planes: generations | selection bitmap | selection list | first[] | count, error
   DevBuf d_merged;                              // adsb_stream_planes_merged: the adsb_merged entries beside d_rows
+  DevBuf d_shared;                              // ADSB_FLAG_STREAM_DECODE_SHARED: the time order's buffers of one call (SharedBufs)
   PinnedBuf h_recs, h_rows, h_items, h_cnt;
+  PinnedBuf h_shared, h_order;                  // ... the items' first[] | start[] on their way up, order[] of the last delivered call
+  PinnedBuf h_order_next;                       // ... and where a call's order[] arrives: the two change places once the call is delivered
   int32_t n_rows = 0;                           // rows of the last delivered call
 };
 constexpr long long kFleetMinCap = 256, kFleetDefaultCap = 1ll << 16, kFleetMaxCap = 1ll << 27;    // (slot index 2^28 - 1 would sort with kDecNoKey)
 constexpr size_t kFleetSlotBytes = 16 + sizeof(Plane);
+static_assert(sizeof(Rec) == adsb_shared_host::kRecBytes && sizeof(DecRow) == adsb_shared_host::kRowBytes,
+              "adsb_shared.hip moves records and rows as opaque words of these sizes");
+static_assert(offsetof(Rec, w) == 0 && kSortTile == adsb_shared_host::kSortTile, "a record's offset is its word 0; one sort tile");
+// ADSB_FLAG_STREAM_DECODE_SHARED: d_shared carved for a call of n records in n_items items, every part on a 256-byte boundary
+struct SharedBufs {
+  unsigned long long *keys = nullptr, *keys_tmp = nullptr;
+  double *ts = nullptr, *ts_sorted = nullptr;
+  Rec* recs = nullptr;                          // the time-ordered list the decode step runs on
+  DecRow* rows = nullptr;                       // ... and its rows
+  unsigned *vals = nullptr, *vals_tmp = nullptr, *hist = nullptr;
+  int *order = nullptr, *first = nullptr;
+  double* start = nullptr;
+  SharedBufs() = default;                       // a context without the flag: nothing
+  // the parts' offsets in bytes, in the members' order -> the size of the whole
+  static size_t layout(size_t n, size_t n_items, size_t off[12]) {
+    const size_t part[12] = {n * 8, n * 8, n * 8, n * 8, n * sizeof(Rec), n * sizeof(DecRow), n * 4, n * 4,
+                             adsb_shared_host::sort_hist_bytes((int)n), n * 4, (n_items + 1) * sizeof(int), n_items * sizeof(double)};
+    size_t at = 0;
+    for (int k = 0; k < 12; ++k) { off[k] = at; at += (part[k] + 255) & ~(size_t)255; }
+    return at;
+  }
+  static size_t bytes(size_t n, size_t n_items) { size_t off[12]; return layout(n, n_items, off); }
+  // base: device memory of bytes(n, n_items)
+  SharedBufs(void* base, size_t n, size_t n_items) {
+    size_t off[12];
+    layout(n, n_items, off);
+    char* const b = (char*)base;
+    keys = (unsigned long long*)(b + off[0]); keys_tmp = (unsigned long long*)(b + off[1]);
+    ts = (double*)(b + off[2]); ts_sorted = (double*)(b + off[3]);
+    recs = (Rec*)(b + off[4]); rows = (DecRow*)(b + off[5]);
+    vals = (unsigned*)(b + off[6]); vals_tmp = (unsigned*)(b + off[7]); hist = (unsigned*)(b + off[8]);
+    order = (int*)(b + off[9]); first = (int*)(b + off[10]); start = (double*)(b + off[11]);
+  }
+};
 
 }  // namespace
 
@@ -1686,21 +1725,29 @@ int fleet_close(adsb_ctx* c) {
   FleetDec& F = c->fd;
   F.open = false; F.cap = 0; F.n_rows = 0;
   F.start.clear(); F.gen.clear(); F.slots.clear(); F.planes.clear();
-  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen, &F.d_snap, &F.d_ages, &F.d_merged}) HIPCHK(c, b->release());
-  for (PinnedBuf* b : {&F.h_recs, &F.h_rows, &F.h_items, &F.h_cnt}) HIPCHK(c, b->release());
+  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen, &F.d_snap, &F.d_ages, &F.d_merged, &F.d_shared}) HIPCHK(c, b->release());
+  for (PinnedBuf* b : {&F.h_recs, &F.h_rows, &F.h_items, &F.h_cnt, &F.h_shared, &F.h_order, &F.h_order_next}) HIPCHK(c, b->release());
   return 0;
 }
 
 // The decode step of one delivered call: recs[0 .. n) is its final list (item i: [item_first[i], item_first[i + 1])).  The
 // records come back in F.h_recs with their verdict flags, the rows in F.h_rows.  Everything that can fail for want of
 // memory happens before the first kernel that touches the store.
+// ADSB_FLAG_STREAM_DECODE_SHARED: one decoder for all streams.  The list is put into the order ascending (timestamp, list
+// position) first (adsb_shared.hip), the same kernels run on that list as ONE item of stream 0, and the verdict flags and
+// rows go back to list positions; F.h_order holds the order of the last call that was delivered (a call that fails here leaves it).
 int fleet_step(adsb_ctx* c, const adsb_stream_item* items, int32_t n_items, const int32_t* item_first, const adsb_burst* recs, int32_t n) {
   FleetDec& F = c->fd;
   const hipStream_t st = c->stream;
   if (n == 0) { F.n_rows = 0; return 0; }
   int r;
-  const size_t nn = (size_t)n, ni = (size_t)n_items;
+  const bool shared = (c->flags & ADSB_FLAG_STREAM_DECODE_SHARED) != 0;
+  const size_t nn = (size_t)n, ni = shared ? 1 : (size_t)n_items;      // ni: the items of the decode step's own table
   const int nblk = (int)((nn + kSortTile - 1) / kSortTile);
+  const size_t shared_tab = ((size_t)n_items + 1) * sizeof(int) + (size_t)n_items * sizeof(double);
+  if (shared && ((r = ensure(c, F.d_shared, SharedBufs::bytes(nn, (size_t)n_items))) || (r = ensure_pinned(c, F.h_shared, shared_tab)) ||
+                 (r = ensure_pinned(c, F.h_order_next, nn * sizeof(int)))))
+    return r;
   const size_t cnt_bytes = ni * sizeof(FleetCount) + (ni + 2) * sizeof(int);
   if ((r = ensure(c, F.d_recs, nn * sizeof(Rec))) || (r = ensure(c, F.d_items, (ni + 1) * sizeof(FleetItem))) ||
       (r = ensure(c, F.d_cnt, cnt_bytes)) || (r = ensure(c, F.d_keys, nn * 8)) || (r = ensure(c, F.d_sorted, nn * 8)) ||
@@ -1721,32 +1768,58 @@ int fleet_step(adsb_ctx* c, const adsb_stream_item* items, int32_t n_items, cons
     if (cap > old_cap) F.grows++;
   }
   FleetItem* const hi = (FleetItem*)F.h_items.p;
-  for (int32_t i = 0; i < n_items; ++i) {
-    const size_t s = (size_t)items[i].stream;
-    hi[i].first = item_first[i];
-    hi[i].stream = items[i].stream;
-    hi[i].base = ((unsigned long long)F.gen[s] << (kFleetAddrBits + kFleetStreamBits)) | ((unsigned long long)s << kFleetAddrBits);
-    hi[i].start = F.start[s];
-  }
-  hi[n_items].first = n; hi[n_items].stream = -1; hi[n_items].base = 0; hi[n_items].start = 0;
+  SharedBufs sh;
+  if (shared) {                                  // the whole list is one item of stream 0 (its start is not used: see d_ts below)
+    sh = SharedBufs(F.d_shared.p, nn, (size_t)n_items);
+    hi[0].first = 0; hi[0].stream = 0; hi[0].base = (unsigned long long)F.gen[0] << (kFleetAddrBits + kFleetStreamBits); hi[0].start = 0;
+    int* const hf = (int*)F.h_shared.p;
+    double* const hs = (double*)(hf + n_items + 1);
+    for (int32_t i = 0; i < n_items; ++i) {
+      hf[i] = item_first[i];
+      const double start = F.start[(size_t)items[i].stream];
+      memcpy(&hs[i], &start, sizeof(double));    // (behind an odd number of ints: not aligned)
+    }
+    hf[n_items] = n;
+  } else
+    for (int32_t i = 0; i < n_items; ++i) {
+      const size_t s = (size_t)items[i].stream;
+      hi[i].first = item_first[i];
+      hi[i].stream = items[i].stream;
+      hi[i].base = ((unsigned long long)F.gen[s] << (kFleetAddrBits + kFleetStreamBits)) | ((unsigned long long)s << kFleetAddrBits);
+      hi[i].start = F.start[s];
+    }
+  hi[ni].first = n; hi[ni].stream = -1; hi[ni].base = 0; hi[ni].start = 0;
   memcpy(F.h_recs.p, recs, nn * sizeof(Rec));
   HIPCHK(c, hipMemcpyAsync(F.d_recs.p, F.h_recs.p, nn * sizeof(Rec), hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(F.d_items.p, hi, (ni + 1) * sizeof(FleetItem), hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemsetAsync(F.d_cnt.p, 0, cnt_bytes, st));
+  if (shared) {
+    HIPCHK(c, hipMemcpyAsync(sh.first, F.h_shared.p, ((size_t)n_items + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(sh.start, (const char*)F.h_shared.p + ((size_t)n_items + 1) * sizeof(int), (size_t)n_items * sizeof(double),
+                             hipMemcpyHostToDevice, st));
+    hipError_t e;
+    if ((e = (hipError_t)adsb_shared_host::launch_keys(st, F.d_recs.p, n, sh.first, sh.start, n_items, c->fs, sh.keys, sh.vals, sh.ts)) ||
+        (e = (hipError_t)adsb_shared_host::launch_sort(st, sh.keys, sh.vals, sh.keys_tmp, sh.vals_tmp, n, sh.hist)) ||
+        (e = (hipError_t)adsb_shared_host::launch_gather(st, F.d_recs.p, sh.ts, sh.vals, n, sh.recs, sh.ts_sorted, sh.order)))
+      return fail(c, -EIO, "shared decoder: the time order's kernels", e);
+  }
   FleetArgs a{};
-  a.recs = (Rec*)F.d_recs.p; a.n = n; a.n_items = n_items; a.items = (const FleetItem*)F.d_items.p;
+  a.recs = shared ? sh.recs : (Rec*)F.d_recs.p; a.n = n; a.n_items = (int)ni; a.items = (const FleetItem*)F.d_items.p;
   a.count = (FleetCount*)F.d_cnt.p; a.ncond = (int*)(a.count + ni); a.error = a.ncond + ni + 1;
   a.s = fleet_view(F.d_store.p, F.cap);
   a.call = F.call << 32;
   a.fec = (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) ? 1 : 0; a.all = F.all; a.fs = c->fs;
-  a.keys = (unsigned long long*)F.d_keys.p; a.sorted = (const unsigned long long*)F.d_sorted.p; a.rows = (DecRow*)F.d_rows.p;
+  a.keys = (unsigned long long*)F.d_keys.p; a.sorted = (const unsigned long long*)F.d_sorted.p;
+  a.rows = shared ? sh.rows : (DecRow*)F.d_rows.p;
   a.ts = (double*)F.d_ts.p; a.seen = fleet_seen(c, F.d_store.p, F.cap);
   const unsigned g = step_grid(n, kThreads);
   hipLaunchKernelGGL(k_fleet_announce, dim3(g), dim3(kThreads), 0, st, a);
   hipLaunchKernelGGL(k_fleet_verdict, dim3(g), dim3(kThreads), 0, st, a, 0);
-  hipLaunchKernelGGL(k_fleet_cond, dim3((unsigned)n_items), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(k_fleet_cond, dim3((unsigned)ni), dim3(64), 0, st, a);
   hipLaunchKernelGGL(k_fleet_verdict, dim3(g), dim3(kThreads), 0, st, a, 1);
   hipLaunchKernelGGL(k_fleet_classify, dim3(g), dim3(kThreads), 0, st, a);
+  // k_fleet_classify's timestamps are start + offset / fs with the ONE item's start: the true ones, in time order, over them
+  if (shared) HIPCHK(c, hipMemcpyAsync(F.d_ts.p, sh.ts_sorted, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
   unsigned long long* in = (unsigned long long*)F.d_keys.p;
   unsigned long long* out = (unsigned long long*)F.d_sorted.p;
   for (int shift = 32; shift < 60; shift += 4) {          // as launch_dec: seven passes, the result ends in d_sorted
@@ -1758,19 +1831,25 @@ int fleet_step(adsb_ctx* c, const adsb_stream_item* items, int32_t n_items, cons
   }
   hipLaunchKernelGGL(k_fleet_fold, dim3((unsigned)((nn + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, a);     // one thread per key
   HIPCHK(c, hipGetLastError());
+  if (shared) {
+    const hipError_t e = (hipError_t)adsb_shared_host::launch_scatter(st, sh.recs, sh.rows, sh.order, n, F.d_recs.p, F.d_rows.p);
+    if (e) return fail(c, -EIO, "shared decoder: k_shared_scatter", e);
+    HIPCHK(c, hipMemcpyAsync(F.h_order_next.p, sh.order, nn * sizeof(int), hipMemcpyDeviceToHost, st));
+  }
   HIPCHK(c, hipMemcpyAsync(F.h_recs.p, F.d_recs.p, nn * sizeof(Rec), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipMemcpyAsync(F.h_rows.p, F.d_rows.p, nn * sizeof(DecRow), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipMemcpyAsync(F.h_cnt.p, F.d_cnt.p, cnt_bytes, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   const FleetCount* const hc = (const FleetCount*)F.h_cnt.p;
   if (((const int*)(hc + ni))[ni + 1] != 0) return fail(c, -EIO, "stream decoders: the decode step found the store inconsistent");
-  for (int32_t i = 0; i < n_items; ++i) {
-    const size_t s = (size_t)items[i].stream;
+  for (size_t i = 0; i < ni; ++i) {
+    const size_t s = shared ? 0 : (size_t)items[i].stream;
     F.slots[s] += hc[i].slots; F.planes[s] += hc[i].planes;
     F.live_slots += hc[i].slots; F.live_planes += hc[i].planes; F.used += hc[i].slots;
   }
   F.call++;
   F.n_rows = n;
+  if (shared) { std::swap(F.h_order.p, F.h_order_next.p); std::swap(F.h_order.cap, F.h_order_next.cap); }      // delivered
   return 0;
 }
 
@@ -2045,6 +2124,7 @@ int adsb_create(double fs, float threshold, int device, uint32_t flags, adsb_ctx
   if ((flags & ADSB_FLAG_DECODE) && !(flags & ADSB_FLAG_AIRCRAFT_TABLE)) return -EINVAL;   // the decode step follows the table's
   if ((flags & ADSB_FLAG_STREAM_DECODE) && (flags & (ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE | ADSB_FLAG_CONFIDENCE))) return -EINVAL;
   if ((flags & ADSB_FLAG_PLANE_AGES) && !(flags & (ADSB_FLAG_DECODE | ADSB_FLAG_STREAM_DECODE))) return -EINVAL;   // no planes to age
+  if ((flags & ADSB_FLAG_STREAM_DECODE_SHARED) && !(flags & ADSB_FLAG_STREAM_DECODE)) return -EINVAL;           // no decoder to share
   if (!out) return -EINVAL;
   *out = nullptr;
   if (!(fs > 0) || fmod(fs, 1e6) != 0.0) return -EINVAL;        // framer.py:44, demod.py:42
@@ -2351,7 +2431,23 @@ int adsb_stream_reset(adsb_ctx* c, int32_t stream) {
   if (!c) return -EINVAL;
   if (stream < 0 || (size_t)stream >= c->sb.st.size()) return fail(c, -EINVAL, "adsb_stream_reset: no such stream");
   stream_make_fresh(c->sb.st[(size_t)stream]);
-  if (c->fd.open) return fleet_reset_stream(c, (size_t)stream);
+  if (c->fd.open && !(c->flags & ADSB_FLAG_STREAM_DECODE_SHARED)) return fleet_reset_stream(c, (size_t)stream);
+  return 0;               // (a shared decoder is nobody's: adsb_streams_decoder_reset)
+}
+
+int adsb_streams_decoder_reset(adsb_ctx* c) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DECODE_SHARED)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE_SHARED");
+  if (!c->fd.open) return fail(c, -EINVAL, "adsb_streams_decoder_reset: no streams (adsb_streams_open first)");
+  return fleet_reset_stream(c, 0);
+}
+
+int adsb_stream_last_order(adsb_ctx* c, const int32_t** order, int32_t* n) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DECODE_SHARED)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE_SHARED");
+  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_last_order: no streams (adsb_streams_open first)");
+  if (order) *order = c->fd.n_rows > 0 ? (const int32_t*)c->fd.h_order.p : nullptr;
+  if (n) *n = c->fd.n_rows;
   return 0;
 }
 

@@ -150,11 +150,12 @@ class FrontEnd:
         return self.ctx.last_batch_fallbacks
 
     # -- many receivers that go on: streams carried across batch calls -----------------------------------
-    def receivers(self, n, fmt=None, starts=None, msg_filter=None, ages=False):
+    def receivers(self, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False):
         """n receiver streams on this context (Receivers below).  fmt: one of _native.FMT_*, or None: by the arrays' dtype.
         starts / msg_filter: FLAG_STREAM_DECODE contexts, the streams' start timestamps and their decoders' msg_filter.
-        ages: the context also has FLAG_PLANE_AGES (ValueError otherwise): .planes(seen=True) and .expire(cutoffs)."""
-        return Receivers(self.ctx, n, fmt, starts, msg_filter, ages)
+        ages: the context also has FLAG_PLANE_AGES (ValueError otherwise): .planes(seen=True) and .expire(cutoffs).
+        shared: the context also has FLAG_STREAM_DECODE_SHARED (ValueError otherwise): ONE decoder behind all n streams."""
+        return Receivers(self.ctx, n, fmt, starts, msg_filter, ages, shared)
 
     def shard_tensor(self, t, origin, own_lo, own_hi, stream_len, fmt=0, head_cands=0):
         _after_torch(self.ctx, t)
@@ -189,13 +190,23 @@ class Receivers:
     On a FLAG_STREAM_DECODE context every stream has a decoder of its own: after push() / finish(), .rows holds the list of
     DECODED_DTYPE row arrays that matches the returned record arrays (row t of a stream belongs to its record t;
     _native.decoded_pdu turns a row into the reference's published PDU).  starts: the streams' start timestamps (a record's
-    PDU timestamp is start + offset / fs), msg_filter: "All Messages" (default) or "Extended Squitter Only"."""
+    PDU timestamp is start + offset / fs), msg_filter: "All Messages" (default) or "Extended Squitter Only".
+    shared (a FLAG_STREAM_DECODE | FLAG_STREAM_DECODE_SHARED context): ONE decoder behind all streams, fed every push's records
+    in the order ascending (timestamp, position in the push's list), so `starts` have to be real, comparable times.  .rows is
+    as above -- each row what the one decoder made of that record --, .order holds the publication order of the last push /
+    finish as positions in the concatenation of the returned record arrays, and planes(), merged(), table() and expire()
+    address the one plane table: planes() returns ONE row array (seen=True: one (rows, last_seen) pair), expire() takes one
+    cutoff, and none of them takes ids.  The same reply heard by several receivers counts once per hearing."""
 
-    def __init__(self, ctx, n, fmt=None, starts=None, msg_filter=None, ages=False):
+    def __init__(self, ctx, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False):
         self.ctx, self.n, self.fmt = ctx, int(n), fmt
         self.decode = bool(getattr(ctx, "flags", 0) & _native.FLAG_STREAM_DECODE)
         self.ages = bool(ages)
+        self.shared = bool(shared)
         self.rows = []
+        self.order = np.zeros(0, dtype=np.int32)
+        if self.shared != bool(getattr(ctx, "flags", 0) & _native.FLAG_STREAM_DECODE_SHARED):
+            raise ValueError("shared=True needs, and shared=False excludes, a FLAG_STREAM_DECODE | FLAG_STREAM_DECODE_SHARED context")
         if self.ages and not (self.decode and getattr(ctx, "flags", 0) & _native.FLAG_PLANE_AGES):
             raise ValueError("ages needs a FLAG_STREAM_DECODE | FLAG_PLANE_AGES context")
         if not self.decode and (starts is not None or msg_filter is not None):      # (before any stream is opened)
@@ -212,6 +223,7 @@ class Receivers:
         assert len(ids) == len(arrays)
         if not ids:
             self.rows = []
+            self.order = np.zeros(0, dtype=np.int32)
             return []
         arrays = [np.asarray(a) for a in arrays]
         fmt = self._last_fmt = self.fmt if self.fmt is not None else _FMT_OF_DTYPE[arrays[0].dtype]
@@ -219,6 +231,8 @@ class Receivers:
         if self.decode:
             rows = self.ctx.last_stream_decoded()
             self.rows = [rows[first[i]:first[i + 1]] for i in range(len(ids))]
+        if self.shared:
+            self.order = self.ctx.last_stream_order()
         return [recs[first[i]:first[i + 1]] for i in range(len(ids))]
 
     def push(self, arrays, ids=None, thresholds=None):
@@ -251,6 +265,13 @@ class Receivers:
         seen (receivers(ages=True)): a list of (rows, last_seen) pairs, last_seen the int64 clocks of the rows."""
         if not self.decode:
             raise ValueError("planes() needs a FLAG_STREAM_DECODE context")
+        if self.shared:                              # the one decoder's table: the store's stream 0
+            if ids is not None:
+                raise ValueError("a shared decoder has one table: planes() takes no ids")
+            return self._per_stream_planes([0], seen)[0]
+        return self._per_stream_planes(ids, seen)
+
+    def _per_stream_planes(self, ids, seen):
         if seen:
             if not self.ages:
                 raise ValueError("planes(seen=True) needs receivers(ages=True)")
@@ -265,6 +286,10 @@ class Receivers:
         stream of `ids`, or a scalar for all of them (streams do not share a clock: a scalar suits equal start timestamps)."""
         if not self.ages:
             raise ValueError("expire() needs receivers(ages=True)")
+        if self.shared:
+            if ids is not None or np.ndim(cutoffs) != 0:
+                raise ValueError("a shared decoder has one table: expire() takes one cutoff and no ids")
+            return self.ctx.expire_stream_planes(np.array([int(cutoffs)], dtype=np.int64), [0])
         k = self.n if ids is None else len(ids)
         cut = np.full(k, int(cutoffs), dtype=np.int64) if np.ndim(cutoffs) == 0 else np.asarray(cutoffs, dtype=np.int64)
         return self.ctx.expire_stream_planes(cut, ids)
@@ -278,6 +303,10 @@ class Receivers:
         `starts` real times.  _native.plane_entry(row, last_seen) turns a row into the reference's plane_dict entry."""
         if not (self.decode and self.ages):
             raise ValueError("merged() needs receivers(ages=True) on a FLAG_STREAM_DECODE | FLAG_PLANE_AGES context")
+        if self.shared:
+            if ids is not None:
+                raise ValueError("a shared decoder has one table: merged() takes no ids")
+            ids = [0]
         return self.ctx.merged_planes(ids, cutoff)
 
     def table(self, timestamp, ids=None, cutoff=None):

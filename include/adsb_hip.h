@@ -136,6 +136,13 @@ extern "C" {
  * below.  One int64 per address beside the planes of one decoder (2^24 entries, 128 MiB), one per slot beside a fleet's
  * store.  Without the flag nothing is allocated or launched and no byte changes. */
 #define ADSB_FLAG_PLANE_AGES 2048u
+/* Opt-in, only together with ADSB_FLAG_STREAM_DECODE (adsb_create: -EINVAL otherwise): ONE DECODER BEHIND ALL STREAMS, the
+ * reference's fan-in of several demod blocks into one decoder block (decoder.py:325-352: one plane_dict, fed in arrival
+ * order) -- see SHARED DECODER below.  Every delivered adsb_process_stream_batch* call publishes its records to that one
+ * decoder in time order, so an aircraft whose replies are split over receivers is decoded as one receiver that heard them all
+ * would decode it.  Combines with ADSB_FLAG_FEC_CONSERVATIVE, _LONG_AWARE_GATE and _PLANE_AGES exactly as
+ * ADSB_FLAG_STREAM_DECODE does.  Without the flag nothing is allocated or launched and no byte of any existing call changes. */
+#define ADSB_FLAG_STREAM_DECODE_SHARED 4096u
 
 /* adsb_burst.flags */
 #define ADSB_BURST_DEMOD 1u /* eob inside the demod input: bits[] valid, a PDU is published (demod.py:82) */
@@ -546,6 +553,36 @@ int adsb_process_stream_batch_device(adsb_ctx* ctx, int format, const adsb_strea
  * adsb_stream_reset also makes that stream's decoder fresh (a new generation in the store's key: O(1) on the host; every
  * 2^20 - 2 resets of one stream the store is rehashed); adsb_reset does so for every stream; an ADSB_STREAM_END item does
  * NOT: the aircraft are still there when the receiver reconnects.  At most 2^20 streams. */
+/* SHARED DECODER (ADSB_FLAG_STREAM_DECODE | ADSB_FLAG_STREAM_DECODE_SHARED): the streams keep their own framing state and
+ * feed ONE decoder.  For one delivered adsb_process_stream_batch[_device] call with final record list out[0 .. n), let
+ *   ts[t] = start[stream of t] + (double)offset[t] / fs        (adsb_stream_set_start; the offset with the stream's base).
+ * PUBLICATION ORDER: within the call ascending (ts[t], t) -- time first, ties in the list order of the call, which is the
+ * order of the items as the caller passed them and then the position, NOT the stream index.  Records without
+ * ADSB_BURST_DEMOD take part in the order and publish nothing.  Calls publish in call order: a later call may carry earlier
+ * timestamps, and the decoder then sees time go backwards, as adsb_decode_pdus allows.
+ * EQUIVALENCE: the records' ADSB_BURST_AP_KNOWN / _AP_FEC flags and the rows of adsb_stream_last_decoded are byte-identical
+ * to what ONE reference-equivalent decoder (msg_filter of adsb_streams_set_decoder; error_corr "Conservative" iff
+ * ADSB_FLAG_FEC_CONSERVATIVE) gives when fed exactly that PDU sequence with those timestamps.  Row t still belongs to
+ * out[t]; item_first and the order of the records in out are those of a context without the flag.
+ * As for STREAM DECODERS: a call that returns -ENOSPC or any other error has changed no decoder state; items that took the
+ * ordinary pass are decoded with the rest; n == 0 and ADSB_STREAM_END items are legal; growth and rehash change no row.
+ * STATE: the decoder lives in the store under stream index 0 and that index's generation, and every plane entry point
+ * reports it as stream 0's -- adsb_stream_planes[_seen], adsb_stream_planes_expire, adsb_stream_planes_merged,
+ * adsb_stream_decoder_stats --; all other streams hold nothing (adsb_stream_planes with streams == NULL: first[] =
+ * 0, n, n, ...).  adsb_stream_reset(s) resets stream s's framing state only; adsb_reset and adsb_streams_decoder_reset make
+ * the decoder fresh; an ADSB_STREAM_END item leaves it alone.
+ * NOT DONE: the same reply heard by several receivers is published once per hearing, as in the reference's fan-in: num_msgs
+ * counts every hearing.  De-duplication across receivers is the follow-up.
+ * ADSB_ABI_VERSION is unchanged: a flag and entry points only. */
+/* order[r]: the list position of the r-th record in the publication order of the last DELIVERED stream-batch call (*n = that
+ * call's *n_out; *order NULL when 0).  Pinned memory of the context, valid until the next DELIVERED stream-batch call: a
+ * call that fails leaves the pointer and what it points to alone.  -EINVAL on a
+ * context without ADSB_FLAG_STREAM_DECODE_SHARED or without open streams. */
+int adsb_stream_last_order(adsb_ctx* ctx, const int32_t** order, int32_t* n);
+/* A fresh shared decoder in O(1): a new generation of the store's key, as adsb_stream_reset gives one stream's decoder on a
+ * context without the shared flag.  The streams' framing state stays.  -EINVAL without ADSB_FLAG_STREAM_DECODE_SHARED or
+ * without open streams. */
+int adsb_streams_decoder_reset(adsb_ctx* ctx);
 int adsb_streams_set_decoder(adsb_ctx* ctx, int32_t msg_filter);   /* ADSB_DEC_*, for all streams; default ADSB_DEC_ALL_MESSAGES */
 int adsb_stream_set_start(adsb_ctx* ctx, int32_t stream, double start_timestamp);   /* fresh streams only; default 0 */
 /* Row t belongs to out[t] of the last DELIVERED adsb_process_stream_batch[_device] call (*n = that call's *n_out; *rows NULL

@@ -39,9 +39,7 @@ def build(specs):
     for spec in specs:
         name, flags = spec.split("=", 1)
         out = os.path.join(VDIR, "libadsb_%s.so" % name)
-        cmd = [b.hipcc()] + b.FLAGS + flags.split() + [os.path.join(b.CSRC, "adsb_hip.hip"), "-o", out]
-        print(" ".join(cmd))
-        subprocess.check_call(cmd)
+        b.compile_and_link(out, flags.split(), verbose=True)       # every translation unit of the library, with the extra flags
         with open(out + ".flags", "w") as f:
             f.write(flags)
 
