@@ -738,6 +738,22 @@ void launch_fec(hipStream_t st, const Slot& s, Rec* out, const Summary* sum) {
                      (Rec*)(s.host_cap > 0 ? s.h_out.p : nullptr), s.host_cap);
 }
 
+// The library's key sort (adsb_device.h: k_dec_sort_*): stable, by the bits [lo_bit, hi_bit), four a pass -- a block histogram
+// (hist: 16 words per tile of keys), one scan, a stable scatter, ping-pong between keys and sorted.  Both ranges in use give an
+// odd number of passes (seven: the decode steps' address and "no key" marker; eleven: the store's keys): the result ends in sorted.
+constexpr bool odd_passes(int lo_bit, int hi_bit) { return ((hi_bit - lo_bit + 3) / 4) % 2 == 1; }
+static_assert(odd_passes(32, 60) && odd_passes(0, kFleetAddrBits + kFleetStreamBits), "the key sort's result has to end in sorted");
+void launch_key_sort(hipStream_t st, unsigned long long* keys, unsigned long long* sorted, int n, int lo_bit, int hi_bit, unsigned* hist) {
+  const int nblk = (n + kSortTile - 1) / kSortTile;
+  for (int shift = lo_bit; shift < hi_bit; shift += 4) {
+    hipLaunchKernelGGL(k_dec_sort_hist, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)keys, n, shift, hist);
+    hipLaunchKernelGGL(k_dec_sort_scan, dim3(1), dim3(kThreads), 0, st, hist, nblk * 16);
+    hipLaunchKernelGGL(k_dec_sort_scatter, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)keys, sorted, n, shift,
+                       (const unsigned*)hist);
+    std::swap(keys, sorted);
+  }
+}
+
 // opt-in aircraft table (ADSB_FLAG_AIRCRAFT_TABLE): the table step of one published pass (list: out / mirror / sum; slices:
 // bits14 / ok, n = ntags), in stream order behind every earlier pass's step: the three slots run on their own streams, so
 // the step waits for the event recorded behind the previous one (pass n's verdict needs every announcement of passes < n)
@@ -757,16 +773,7 @@ int launch_dec(adsb_ctx* c, hipStream_t st, const AirArgs& a, unsigned g, DecRow
   d.air = a; d.ts = ts; d.start = c->dec_start; d.fs = c->fs; d.planes = c->d_planes; d.epoch = c->dec_epoch; d.all = c->dec_all;
   d.keys = (unsigned long long*)c->d_dec_keys.p; d.sorted = (const unsigned long long*)c->d_dec_sorted.p; d.rows = rows; d.seen = c->d_seen;
   hipLaunchKernelGGL(k_dec_classify, dim3(g), dim3(kThreads), 0, st, d);
-  unsigned long long* in = (unsigned long long*)c->d_dec_keys.p;
-  unsigned long long* out = (unsigned long long*)c->d_dec_sorted.p;
-  for (int shift = 32; shift < 60; shift += 4) {          // seven passes: the result ends in d_dec_sorted
-    hipLaunchKernelGGL(k_dec_sort_hist, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, (int)n, shift,
-                       (unsigned*)c->d_dec_tmp.p);
-    hipLaunchKernelGGL(k_dec_sort_scan, dim3(1), dim3(kThreads), 0, st, (unsigned*)c->d_dec_tmp.p, nblk * 16);
-    hipLaunchKernelGGL(k_dec_sort_scatter, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, out, (int)n, shift,
-                       (const unsigned*)c->d_dec_tmp.p);
-    unsigned long long* x = in; in = out; out = x;
-  }
+  launch_key_sort(st, (unsigned long long*)c->d_dec_keys.p, (unsigned long long*)c->d_dec_sorted.p, (int)n, 32, 60, (unsigned*)c->d_dec_tmp.p);
   if (d.seen) hipLaunchKernelGGL(k_ages_fold, dim3(g), dim3(kThreads), 0, st, d);
   else hipLaunchKernelGGL(k_dec_fold, dim3(g), dim3(kThreads), 0, st, d);
   return 0;
@@ -1820,15 +1827,7 @@ int fleet_step(adsb_ctx* c, const adsb_stream_item* items, int32_t n_items, cons
   hipLaunchKernelGGL(k_fleet_classify, dim3(g), dim3(kThreads), 0, st, a);
   // k_fleet_classify's timestamps are start + offset / fs with the ONE item's start: the true ones, in time order, over them
   if (shared) HIPCHK(c, hipMemcpyAsync(F.d_ts.p, sh.ts_sorted, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
-  unsigned long long* in = (unsigned long long*)F.d_keys.p;
-  unsigned long long* out = (unsigned long long*)F.d_sorted.p;
-  for (int shift = 32; shift < 60; shift += 4) {          // as launch_dec: seven passes, the result ends in d_sorted
-    hipLaunchKernelGGL(k_dec_sort_hist, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, (int)n, shift, (unsigned*)F.d_tmp.p);
-    hipLaunchKernelGGL(k_dec_sort_scan, dim3(1), dim3(kThreads), 0, st, (unsigned*)F.d_tmp.p, nblk * 16);
-    hipLaunchKernelGGL(k_dec_sort_scatter, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, out, (int)n, shift,
-                       (const unsigned*)F.d_tmp.p);
-    unsigned long long* x = in; in = out; out = x;
-  }
+  launch_key_sort(st, (unsigned long long*)F.d_keys.p, (unsigned long long*)F.d_sorted.p, (int)n, 32, 60, (unsigned*)F.d_tmp.p);      // as launch_dec
   hipLaunchKernelGGL(k_fleet_fold, dim3((unsigned)((nn + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, a);     // one thread per key
   HIPCHK(c, hipGetLastError());
   if (shared) {
@@ -2734,82 +2733,113 @@ int adsb_planes_expire(adsb_ctx* c, int64_t cutoff, int64_t* n_removed) {
   return 0;
 }
 
+// The fleet calls' stream selection: the decoders are open; streams null selects all of them (*n_sel = their number), else
+// *n_sel >= 0 indices, in range and strictly ascending.  api: the call's name in its refusals; cutoffs: null, or
+// adsb_stream_planes_expire's (that call's n_sel refusal covers a missing *cutoffs too)
+static int fleet_selection(adsb_ctx* c, const char* api, const int32_t* streams, int32_t* n_sel, const int64_t* const* cutoffs = nullptr) {
+  const auto refuse = [&](const char* what) { snprintf(c->err, sizeof(c->err), "%s: %s", api, what); return -EINVAL; };
+  if (!c->fd.open) return refuse("no streams (adsb_streams_open first)");
+  const size_t ns = c->fd.gen.size();
+  if (!streams) *n_sel = (int32_t)ns;
+  if (*n_sel < 0 || (cutoffs && *n_sel > 0 && !*cutoffs)) return refuse(cutoffs ? "n_sel < 0, or cutoffs missing" : "n_sel < 0");
+  for (int32_t i = 0; streams && i < *n_sel; ++i)
+    if (streams[i] < 0 || (size_t)streams[i] >= ns || (i > 0 && streams[i] <= streams[i - 1]))
+      return refuse("stream indices have to be in range and strictly ascending");
+  return 0;
+}
+
+// The staging block of a fleet readout, in F.d_snap behind what is queued: generations | selection bitmap | with_list: selection
+// list, first[] | count, error -- and room in F.d_keys / F.d_sorted for every live plane's key
+struct FleetStage {
+  PlanesFleet a{};
+  int *sel = nullptr, *first = nullptr, *cnt = nullptr;     // on the device: the list and first[] (with_list), (count, error)
+};
+static int fleet_stage(adsb_ctx* c, const int32_t* streams, int32_t n_sel, bool with_list, FleetStage* sg) {
+  FleetDec& F = c->fd;
+  const size_t ns = F.gen.size(), nsel = with_list ? (size_t)n_sel : 0;
+  const size_t o_bits = ns, o_sel = o_bits + (ns + 31) / 32, o_first = o_sel + nsel, o_cnt = o_first + (with_list ? nsel + 1 : 0), words = o_cnt + 2;
+  std::vector<unsigned> h(words, 0u);
+  for (size_t s = 0; s < ns; ++s) h[s] = F.gen[s];
+  for (int32_t i = 0; streams && i < n_sel; ++i) {
+    h[o_bits + (size_t)streams[i] / 32] |= 1u << ((unsigned)streams[i] & 31u);
+    if (with_list) h[o_sel + (size_t)i] = (unsigned)streams[i];
+  }
+  const long long key_cap = F.live_planes;                     // every live plane is counted there (fleet_step)
+  int rc;
+  if ((rc = ensure(c, F.d_snap, words * sizeof(unsigned))) || (rc = ensure(c, F.d_keys, (size_t)key_cap * 8)) ||
+      (rc = ensure(c, F.d_sorted, (size_t)key_cap * 8)))
+    return rc;
+  unsigned* const d = (unsigned*)F.d_snap.p;
+  HIPCHK(c, hipMemcpyAsync(d, h.data(), words * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+  sg->a.s = fleet_view(F.d_store.p, F.cap); sg->a.gen = d; sg->a.sel_bits = streams ? d + o_bits : nullptr; sg->a.n_streams = (int)ns;
+  sg->sel = (int*)(d + o_sel); sg->first = (int*)(d + o_first); sg->cnt = (int*)(d + o_cnt);
+  return 0;
+}
+
+// The selected planes' keys into F.d_keys (merge_seen null: k_planes_store_keys; else k_merge_keys, address-major, the planes
+// seen before cutoff left out), their count read back into *n and checked against the streams' books, and for 1 .. limit keys
+// the sort into F.d_sorted.  tmp_chunk: 0, or the keys per count of a later step that shares F.d_tmp with the sort.
+static int fleet_sorted_keys(adsb_ctx* c, const FleetStage& sg, const long long* merge_seen, long long cutoff, int limit, int tmp_chunk, int* n_keys) {
+  FleetDec& F = c->fd;
+  const hipStream_t st = c->stream;
+  const long long key_cap = F.live_planes;
+  if (merge_seen)
+    hipLaunchKernelGGL(k_merge_keys, dim3(step_grid(F.cap, kThreads)), dim3(kThreads), 0, st, sg.a, merge_seen, cutoff,
+                       (unsigned long long*)F.d_keys.p, (int)key_cap, sg.cnt);
+  else
+    hipLaunchKernelGGL(k_planes_store_keys, dim3(step_grid(F.cap, kThreads)), dim3(kThreads), 0, st, sg.a, (unsigned long long*)F.d_keys.p,
+                       (int)key_cap, sg.cnt);
+  HIPCHK(c, hipGetLastError());
+  int n = 0;
+  HIPCHK(c, hipMemcpyAsync(&n, sg.cnt, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if ((long long)n > key_cap) return fail(c, -EIO, "stream decoders: the store holds more planes than the streams count");
+  *n_keys = n;
+  if (n == 0 || n > limit) return 0;
+  const size_t nblk = ((size_t)n + kSortTile - 1) / kSortTile, n_counts = tmp_chunk ? ((size_t)n + tmp_chunk - 1) / tmp_chunk + 1 : 0;
+  int rc;
+  if ((rc = ensure(c, F.d_tmp, std::max(nblk * 16, n_counts) * sizeof(unsigned)))) return rc;
+  launch_key_sort(st, (unsigned long long*)F.d_keys.p, (unsigned long long*)F.d_sorted.p, n, 0, kFleetAddrBits + kFleetStreamBits, (unsigned*)F.d_tmp.p);
+  return 0;
+}
+
 static int planes_fleet(adsb_ctx* c, const int32_t* streams, int32_t n_sel, adsb_decoded* rows, int64_t* last_seen, bool ages,
                         int32_t cap, int32_t* first, int32_t* n_out) {
   int rc = planes_args(c, rows, cap, n_out, ages, last_seen);
   if (rc) return rc;
   if (!(c->flags & ADSB_FLAG_STREAM_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE");
-  FleetDec& F = c->fd;
-  if (!F.open) return fail(c, -EINVAL, "adsb_stream_planes: no streams (adsb_streams_open first)");
-  const size_t ns = F.gen.size();
-  if (!streams) n_sel = (int32_t)ns;
-  if (n_sel < 0) return fail(c, -EINVAL, "adsb_stream_planes: n_sel < 0");
-  for (int32_t i = 0; streams && i < n_sel; ++i)
-    if (streams[i] < 0 || (size_t)streams[i] >= ns || (i > 0 && streams[i] <= streams[i - 1]))
-      return fail(c, -EINVAL, "adsb_stream_planes: stream indices have to be in range and strictly ascending");
-  if ((rc = require_idle(c, kCallPending))) return rc;
+  if ((rc = fleet_selection(c, "adsb_stream_planes", streams, &n_sel)) || (rc = require_idle(c, kCallPending))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
+  FleetDec& F = c->fd;
   const hipStream_t st = c->stream;
-  // the staging block: generations | selection bitmap | selection list | first[] | count, error
-  const size_t nw = (ns + 31) / 32, nsel = (size_t)n_sel;
-  const size_t o_bits = ns, o_sel = o_bits + nw, o_first = o_sel + nsel, o_cnt = o_first + nsel + 1, words = o_cnt + 2;
-  std::vector<unsigned> h(words, 0u);
-  for (size_t s = 0; s < ns; ++s) h[s] = F.gen[s];
-  for (int32_t i = 0; streams && i < n_sel; ++i) {
-    h[o_bits + (size_t)streams[i] / 32] |= 1u << ((unsigned)streams[i] & 31u);
-    h[o_sel + (size_t)i] = (unsigned)streams[i];
-  }
-  const long long key_cap = F.live_planes;                     // every live plane is counted there (fleet_step)
-  if ((rc = ensure(c, F.d_snap, words * sizeof(unsigned))) || (rc = ensure(c, F.d_keys, (size_t)key_cap * 8)) ||
-      (rc = ensure(c, F.d_sorted, (size_t)key_cap * 8)))
-    return rc;
-  unsigned* const d = (unsigned*)F.d_snap.p;
-  HIPCHK(c, hipMemcpyAsync(d, h.data(), words * sizeof(unsigned), hipMemcpyHostToDevice, st));
-  PlanesFleet a{};
-  a.s = fleet_view(F.d_store.p, F.cap); a.gen = d; a.sel_bits = streams ? d + o_bits : nullptr; a.n_streams = (int)ns;
-  int* const d_cnt = (int*)(d + o_cnt);
-  hipLaunchKernelGGL(k_planes_store_keys, dim3(step_grid(F.cap, kThreads)), dim3(kThreads), 0, st, a, (unsigned long long*)F.d_keys.p,
-                     (int)key_cap, d_cnt);
-  HIPCHK(c, hipGetLastError());
-  int got[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(got, d_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  const int n = got[0];
-  if ((long long)n > key_cap) return fail(c, -EIO, "stream decoders: the store holds more planes than the streams count");
+  const size_t nsel = (size_t)n_sel;
+  FleetStage sg;
+  int n = 0;
+  if ((rc = fleet_stage(c, streams, n_sel, true, &sg)) || (rc = fleet_sorted_keys(c, sg, nullptr, 0, cap, 0, &n))) return rc;
   *n_out = n;
   if (n > cap) return fail(c, -ENOSPC, "adsb_stream_planes: cap is smaller than the number of planes (*n_out)");
   if (n == 0) {
     if (first) memset(first, 0, (nsel + 1) * sizeof(int32_t));
     return 0;
   }
-  const int nblk = (n + kSortTile - 1) / kSortTile;
-  if ((rc = ensure(c, F.d_tmp, (size_t)nblk * 16 * sizeof(unsigned))) || (rows && (rc = ensure(c, F.d_rows, (size_t)n * sizeof(DecRow)))) ||
-      (last_seen && (rc = ensure(c, F.d_ages, (size_t)n * sizeof(long long)))))
+  if ((rows && (rc = ensure(c, F.d_rows, (size_t)n * sizeof(DecRow)))) || (last_seen && (rc = ensure(c, F.d_ages, (size_t)n * sizeof(long long)))))
     return rc;
-  unsigned long long* in = (unsigned long long*)F.d_keys.p;
-  unsigned long long* out = (unsigned long long*)F.d_sorted.p;
-  for (int shift = 0; shift < kFleetAddrBits + kFleetStreamBits; shift += 4) {          // eleven passes: the result ends in d_sorted
-    hipLaunchKernelGGL(k_dec_sort_hist, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, n, shift, (unsigned*)F.d_tmp.p);
-    hipLaunchKernelGGL(k_dec_sort_scan, dim3(1), dim3(kThreads), 0, st, (unsigned*)F.d_tmp.p, nblk * 16);
-    hipLaunchKernelGGL(k_dec_sort_scatter, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, out, n, shift,
-                       (const unsigned*)F.d_tmp.p);
-    unsigned long long* x = in; in = out; out = x;
-  }
+  const int* const sel = streams ? sg.sel : nullptr;
+  int* const d_first = first ? sg.first : nullptr;
   const unsigned eg = step_grid(std::max((long long)n, (long long)nsel + 1), kThreads);
   if (!ages)
-    hipLaunchKernelGGL(k_planes_store_emit, dim3(eg), dim3(kThreads), 0, st, a,
-                       (const unsigned long long*)F.d_sorted.p, n, streams ? (const int*)(d + o_sel) : (const int*)nullptr, (int)n_sel,
-                       (DecRow*)F.d_rows.p, first ? (int*)(d + o_first) : (int*)nullptr, d_cnt + 1);
+    hipLaunchKernelGGL(k_planes_store_emit, dim3(eg), dim3(kThreads), 0, st, sg.a, (const unsigned long long*)F.d_sorted.p, n, sel, (int)n_sel,
+                       (DecRow*)F.d_rows.p, d_first, sg.cnt + 1);
   else
-    hipLaunchKernelGGL(k_ages_store_emit, dim3(eg), dim3(kThreads), 0, st, a,
-                       (const unsigned long long*)F.d_sorted.p, n, streams ? (const int*)(d + o_sel) : (const int*)nullptr, (int)n_sel,
-                       rows ? (DecRow*)F.d_rows.p : (DecRow*)nullptr, first ? (int*)(d + o_first) : (int*)nullptr, d_cnt + 1,
+    hipLaunchKernelGGL(k_ages_store_emit, dim3(eg), dim3(kThreads), 0, st, sg.a, (const unsigned long long*)F.d_sorted.p, n, sel, (int)n_sel,
+                       rows ? (DecRow*)F.d_rows.p : (DecRow*)nullptr, d_first, sg.cnt + 1,
                        (const long long*)fleet_seen(c, F.d_store.p, F.cap), last_seen ? (long long*)F.d_ages.p : (long long*)nullptr);
   HIPCHK(c, hipGetLastError());
+  int got[2] = {0, 0};
   if (rows) HIPCHK(c, hipMemcpyAsync(rows, F.d_rows.p, (size_t)n * sizeof(DecRow), hipMemcpyDeviceToHost, st));
   if (last_seen) HIPCHK(c, hipMemcpyAsync(last_seen, F.d_ages.p, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost, st));
-  if (first) HIPCHK(c, hipMemcpyAsync(first, d + o_first, (nsel + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(got, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (first) HIPCHK(c, hipMemcpyAsync(first, sg.first, (nsel + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(got, sg.cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   if (got[1]) return fail(c, -EIO, "stream decoders: the snapshot found a plane without a slot");
   return 0;
@@ -2829,18 +2859,11 @@ int adsb_stream_planes_expire(adsb_ctx* c, const int32_t* streams, int32_t n_sel
   if (!c) return -EINVAL;
   if (!(c->flags & ADSB_FLAG_STREAM_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE");
   if (!(c->flags & ADSB_FLAG_PLANE_AGES)) return fail(c, -EINVAL, "context created without ADSB_FLAG_PLANE_AGES");
-  FleetDec& F = c->fd;
-  if (!F.open) return fail(c, -EINVAL, "adsb_stream_planes_expire: no streams (adsb_streams_open first)");
-  const size_t ns = F.gen.size();
-  if (!streams) n_sel = (int32_t)ns;
-  if (n_sel < 0 || (n_sel > 0 && !cutoffs)) return fail(c, -EINVAL, "adsb_stream_planes_expire: n_sel < 0, or cutoffs missing");
-  for (int32_t i = 0; streams && i < n_sel; ++i)
-    if (streams[i] < 0 || (size_t)streams[i] >= ns || (i > 0 && streams[i] <= streams[i - 1]))
-      return fail(c, -EINVAL, "adsb_stream_planes_expire: stream indices have to be in range and strictly ascending");
-  int rc = require_idle(c, kCallPending);
-  if (rc) return rc;
+  int rc;
+  if ((rc = fleet_selection(c, "adsb_stream_planes_expire", streams, &n_sel, &cutoffs)) || (rc = require_idle(c, kCallPending))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  std::vector<long long> cut(ns, LLONG_MIN);                       // (nothing is below it: an unselected stream loses nothing)
+  FleetDec& F = c->fd;
+  std::vector<long long> cut(F.gen.size(), LLONG_MIN);                       // (nothing is below it: an unselected stream loses nothing)
   for (int32_t i = 0; i < n_sel; ++i) cut[streams ? (size_t)streams[i] : (size_t)i] = (long long)cutoffs[i];
   long long total = 0;
   if ((rc = fleet_rehash(c, F.cap, false, cut.data(), &total))) return rc;
@@ -2857,56 +2880,21 @@ int adsb_stream_planes_merged(adsb_ctx* c, const int32_t* streams, int32_t n_sel
   if (!(c->flags & ADSB_FLAG_STREAM_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE");
   if (!(c->flags & ADSB_FLAG_PLANE_AGES)) return fail(c, -EINVAL, "context created without ADSB_FLAG_PLANE_AGES");
   if (!n_out || cap < 0 || (cap > 0 && !rows && !info)) return fail(c, -EINVAL, "adsb_stream_planes_merged: n_out, or rows / info for cap > 0, missing");
-  FleetDec& F = c->fd;
-  if (!F.open) return fail(c, -EINVAL, "adsb_stream_planes_merged: no streams (adsb_streams_open first)");
-  const size_t ns = F.gen.size();
-  if (!streams) n_sel = (int32_t)ns;
-  if (n_sel < 0) return fail(c, -EINVAL, "adsb_stream_planes_merged: n_sel < 0");
-  for (int32_t i = 0; streams && i < n_sel; ++i)
-    if (streams[i] < 0 || (size_t)streams[i] >= ns || (i > 0 && streams[i] <= streams[i - 1]))
-      return fail(c, -EINVAL, "adsb_stream_planes_merged: stream indices have to be in range and strictly ascending");
-  int rc = require_idle(c, kCallPending);
-  if (rc) return rc;
+  int rc;
+  if ((rc = fleet_selection(c, "adsb_stream_planes_merged", streams, &n_sel)) || (rc = require_idle(c, kCallPending))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
+  FleetDec& F = c->fd;
   const hipStream_t st = c->stream;
-  // the staging block: generations | selection bitmap | count, error
-  const size_t nw = (ns + 31) / 32, o_bits = ns, o_cnt = o_bits + nw, words = o_cnt + 2;
-  std::vector<unsigned> h(words, 0u);
-  for (size_t s = 0; s < ns; ++s) h[s] = F.gen[s];
-  for (int32_t i = 0; streams && i < n_sel; ++i) h[o_bits + (size_t)streams[i] / 32] |= 1u << ((unsigned)streams[i] & 31u);
-  const long long key_cap = F.live_planes;                     // every live plane is counted there (fleet_step)
-  if ((rc = ensure(c, F.d_snap, words * sizeof(unsigned))) || (rc = ensure(c, F.d_keys, (size_t)key_cap * 8)) ||
-      (rc = ensure(c, F.d_sorted, (size_t)key_cap * 8)))
-    return rc;
-  unsigned* const d = (unsigned*)F.d_snap.p;
-  HIPCHK(c, hipMemcpyAsync(d, h.data(), words * sizeof(unsigned), hipMemcpyHostToDevice, st));
-  PlanesFleet a{};
-  a.s = fleet_view(F.d_store.p, F.cap); a.gen = d; a.sel_bits = streams ? d + o_bits : nullptr; a.n_streams = (int)ns;
   const long long* const seen = fleet_seen(c, F.d_store.p, F.cap);
-  int* const d_cnt = (int*)(d + o_cnt);
-  hipLaunchKernelGGL(k_merge_keys, dim3(step_grid(F.cap, kThreads)), dim3(kThreads), 0, st, a, seen, (long long)cutoff,
-                     (unsigned long long*)F.d_keys.p, (int)key_cap, d_cnt);
-  HIPCHK(c, hipGetLastError());
-  int got[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(got, d_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  const int n = got[0];
-  if ((long long)n > key_cap) return fail(c, -EIO, "stream decoders: the store holds more planes than the streams count");
+  FleetStage sg;
+  int n = 0;
+  if ((rc = fleet_stage(c, streams, n_sel, false, &sg)) || (rc = fleet_sorted_keys(c, sg, seen, (long long)cutoff, INT_MAX, kMergeChunk, &n)))
+    return rc;
   if (n == 0) {
     *n_out = 0;
     return 0;
   }
-  const int nblk = (n + kSortTile - 1) / kSortTile, n_chunks = (n + kMergeChunk - 1) / kMergeChunk;
-  if ((rc = ensure(c, F.d_tmp, std::max((size_t)nblk * 16, (size_t)n_chunks + 1) * sizeof(unsigned)))) return rc;
-  unsigned long long* in = (unsigned long long*)F.d_keys.p;
-  unsigned long long* out = (unsigned long long*)F.d_sorted.p;
-  for (int shift = 0; shift < kFleetAddrBits + kFleetStreamBits; shift += 4) {          // eleven passes: the result ends in d_sorted
-    hipLaunchKernelGGL(k_dec_sort_hist, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, n, shift, (unsigned*)F.d_tmp.p);
-    hipLaunchKernelGGL(k_dec_sort_scan, dim3(1), dim3(kThreads), 0, st, (unsigned*)F.d_tmp.p, nblk * 16);
-    hipLaunchKernelGGL(k_dec_sort_scatter, dim3(nblk), dim3(kThreads), 0, st, (const unsigned long long*)in, out, n, shift,
-                       (const unsigned*)F.d_tmp.p);
-    unsigned long long* x = in; in = out; out = x;
-  }
+  const int n_chunks = (n + kMergeChunk - 1) / kMergeChunk;
   const unsigned eg = step_grid(n, kThreads);
   hipLaunchKernelGGL(k_merge_heads, dim3(eg), dim3(kThreads), 0, st, (const unsigned long long*)F.d_sorted.p, n, (unsigned*)F.d_tmp.p);
   hipLaunchKernelGGL(k_dec_sort_scan, dim3(1), dim3(kThreads), 0, st, (unsigned*)F.d_tmp.p, n_chunks + 1);
@@ -2919,13 +2907,14 @@ int adsb_stream_planes_merged(adsb_ctx* c, const int32_t* streams, int32_t n_sel
   if (total > (unsigned)cap) return fail(c, -ENOSPC, "adsb_stream_planes_merged: cap is smaller than the number of aircraft (*n_out)");
   if ((rows && (rc = ensure(c, F.d_rows, (size_t)total * sizeof(DecRow)))) || (info && (rc = ensure(c, F.d_merged, (size_t)total * sizeof(MergedInfo)))))
     return rc;
-  hipLaunchKernelGGL(k_merge_emit, dim3(eg), dim3(kThreads), 0, st, a, (const unsigned long long*)F.d_sorted.p, n,
+  hipLaunchKernelGGL(k_merge_emit, dim3(eg), dim3(kThreads), 0, st, sg.a, (const unsigned long long*)F.d_sorted.p, n,
                      (const unsigned*)F.d_tmp.p, seen, rows ? (DecRow*)F.d_rows.p : (DecRow*)nullptr,
-                     info ? (MergedInfo*)F.d_merged.p : (MergedInfo*)nullptr, d_cnt + 1);
+                     info ? (MergedInfo*)F.d_merged.p : (MergedInfo*)nullptr, sg.cnt + 1);
   HIPCHK(c, hipGetLastError());
+  int got[2] = {0, 0};
   if (rows) HIPCHK(c, hipMemcpyAsync(rows, F.d_rows.p, (size_t)total * sizeof(DecRow), hipMemcpyDeviceToHost, st));
   if (info) HIPCHK(c, hipMemcpyAsync(info, F.d_merged.p, (size_t)total * sizeof(MergedInfo), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(got, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(got, sg.cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   if (got[1]) return fail(c, -EIO, "stream decoders: the merged picture found a plane without a slot");
   return 0;

@@ -175,7 +175,7 @@ def test_decoded_pdu_equals_reference(g, tag, filt, corr):
 
 # ---- the emulated kernels ----------------------------------------------------------------------------------------------------
 def dec_lib():
-    srcs = [os.path.join(SIM_DIR, "decode_driver.cpp"), os.path.join(SIM_DIR, "hipsim.h"),
+    srcs = [os.path.join(SIM_DIR, "decode_driver.cpp"), os.path.join(SIM_DIR, "sim_support.h"), os.path.join(SIM_DIR, "hipsim.h"),
             os.path.join(HERE, "..", "gr_adsb_amd", "csrc", "adsb_device.h")]
     if not (os.path.exists(DEC_SO) and all(os.path.getmtime(DEC_SO) >= os.path.getmtime(s) for s in srcs)):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unknown-pragmas",

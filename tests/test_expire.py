@@ -35,7 +35,8 @@ vp = ctypes.c_void_p
 
 
 def expire_lib():
-    srcs = [os.path.join(SIM_DIR, f) for f in ("expire_driver.cpp", "planes_driver.cpp", "fleet_driver.cpp", "decode_driver.cpp", "hipsim.h")] + \
+    srcs = [os.path.join(SIM_DIR, f) for f in ("expire_driver.cpp", "planes_driver.cpp", "fleet_driver.cpp", "decode_driver.cpp", "sim_support.h",
+                                               "hipsim.h")] + \
         [os.path.join(HERE, "..", "gr_adsb_amd", "csrc", "adsb_device.h")]
     if not (os.path.exists(EXPIRE_SO) and all(os.path.getmtime(EXPIRE_SO) >= os.path.getmtime(s) for s in srcs)):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unknown-pragmas",

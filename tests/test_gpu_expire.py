@@ -414,6 +414,62 @@ def test_fleet_refusals_and_untouched_state(native):
     plain.close()
 
 
+def test_fleet_selection_refusals_by_text_and_snapshots_in_parts(native):
+    """The stream selection of adsb_stream_planes / _seen / _expire, refusal by refusal, by adsb_last_error's text, and which of
+    two mistakes at once is named: no streams before the selection, n_sel before the indices (the expiry: missing cutoffs
+    with it), the selection before -EBUSY.  Then the snapshot with ages in parts: an empty selection zeroes its first[],
+    -ENOSPC leaves the count, rows alone and last_seen alone are those of the whole call."""
+    vp, ref = ctypes.c_void_p, ctypes.byref
+    rng = np.random.default_rng(86)
+    c = N.Context(FS, THR, flags=SD | AGES)
+    lib, h = c.lib, c._h
+    n32, n64 = ctypes.c_int32(-7), ctypes.c_int64(-7)
+    bad, cut = np.array([2, 0], np.int32), np.zeros(3, np.int64)
+    badp, cutp = vp(bad.ctypes.data), vp(cut.ctypes.data)
+
+    def planes(sp, k):
+        return lib.adsb_stream_planes(h, sp, k, None, 0, None, ref(n32)), lib.adsb_last_error(h).decode()
+
+    def seen(sp, k):
+        return lib.adsb_stream_planes_seen(h, sp, k, None, None, 0, None, ref(n32)), lib.adsb_last_error(h).decode()
+
+    def expire(sp, k, cp):
+        return lib.adsb_stream_planes_expire(h, sp, k, cp, ref(n64)), lib.adsb_last_error(h).decode()
+    closed = "%s: no streams (adsb_streams_open first)"
+    assert planes(badp, -1) == seen(badp, -1) == (-EINVAL, closed % "adsb_stream_planes")
+    assert expire(badp, -1, None) == (-EINVAL, closed % "adsb_stream_planes_expire")
+    c.open_streams(3)
+    iq = stream(np.array([ident(0x10 + k, rng) for k in range(12)], np.uint8), FS)[0]
+    tk = c.submit_format_host(N.FMT_FC32, iq)                                   # busy: a bad selection is still named first
+    order = "%s: stream indices have to be in range and strictly ascending"
+    assert planes(badp, -1) == seen(badp, -1) == (-EINVAL, "adsb_stream_planes: n_sel < 0")
+    assert planes(badp, 2) == seen(badp, 2) == (-EINVAL, order % "adsb_stream_planes")
+    missing = (-EINVAL, "adsb_stream_planes_expire: n_sel < 0, or cutoffs missing")
+    assert expire(badp, -1, cutp) == missing and expire(badp, 2, None) == missing and expire(None, 0, None) == missing
+    assert expire(badp, 2, cutp) == (-EINVAL, order % "adsb_stream_planes_expire")
+    assert planes(None, 0)[0] == seen(None, 0)[0] == expire(None, 0, cutp)[0] == expire(badp, 0, None)[0] == -EBUSY
+    c.wait(tk)
+    first = np.full(4, 0x55555555, np.int32)
+    sel = np.array([0, 2], np.int32)
+    assert lib.adsb_stream_planes_seen(h, vp(sel.ctypes.data), 2, None, None, 0, vp(first.ctypes.data), ref(n32)) == 0
+    assert n32.value == 0 and first.tolist() == [0, 0, 0, 0x55555555]
+    for s in range(3):
+        c.set_stream_start(s, 500.5 + 100 * s)
+    c.process_stream_batch(N.FMT_FC32, [0, 1, 2], [iq] * 3, end=True)
+    rows, ages, f0 = c.stream_planes(seen=True)
+    assert len(rows) == 36 and list(f0) == [0, 12, 24, 36]
+    r, a = np.zeros(36, N.DECODED_DTYPE), np.zeros(36, np.int64)
+    r.view(np.uint8)[:] = 0x77
+    assert lib.adsb_stream_planes_seen(h, None, 0, vp(r.ctypes.data), vp(a.ctypes.data), 35, vp(first.ctypes.data), ref(n32)) == -ENOSPC
+    assert lib.adsb_last_error(h).decode() == "adsb_stream_planes: cap is smaller than the number of planes (*n_out)"
+    assert n32.value == 36 and (r.view(np.uint8) == 0x77).all() and not a.any() and first.tolist() == [0, 0, 0, 0x55555555]
+    assert lib.adsb_stream_planes_seen(h, None, 0, vp(r.ctypes.data), None, 36, vp(first.ctypes.data), ref(n32)) == 0
+    assert r.tobytes() == rows.tobytes() and first.tolist() == [0, 12, 24, 36] and not a.any()
+    assert lib.adsb_stream_planes_seen(h, vp(sel.ctypes.data), 2, None, vp(a.ctypes.data), 36, None, ref(n32)) == 0
+    assert n32.value == 24 and a[:24].tolist() == ages[:12].tolist() + ages[24:].tolist() and not a[24:].any()
+    c.close()
+
+
 def test_decoder_block_with_a_plane_timeout(native, ge):
     """blocks.decoder(plane_timeout=60) on the device: the model with the sweep last_seen < int(timestamp) - 60 in front of
     every PDU; plane_dict carries last_seen; the default block sweeps nothing."""

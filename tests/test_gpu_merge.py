@@ -254,6 +254,31 @@ def test_refusals_cap_rules_and_untouched_state(native):
     c.close(); twin.close()
 
 
+def test_selection_refusals_by_text_and_which_comes_first(native):
+    """adsb_stream_planes_merged's refusals by adsb_last_error's text, and which of two mistakes at once is named: the missing
+    n_out before everything about the streams, no streams before the selection, n_sel before the indices, the selection
+    before -EBUSY."""
+    vp = ctypes.c_void_p
+    c = N.Context(FS, THR, flags=SD | AGES)
+    n32 = ctypes.c_int32(-7)
+    bad = np.array([2, 0], np.int32)
+
+    def merged(k, n_out=n32):
+        rc = c.lib.adsb_stream_planes_merged(c._h, vp(bad.ctypes.data), k, 0, None, None, 0, None if n_out is None else ctypes.byref(n_out))
+        return rc, c.lib.adsb_last_error(c._h).decode()
+    assert merged(-1, None) == (-EINVAL, "adsb_stream_planes_merged: n_out, or rows / info for cap > 0, missing")
+    assert merged(-1) == (-EINVAL, "adsb_stream_planes_merged: no streams (adsb_streams_open first)")
+    c.open_streams(3)
+    iq = stream(np.array([ident(0x10 + k, np.random.default_rng(96)) for k in range(4)], np.uint8), FS)[0]
+    tk = c.submit_format_host(N.FMT_FC32, iq)                                   # busy: a bad selection is still named first
+    assert merged(-1) == (-EINVAL, "adsb_stream_planes_merged: n_sel < 0")
+    assert merged(2) == (-EINVAL, "adsb_stream_planes_merged: stream indices have to be in range and strictly ascending")
+    assert merged(0)[0] == merged(1)[0] == -EBUSY
+    c.wait(tk)
+    assert merged(1)[0] == 0 and n32.value == 0                                 # stream 2 alone: nothing heard yet
+    c.close()
+
+
 def test_merged_around_an_expiry(native):
     rng = np.random.default_rng(94)
     f = Fleet(3)

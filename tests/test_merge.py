@@ -41,7 +41,7 @@ SRC = ("src_callsign", "src_altitude", "src_velocity", "src_position")
 
 def merge_lib():
     srcs = [os.path.join(SIM_DIR, f) for f in ("merge_driver.cpp", "expire_driver.cpp", "planes_driver.cpp", "fleet_driver.cpp",
-                                               "decode_driver.cpp", "hipsim.h")] + \
+                                               "decode_driver.cpp", "sim_support.h", "hipsim.h")] + \
         [os.path.join(HERE, "..", "gr_adsb_amd", "csrc", "adsb_device.h")]
     if not (os.path.exists(MERGE_SO) and all(os.path.getmtime(MERGE_SO) >= os.path.getmtime(s) for s in srcs)):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unknown-pragmas",

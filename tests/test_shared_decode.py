@@ -33,8 +33,8 @@ vp = ctypes.c_void_p
 
 def shared_lib():
     csrc = os.path.join(HERE, "..", "gr_adsb_amd", "csrc")
-    srcs = [os.path.join(SIM_DIR, "shared_driver.cpp"), os.path.join(SIM_DIR, "hipsim.h"), os.path.join(csrc, "adsb_device.h"),
-            os.path.join(csrc, "adsb_shared_device.h")]
+    srcs = [os.path.join(SIM_DIR, f) for f in ("shared_driver.cpp", "fleet_driver.cpp", "sim_support.h", "hipsim.h")] + \
+        [os.path.join(csrc, "adsb_device.h"), os.path.join(csrc, "adsb_shared_device.h")]
     if not (os.path.exists(SHARED_SO) and all(os.path.getmtime(SHARED_SO) >= os.path.getmtime(s) for s in srcs)):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unknown-pragmas",
                                srcs[0], "-o", SHARED_SO])

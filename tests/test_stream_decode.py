@@ -29,7 +29,7 @@ MIN_CAP = 256
 
 
 def fleet_lib():
-    srcs = [os.path.join(SIM_DIR, "fleet_driver.cpp"), os.path.join(SIM_DIR, "hipsim.h"),
+    srcs = [os.path.join(SIM_DIR, "fleet_driver.cpp"), os.path.join(SIM_DIR, "sim_support.h"), os.path.join(SIM_DIR, "hipsim.h"),
             os.path.join(HERE, "..", "gr_adsb_amd", "csrc", "adsb_device.h")]
     if not (os.path.exists(FLEET_SO) and all(os.path.getmtime(FLEET_SO) >= os.path.getmtime(s) for s in srcs)):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unknown-pragmas",
