@@ -27,6 +27,7 @@ FLAG_AIRCRAFT_TABLE = 256    # opt-in: the decoder's aircraft table on the devic
 FLAG_DECODE = 512            # opt-in (with FLAG_AIRCRAFT_TABLE): the decoder's message decoding and plane fields on the device
 FLAG_STREAM_DECODE = 1024    # opt-in: one decoder behind every receiver stream (open_streams), one device step per stream-batch call
 FLAG_STREAM_DECODE_SHARED = 4096   # opt-in, with FLAG_STREAM_DECODE: ONE decoder behind all streams, fed every call's records in time order
+FLAG_STREAM_DEDUP = 8192     # opt-in, with FLAG_STREAM_DECODE | FLAG_STREAM_DECODE_SHARED: a reply heard by several receivers is published once
 FLAG_PLANE_AGES = 2048       # opt-in, with FLAG_DECODE or FLAG_STREAM_DECODE: plane_dict's last_seen on the device (planes(seen=True), expire_*)
 # include/adsb_hip.h adsb_decoded: one row per delivered record of a FLAG_DECODE context
 DECODED_DTYPE = np.dtype([("port", "u1"), ("df", "u1"), ("present", "u1"), ("pad0", "u1"), ("icao", "<i4"), ("bits", "u1", (14,)),
@@ -35,6 +36,7 @@ DECODED_DTYPE = np.dtype([("port", "u1"), ("df", "u1"), ("present", "u1"), ("pad
                           ("num_msgs", "<u4"), ("pad2", "<u4")])
 assert DECODED_DTYPE.itemsize == 72
 DEC_NONE, DEC_DECODED, DEC_UNKNOWN, DEC_RAISED = 0, 1, 2, 3
+DEC_DUPLICATE = 4            # FLAG_STREAM_DEDUP: another receiver's hearing of this reply was published, this one was not
 DEC_HAS_PLANE, DEC_HAS_CALLSIGN, DEC_HAS_ALTITUDE, DEC_HAS_VELOCITY = 1, 2, 4, 8
 DEC_MSG_FILTERS = {"All Messages": 0, "Extended Squitter Only": 1}
 ABI_VERSION = 5
@@ -87,6 +89,7 @@ EXPORTS = [
     "adsb_stream_decoder_stats", "adsb_planes", "adsb_stream_planes",
     "adsb_planes_seen", "adsb_stream_planes_seen", "adsb_planes_expire", "adsb_stream_planes_expire",
     "adsb_stream_planes_merged", "adsb_stream_last_order", "adsb_streams_decoder_reset",
+    "adsb_streams_set_dedup", "adsb_stream_last_duplicates", "adsb_stream_dedup_stats",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
 ]
 
@@ -190,6 +193,9 @@ def load():
     lib.adsb_stream_last_decoded.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
     lib.adsb_stream_last_order.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
     lib.adsb_streams_decoder_reset.argtypes = [vp]
+    lib.adsb_streams_set_dedup.argtypes = [vp, c.c_double, c.c_double]
+    lib.adsb_stream_last_duplicates.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
+    lib.adsb_stream_dedup_stats.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(c.c_double)]
     lib.adsb_stream_decoder_reserve.argtypes = [vp, i64]
     lib.adsb_stream_decoder_stats.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
     lib.adsb_planes.argtypes = [vp, vp, i32, c.POINTER(i32)]
@@ -583,6 +589,27 @@ class Context:
     def reset_streams_decoder(self):
         """A fresh shared decoder; the streams' framing state stays (adsb_streams_decoder_reset)."""
         self._chk(self.lib.adsb_streams_decoder_reset(self._h))
+
+    # FLAG_STREAM_DEDUP contexts (include/adsb_hip.h DE-DUPLICATION)
+    def set_streams_dedup(self, window_s=0.002, horizon_s=1.0):
+        """The rule's window and the carry's horizon, in seconds, before the first delivered call (adsb_streams_set_dedup)."""
+        self._chk(self.lib.adsb_streams_set_dedup(self._h, float(window_s), float(horizon_s)))
+
+    def last_stream_duplicates(self):
+        """int32[n] for the last delivered stream-batch call: -1 position t is no duplicate, -2 its match lies in an earlier
+        call, else the list position of the earliest-published match of this call (adsb_stream_last_duplicates)."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int32(0)
+        self._chk(self.lib.adsb_stream_last_duplicates(self._h, ctypes.byref(p), ctypes.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=np.int32)
+        return np.frombuffer((ctypes.c_char * (n.value * 4)).from_address(p.value), dtype=np.int32).copy()
+
+    def stream_dedup_stats(self):
+        """(duplicates since the decoder was fresh, entries the carry holds, hi: the largest delivered timestamp)"""
+        d, k, h = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0)
+        self._chk(self.lib.adsb_stream_dedup_stats(self._h, ctypes.byref(d), ctypes.byref(k), ctypes.byref(h)))
+        return d.value, k.value, h.value
 
     def stream_decoder_reserve(self, slots):
         """The capacity of the decoders' store, while it holds nothing (adsb_stream_decoder_reserve)."""

@@ -9,8 +9,10 @@ LIB = os.path.join(HERE, "libadsb_hip.so")
 SOURCES = ["adsb_hip.hip"]
 # ADSB_FLAG_STREAM_DECODE_SHARED's kernels: a translation unit of its own, so that adsb_hip.hip's kernels compile as without it
 SHARED_SOURCE = "adsb_shared.hip"
+# ADSB_FLAG_STREAM_DEDUP's kernels: a third unit, for the same reason
+DEDUP_SOURCE = "adsb_dedup.hip"
 DEPS = ["adsb_hip.hip", "adsb_device.h", "adsb_plan.h", os.path.join("..", "..", "include", "adsb_hip.h"),
-        "adsb_shared.hip", "adsb_shared.h", "adsb_shared_device.h"]
+        "adsb_shared.hip", "adsb_shared.h", "adsb_shared_device.h", "adsb_dedup.hip", "adsb_dedup.h", "adsb_dedup_device.h"]
 # -ffp-contract=off: |IQ|^2 must be two rounded products and one rounded add
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread"]
 
@@ -31,6 +33,7 @@ def up_to_date():
 
 RES = os.path.join(HERE, "kernel_resources.json")
 RES_SHARED = os.path.join(HERE, "kernel_resources_shared.json")
+RES_DEDUP = os.path.join(HERE, "kernel_resources_dedup.json")
 
 
 def _parse_resources(remarks):
@@ -52,15 +55,15 @@ def _parse_resources(remarks):
 
 
 def compile_and_link(out, extra_flags=(), verbose=False):
-    """Both translation units, each compiled with FLAGS + extra_flags side by side, linked into the shared library `out`
-    (libadsb_hip.so, or a side copy: tools/kbench.py) -> [the compiler's output per unit, SOURCES first].  The objects live
+    """The translation units, each compiled with FLAGS + extra_flags side by side, linked into the shared library `out`
+    (libadsb_hip.so, or a side copy: tools/kbench.py) -> [the compiler's output per unit: SOURCES, SHARED_SOURCE, DEDUP_SOURCE].  The objects live
     in a temporary directory."""
     import shutil
     import tempfile
     compile_flags = [f for f in FLAGS if f != "-shared"] + list(extra_flags)
     tmp = tempfile.mkdtemp(prefix="adsb_build_")
     try:
-        units = [(os.path.join(CSRC, s), os.path.join(tmp, s + ".o")) for s in SOURCES + [SHARED_SOURCE]]
+        units = [(os.path.join(CSRC, s), os.path.join(tmp, s + ".o")) for s in SOURCES + [SHARED_SOURCE, DEDUP_SOURCE]]
         jobs = []
         for src, obj in units:
             cmd = [hipcc()] + compile_flags + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", obj]
@@ -87,13 +90,13 @@ def compile_and_link(out, extra_flags=(), verbose=False):
 def build(force=False, verbose=False):
     """hipcc -> libadsb_hip.so, and beside it kernel_resources.json: the compiler's per-kernel register / LDS / scratch
     report (tests/test_abi.py holds the limits the pipeline relies on: k_detect must leave the tail kernels room), and
-    kernel_resources_shared.json: the same for adsb_shared.hip's kernels."""
-    if not force and up_to_date() and os.path.exists(RES) and os.path.exists(RES_SHARED):
+    kernel_resources_shared.json / kernel_resources_dedup.json: the same for adsb_shared.hip's and adsb_dedup.hip's kernels."""
+    if not force and up_to_date() and all(os.path.exists(p) for p in (RES, RES_SHARED, RES_DEDUP)):
         return LIB
     import json
     remarks = compile_and_link(LIB, verbose=verbose)
     assert len(SOURCES) == 1
-    for path, text in zip((RES, RES_SHARED), remarks):
+    for path, text in zip((RES, RES_SHARED, RES_DEDUP), remarks):
         with open(path, "w") as f:
             json.dump(_parse_resources(text), f, indent=1, sort_keys=True)
     return LIB

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "adsb_shared.h"
+#include "adsb_dedup.h"
 
 // wavefront-level ordering point used by adsb_device.h: LDS traffic of one wavefront is executed in
 // program order by the hardware, this only stops the compiler from moving LDS accesses across it
@@ -317,12 +318,27 @@ struct FleetDec {
   PinnedBuf h_shared, h_order;                  // ... the items' first[] | start[] on their way up, order[] of the last delivered call
   PinnedBuf h_order_next;                       // ... and where a call's order[] arrives: the two change places once the call is delivered
   int32_t n_rows = 0;                           // rows of the last delivered call
+  // ADSB_FLAG_STREAM_DEDUP (adsb_dedup.hip): the carry is d_carry[cur][off .. off + cnt), entries of 32 bytes in time order.
+  // A call merges into the other buffer and changes cur / off / cnt / hi only once it is delivered.
+  struct Dedup {
+    double window = 0.002, horizon = 1.0, hi = 0;
+    int cur = 0, off = 0, cnt = 0;
+    long long duplicates = 0;
+    bool delivered = false;                     // a call with records since the decoder was last fresh
+    DevBuf d_carry[2];
+    DevBuf d_call;                              // one call's entries[n] | dup[n] | item_stream[n_items]
+    PinnedBuf h_dup, h_dup_next;                // dup[] of the last delivered call / where a call's arrives (as h_order)
+    void fresh() { hi = 0; off = cnt = 0; duplicates = 0; delivered = false; }
+  } dd;
 };
 constexpr long long kFleetMinCap = 256, kFleetDefaultCap = 1ll << 16, kFleetMaxCap = 1ll << 27;    // (slot index 2^28 - 1 would sort with kDecNoKey)
 constexpr size_t kFleetSlotBytes = 16 + sizeof(Plane);
 static_assert(sizeof(Rec) == adsb_shared_host::kRecBytes && sizeof(DecRow) == adsb_shared_host::kRowBytes,
               "adsb_shared.hip moves records and rows as opaque words of these sizes");
 static_assert(offsetof(Rec, w) == 0 && kSortTile == adsb_shared_host::kSortTile, "a record's offset is its word 0; one sort tile");
+static_assert(sizeof(Rec) == adsb_dedup_host::kRecBytes && sizeof(DecRow) == adsb_dedup_host::kRowBytes && offsetof(DecRow, port) == 0 &&
+              ADSB_DEC_DUPLICATE == 4u && kDemod == ADSB_BURST_DEMOD && kLongFmt == ADSB_BURST_LONG,
+              "adsb_dedup.hip reads a record's flags in word 3 and writes a row's port in byte 0");
 // ADSB_FLAG_STREAM_DECODE_SHARED: d_shared carved for a call of n records in n_items items, every part on a 256-byte boundary
 struct SharedBufs {
   unsigned long long *keys = nullptr, *keys_tmp = nullptr;
@@ -1710,6 +1726,7 @@ int fleet_reset_stream(adsb_ctx* c, size_t s) {
   FleetDec& F = c->fd;
   F.live_slots -= F.slots[s]; F.live_planes -= F.planes[s];
   F.slots[s] = F.planes[s] = 0;
+  if (s == 0 && (c->flags & ADSB_FLAG_STREAM_DEDUP)) F.dd.fresh();      // (a shared decoder lives under index 0: adsb_streams_decoder_reset, adsb_reset)
   if (F.gen[s] < kFleetGenMax) { ++F.gen[s]; return 0; }
   F.gen[s] = ~0u;                               // (no key holds it: the rehash drops every slot of the stream)
   HIPCHK(c, hipSetDevice(c->device));
@@ -1725,6 +1742,7 @@ int fleet_open(adsb_ctx* c, size_t n) {
   F.start.assign(n, 0.0); F.gen.assign(n, 0u); F.slots.assign(n, 0); F.planes.assign(n, 0);
   F.used = F.live_slots = F.live_planes = F.grows = 0;
   F.call = 0; F.n_rows = 0; F.all = 1;
+  F.dd.fresh(); F.dd.window = 0.002; F.dd.horizon = 1.0; F.dd.cur = 0;
   F.open = true;
   return 0;
 }
@@ -1732,8 +1750,8 @@ int fleet_close(adsb_ctx* c) {
   FleetDec& F = c->fd;
   F.open = false; F.cap = 0; F.n_rows = 0;
   F.start.clear(); F.gen.clear(); F.slots.clear(); F.planes.clear();
-  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen, &F.d_snap, &F.d_ages, &F.d_merged, &F.d_shared}) HIPCHK(c, b->release());
-  for (PinnedBuf* b : {&F.h_recs, &F.h_rows, &F.h_items, &F.h_cnt, &F.h_shared, &F.h_order, &F.h_order_next}) HIPCHK(c, b->release());
+  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen, &F.d_snap, &F.d_ages, &F.d_merged, &F.d_shared, &F.dd.d_carry[0], &F.dd.d_carry[1], &F.dd.d_call}) HIPCHK(c, b->release());
+  for (PinnedBuf* b : {&F.h_recs, &F.h_rows, &F.h_items, &F.h_cnt, &F.h_shared, &F.h_order, &F.h_order_next, &F.dd.h_dup, &F.dd.h_dup_next}) HIPCHK(c, b->release());
   return 0;
 }
 
@@ -1743,6 +1761,10 @@ int fleet_close(adsb_ctx* c) {
 // ADSB_FLAG_STREAM_DECODE_SHARED: one decoder for all streams.  The list is put into the order ascending (timestamp, list
 // position) first (adsb_shared.hip), the same kernels run on that list as ONE item of stream 0, and the verdict flags and
 // rows go back to list positions; F.h_order holds the order of the last call that was delivered (a call that fails here leaves it).
+// ADSB_FLAG_STREAM_DEDUP (include/adsb_hip.h: DE-DUPLICATION): between the gather and k_fleet_announce the duplicates lose
+// ADSB_BURST_DEMOD in the time-ordered copy, and the call's entries are merged with the carry into the carry's other buffer;
+// behind the scatter the duplicates' delivered records and rows are marked.  The cut's {offset, count, hi} comes down behind
+// the counts in h_cnt; the host takes it, and the other buffer, only when the call is delivered.
 int fleet_step(adsb_ctx* c, const adsb_stream_item* items, int32_t n_items, const int32_t* item_first, const adsb_burst* recs, int32_t n) {
   FleetDec& F = c->fd;
   const hipStream_t st = c->stream;
@@ -1751,11 +1773,21 @@ int fleet_step(adsb_ctx* c, const adsb_stream_item* items, int32_t n_items, cons
   const bool shared = (c->flags & ADSB_FLAG_STREAM_DECODE_SHARED) != 0;
   const size_t nn = (size_t)n, ni = shared ? 1 : (size_t)n_items;      // ni: the items of the decode step's own table
   const int nblk = (int)((nn + kSortTile - 1) / kSortTile);
-  const size_t shared_tab = ((size_t)n_items + 1) * sizeof(int) + (size_t)n_items * sizeof(double);
+  const bool dedup = shared && (c->flags & ADSB_FLAG_STREAM_DEDUP) != 0;
+  FleetDec::Dedup& D = F.dd;
+  // first[n_items + 1] | start[n_items] (| the items' streams[n_items])
+  const size_t shared_tab = ((size_t)n_items + 1) * sizeof(int) + (size_t)n_items * sizeof(double) + (dedup ? (size_t)n_items * sizeof(int) : 0);
+  const size_t dd_dup = nn * adsb_dedup_host::kEntBytes, dd_streams = dd_dup + ((nn * sizeof(int) + 255) & ~(size_t)255);
+  if (dedup && ((r = ensure(c, D.d_call, dd_streams + (size_t)n_items * sizeof(int))) ||
+                (r = ensure(c, D.d_carry[D.cur ^ 1], ((size_t)D.cnt + nn) * adsb_dedup_host::kEntBytes)) ||
+                (r = ensure_pinned(c, D.h_dup_next, nn * sizeof(int)))))
+    return r;
+  if (dedup && (long long)D.cnt + n >= (1ll << 31)) return fail(c, -ENOMEM, "shared decoder: the de-duplication carry would exceed 2^31 entries");
   if (shared && ((r = ensure(c, F.d_shared, SharedBufs::bytes(nn, (size_t)n_items))) || (r = ensure_pinned(c, F.h_shared, shared_tab)) ||
                  (r = ensure_pinned(c, F.h_order_next, nn * sizeof(int)))))
     return r;
-  const size_t cnt_bytes = ni * sizeof(FleetCount) + (ni + 2) * sizeof(int);
+  const size_t cnt_head = ni * sizeof(FleetCount) + (ni + 2) * sizeof(int), dd_state = (cnt_head + 7) & ~(size_t)7;
+  const size_t cnt_bytes = dedup ? dd_state + sizeof(adsb_dedup_host::State) : cnt_head;
   if ((r = ensure(c, F.d_recs, nn * sizeof(Rec))) || (r = ensure(c, F.d_items, (ni + 1) * sizeof(FleetItem))) ||
       (r = ensure(c, F.d_cnt, cnt_bytes)) || (r = ensure(c, F.d_keys, nn * 8)) || (r = ensure(c, F.d_sorted, nn * 8)) ||
       (r = ensure(c, F.d_tmp, (size_t)nblk * 16 * sizeof(unsigned))) || (r = ensure(c, F.d_ts, nn * 8)) || (r = ensure(c, F.d_rows, nn * sizeof(DecRow))) ||
@@ -1809,6 +1841,19 @@ int fleet_step(adsb_ctx* c, const adsb_stream_item* items, int32_t n_items, cons
         (e = (hipError_t)adsb_shared_host::launch_sort(st, sh.keys, sh.vals, sh.keys_tmp, sh.vals_tmp, n, sh.hist)) ||
         (e = (hipError_t)adsb_shared_host::launch_gather(st, F.d_recs.p, sh.ts, sh.vals, n, sh.recs, sh.ts_sorted, sh.order)))
       return fail(c, -EIO, "shared decoder: the time order's kernels", e);
+    if (dedup) {
+      char* const call = (char*)D.d_call.p;
+      int* const hstreams = (int*)((char*)F.h_shared.p + ((size_t)n_items + 1) * sizeof(int) + (size_t)n_items * sizeof(double));
+      for (int32_t i = 0; i < n_items; ++i) hstreams[i] = items[i].stream;
+      HIPCHK(c, hipMemcpyAsync(call + dd_streams, hstreams, (size_t)n_items * sizeof(int), hipMemcpyHostToDevice, st));
+      const char* const carry = (const char*)D.d_carry[D.cur].p + (size_t)D.off * adsb_dedup_host::kEntBytes;     // (null while cnt == 0: never read)
+      if ((e = (hipError_t)adsb_dedup_host::launch_entries(st, sh.recs, sh.ts_sorted, sh.order, n, sh.first, (const int*)(call + dd_streams),
+                                                           n_items, call)) ||
+          (e = (hipError_t)adsb_dedup_host::launch_find(st, call, n, carry, D.cnt, D.window, sh.order, sh.recs, (int*)(call + dd_dup))) ||
+          (e = (hipError_t)adsb_dedup_host::launch_merge(st, carry, D.cnt, call, n, D.horizon, D.d_carry[D.cur ^ 1].p,
+                                                         (char*)F.d_cnt.p + dd_state)))
+        return fail(c, -EIO, "shared decoder: the de-duplication kernels", e);
+    }
   }
   FleetArgs a{};
   a.recs = shared ? sh.recs : (Rec*)F.d_recs.p; a.n = n; a.n_items = (int)ni; a.items = (const FleetItem*)F.d_items.p;
@@ -1831,9 +1876,15 @@ int fleet_step(adsb_ctx* c, const adsb_stream_item* items, int32_t n_items, cons
   hipLaunchKernelGGL(k_fleet_fold, dim3((unsigned)((nn + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, a);     // one thread per key
   HIPCHK(c, hipGetLastError());
   if (shared) {
+    hipError_t e2;
     const hipError_t e = (hipError_t)adsb_shared_host::launch_scatter(st, sh.recs, sh.rows, sh.order, n, F.d_recs.p, F.d_rows.p);
     if (e) return fail(c, -EIO, "shared decoder: k_shared_scatter", e);
     HIPCHK(c, hipMemcpyAsync(F.h_order_next.p, sh.order, nn * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (dedup) {
+      const int* const dup = (const int*)((const char*)D.d_call.p + dd_dup);
+      if ((e2 = (hipError_t)adsb_dedup_host::launch_mark(st, dup, n, F.d_recs.p, F.d_rows.p))) return fail(c, -EIO, "shared decoder: k_dedup_mark", e2);
+      HIPCHK(c, hipMemcpyAsync(D.h_dup_next.p, dup, nn * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
   }
   HIPCHK(c, hipMemcpyAsync(F.h_recs.p, F.d_recs.p, nn * sizeof(Rec), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipMemcpyAsync(F.h_rows.p, F.d_rows.p, nn * sizeof(DecRow), hipMemcpyDeviceToHost, st));
@@ -1841,6 +1892,11 @@ int fleet_step(adsb_ctx* c, const adsb_stream_item* items, int32_t n_items, cons
   HIPCHK(c, hipStreamSynchronize(st));
   const FleetCount* const hc = (const FleetCount*)F.h_cnt.p;
   if (((const int*)(hc + ni))[ni + 1] != 0) return fail(c, -EIO, "stream decoders: the decode step found the store inconsistent");
+  adsb_dedup_host::State ds{};
+  if (dedup) {                                   // before anything is committed: a call that fails leaves order[], dup[] and the carry alone
+    memcpy(&ds, (const char*)F.h_cnt.p + dd_state, sizeof ds);
+    if (ds.off < 0 || ds.cnt < 1 || (long long)ds.off + ds.cnt != (long long)D.cnt + n) return fail(c, -EIO, "shared decoder: the de-duplication carry's cut is inconsistent");
+  }
   for (size_t i = 0; i < ni; ++i) {
     const size_t s = shared ? 0 : (size_t)items[i].stream;
     F.slots[s] += hc[i].slots; F.planes[s] += hc[i].planes;
@@ -1849,6 +1905,12 @@ int fleet_step(adsb_ctx* c, const adsb_stream_item* items, int32_t n_items, cons
   F.call++;
   F.n_rows = n;
   if (shared) { std::swap(F.h_order.p, F.h_order_next.p); std::swap(F.h_order.cap, F.h_order_next.cap); }      // delivered
+  if (dedup) {
+    std::swap(D.h_dup.p, D.h_dup_next.p); std::swap(D.h_dup.cap, D.h_dup_next.cap);
+    const int* const dup = (const int*)D.h_dup.p;
+    for (size_t t = 0; t < nn; ++t) D.duplicates += dup[t] != -1;
+    D.cur ^= 1; D.off = ds.off; D.cnt = ds.cnt; D.hi = ds.hi; D.delivered = true;
+  }
   return 0;
 }
 
@@ -2124,6 +2186,7 @@ int adsb_create(double fs, float threshold, int device, uint32_t flags, adsb_ctx
   if ((flags & ADSB_FLAG_STREAM_DECODE) && (flags & (ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE | ADSB_FLAG_CONFIDENCE))) return -EINVAL;
   if ((flags & ADSB_FLAG_PLANE_AGES) && !(flags & (ADSB_FLAG_DECODE | ADSB_FLAG_STREAM_DECODE))) return -EINVAL;   // no planes to age
   if ((flags & ADSB_FLAG_STREAM_DECODE_SHARED) && !(flags & ADSB_FLAG_STREAM_DECODE)) return -EINVAL;           // no decoder to share
+  if ((flags & ADSB_FLAG_STREAM_DEDUP) && !(flags & ADSB_FLAG_STREAM_DECODE_SHARED)) return -EINVAL;             // one decoder, or nothing is heard twice
   if (!out) return -EINVAL;
   *out = nullptr;
   if (!(fs > 0) || fmod(fs, 1e6) != 0.0) return -EINVAL;        // framer.py:44, demod.py:42
@@ -2447,6 +2510,35 @@ int adsb_stream_last_order(adsb_ctx* c, const int32_t** order, int32_t* n) {
   if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_last_order: no streams (adsb_streams_open first)");
   if (order) *order = c->fd.n_rows > 0 ? (const int32_t*)c->fd.h_order.p : nullptr;
   if (n) *n = c->fd.n_rows;
+  return 0;
+}
+
+int adsb_streams_set_dedup(adsb_ctx* c, double window_s, double horizon_s) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
+  if (!c->fd.open) return fail(c, -EINVAL, "adsb_streams_set_dedup: no streams (adsb_streams_open first)");
+  if (!(window_s >= 0) || !(horizon_s >= window_s)) return fail(c, -EINVAL, "adsb_streams_set_dedup: 0 <= window_s <= horizon_s, no NaN");
+  if (c->fd.dd.delivered) return fail(c, -EINVAL, "adsb_streams_set_dedup: a call has been delivered since the decoder was fresh");
+  c->fd.dd.window = window_s; c->fd.dd.horizon = horizon_s;
+  return 0;
+}
+
+int adsb_stream_last_duplicates(adsb_ctx* c, const int32_t** dup, int32_t* n) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
+  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_last_duplicates: no streams (adsb_streams_open first)");
+  if (dup) *dup = c->fd.n_rows > 0 ? (const int32_t*)c->fd.dd.h_dup.p : nullptr;
+  if (n) *n = c->fd.n_rows;
+  return 0;
+}
+
+int adsb_stream_dedup_stats(adsb_ctx* c, int64_t* duplicates, int64_t* carried, double* hi) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
+  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_dedup_stats: no streams (adsb_streams_open first)");
+  if (duplicates) *duplicates = c->fd.dd.duplicates;
+  if (carried) *carried = c->fd.dd.cnt;
+  if (hi) *hi = c->fd.dd.hi;
   return 0;
 }
 

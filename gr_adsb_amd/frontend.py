@@ -150,12 +150,13 @@ class FrontEnd:
         return self.ctx.last_batch_fallbacks
 
     # -- many receivers that go on: streams carried across batch calls -----------------------------------
-    def receivers(self, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False):
+    def receivers(self, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False, dedup=False):
         """n receiver streams on this context (Receivers below).  fmt: one of _native.FMT_*, or None: by the arrays' dtype.
         starts / msg_filter: FLAG_STREAM_DECODE contexts, the streams' start timestamps and their decoders' msg_filter.
         ages: the context also has FLAG_PLANE_AGES (ValueError otherwise): .planes(seen=True) and .expire(cutoffs).
-        shared: the context also has FLAG_STREAM_DECODE_SHARED (ValueError otherwise): ONE decoder behind all n streams."""
-        return Receivers(self.ctx, n, fmt, starts, msg_filter, ages, shared)
+        shared: the context also has FLAG_STREAM_DECODE_SHARED (ValueError otherwise): ONE decoder behind all n streams.
+        dedup: True, or (window_s, horizon_s): the context also has FLAG_STREAM_DEDUP (ValueError otherwise)."""
+        return Receivers(self.ctx, n, fmt, starts, msg_filter, ages, shared, dedup)
 
     def shard_tensor(self, t, origin, own_lo, own_hi, stream_len, fmt=0, head_cands=0):
         _after_torch(self.ctx, t)
@@ -196,15 +197,22 @@ class Receivers:
     as above -- each row what the one decoder made of that record --, .order holds the publication order of the last push /
     finish as positions in the concatenation of the returned record arrays, and planes(), merged(), table() and expire()
     address the one plane table: planes() returns ONE row array (seen=True: one (rows, last_seen) pair), expire() takes one
-    cutoff, and none of them takes ids.  The same reply heard by several receivers counts once per hearing."""
+    cutoff, and none of them takes ids.  The same reply heard by several receivers counts once per hearing,
+    unless dedup (a context that also has FLAG_STREAM_DEDUP; True, or (window_s, horizon_s) for other than 0.002 s and 1.0 s):
+    then it is published once, the other hearings' rows have port DEC_DUPLICATE, and .duplicates holds, beside .order, -1 /
+    -2 (the match lies in an earlier push) / the position of the earliest-published match of the last push or finish."""
 
-    def __init__(self, ctx, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False):
+    def __init__(self, ctx, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False, dedup=False):
         self.ctx, self.n, self.fmt = ctx, int(n), fmt
         self.decode = bool(getattr(ctx, "flags", 0) & _native.FLAG_STREAM_DECODE)
         self.ages = bool(ages)
         self.shared = bool(shared)
         self.rows = []
         self.order = np.zeros(0, dtype=np.int32)
+        self.dedup = dedup is not False and dedup is not None
+        self.duplicates = np.zeros(0, dtype=np.int32)
+        if self.dedup != bool(getattr(ctx, "flags", 0) & _native.FLAG_STREAM_DEDUP):
+            raise ValueError("dedup needs, and its absence excludes, a FLAG_STREAM_DEDUP context")
         if self.shared != bool(getattr(ctx, "flags", 0) & _native.FLAG_STREAM_DECODE_SHARED):
             raise ValueError("shared=True needs, and shared=False excludes, a FLAG_STREAM_DECODE | FLAG_STREAM_DECODE_SHARED context")
         if self.ages and not (self.decode and getattr(ctx, "flags", 0) & _native.FLAG_PLANE_AGES):
@@ -217,6 +225,8 @@ class Receivers:
                 ctx.set_streams_decoder(msg_filter)
             for i, t in enumerate(starts if starts is not None else []):
                 ctx.set_stream_start(i, t)
+        if self.dedup and dedup is not True:
+            ctx.set_streams_dedup(*dedup)
 
     def _run(self, arrays, ids, thresholds, end):
         ids = list(range(len(arrays))) if ids is None else [int(i) for i in ids]
@@ -224,6 +234,7 @@ class Receivers:
         if not ids:
             self.rows = []
             self.order = np.zeros(0, dtype=np.int32)
+            self.duplicates = np.zeros(0, dtype=np.int32)
             return []
         arrays = [np.asarray(a) for a in arrays]
         fmt = self._last_fmt = self.fmt if self.fmt is not None else _FMT_OF_DTYPE[arrays[0].dtype]
@@ -233,6 +244,8 @@ class Receivers:
             self.rows = [rows[first[i]:first[i + 1]] for i in range(len(ids))]
         if self.shared:
             self.order = self.ctx.last_stream_order()
+        if self.dedup:
+            self.duplicates = self.ctx.last_stream_duplicates()
         return [recs[first[i]:first[i + 1]] for i in range(len(ids))]
 
     def push(self, arrays, ids=None, thresholds=None):

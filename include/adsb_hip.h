@@ -143,6 +143,10 @@ extern "C" {
  * would decode it.  Combines with ADSB_FLAG_FEC_CONSERVATIVE, _LONG_AWARE_GATE and _PLANE_AGES exactly as
  * ADSB_FLAG_STREAM_DECODE does.  Without the flag nothing is allocated or launched and no byte of any existing call changes. */
 #define ADSB_FLAG_STREAM_DECODE_SHARED 4096u
+/* Shared decoders only (valid together with ADSB_FLAG_STREAM_DECODE | ADSB_FLAG_STREAM_DECODE_SHARED, adsb_create returns
+ * -EINVAL otherwise): a reply heard by several receivers is published once -- see DE-DUPLICATION below.  Without the flag
+ * nothing is allocated or launched and no byte of any call changes. */
+#define ADSB_FLAG_STREAM_DEDUP 8192u
 
 /* adsb_burst.flags */
 #define ADSB_BURST_DEMOD 1u /* eob inside the demod input: bits[] valid, a PDU is published (demod.py:82) */
@@ -184,6 +188,7 @@ typedef struct adsb_burst {
 #define ADSB_DEC_DECODED 1u   /* published on "decoded" (decoder.py:512-526): the plane's fields below */
 #define ADSB_DEC_UNKNOWN 2u   /* published on "unknown" (:529-538) */
 #define ADSB_DEC_RAISED 3u    /* decode_packet raises before it publishes: DF 18 CF 2/3/5, TC 19 ST 0/5/6/7 */
+#define ADSB_DEC_DUPLICATE 4u /* ADSB_FLAG_STREAM_DEDUP: another receiver's hearing of this reply was published; this one was not */
 #define ADSB_DEC_HAS_PLANE 1u     /* plane_dict[icao] exists after the PDU: the fields below are its snapshot */
 #define ADSB_DEC_HAS_CALLSIGN 2u  /* callsign is not None */
 #define ADSB_DEC_HAS_ALTITUDE 4u  /* altitude is not NaN */
@@ -571,8 +576,8 @@ int adsb_process_stream_batch_device(adsb_ctx* ctx, int format, const adsb_strea
  * adsb_stream_decoder_stats --; all other streams hold nothing (adsb_stream_planes with streams == NULL: first[] =
  * 0, n, n, ...).  adsb_stream_reset(s) resets stream s's framing state only; adsb_reset and adsb_streams_decoder_reset make
  * the decoder fresh; an ADSB_STREAM_END item leaves it alone.
- * NOT DONE: the same reply heard by several receivers is published once per hearing, as in the reference's fan-in: num_msgs
- * counts every hearing.  De-duplication across receivers is the follow-up.
+ * The same reply heard by several receivers is published once per hearing, as in the reference's fan-in: num_msgs counts
+ * every hearing -- unless the context has ADSB_FLAG_STREAM_DEDUP: see DE-DUPLICATION below.
  * ADSB_ABI_VERSION is unchanged: a flag and entry points only. */
 /* order[r]: the list position of the r-th record in the publication order of the last DELIVERED stream-batch call (*n = that
  * call's *n_out; *order NULL when 0).  Pinned memory of the context, valid until the next DELIVERED stream-batch call: a
@@ -584,6 +589,45 @@ int adsb_stream_last_order(adsb_ctx* ctx, const int32_t** order, int32_t* n);
  * without open streams. */
 int adsb_streams_decoder_reset(adsb_ctx* ctx);
 int adsb_streams_set_decoder(adsb_ctx* ctx, int32_t msg_filter);   /* ADSB_DEC_*, for all streams; default ADSB_DEC_ALL_MESSAGES */
+/* DE-DUPLICATION (ADSB_FLAG_STREAM_DEDUP on a shared decoder): a reply that k receivers hear is published once, not k times.
+ * THE RULE.  A record TAKES PART if it has ADSB_BURST_DEMOD.  Its PAYLOAD is its bits[] as the decode step receives them
+ * (with ADSB_BURST_FEC_FIXED: the repaired reply): the first 112 bits if ADSB_BURST_LONG is set, otherwise the first 56 bits
+ * only -- a short reply's bytes 7..13 are sliced noise and differ between receivers.  Two payloads are equal when their
+ * lengths and those bits are equal.  With ts[t] = start[stream] + (double)offset / fs as above, record r is a DUPLICATE iff
+ * there is a record q that takes part, is EARLIER IN PUBLICATION ORDER (an earlier delivered call, or the same call and
+ * earlier in ascending (ts, list position)), is still held by the carry (below), comes from a DIFFERENT STREAM, has an equal
+ * payload, and satisfies fabs(ts[r] - ts[q]) <= window, evaluated in double with exactly that expression.  q may itself be
+ * a duplicate: the rule depends on the inputs only, never on earlier verdicts, so one thread per record evaluates it.
+ * CONSEQUENCES.  Of a set of hearings from distinct streams that lie pairwise within window, exactly the first in
+ * publication order is published, for any chunking within the horizon.  The same payload twice on the SAME stream is two
+ * transmissions: both are published.  A context with one stream never marks anything.
+ * A DUPLICATE publishes nothing: no slot, no plane update, no num_msgs, no last_seen.  Its delivered record is that of a
+ * context without a decoder (ADSB_BURST_DEMOD kept, never ADSB_BURST_AP_KNOWN / _AP_FEC); its row is the row of a record
+ * without ADSB_BURST_DEMOD with port = ADSB_DEC_DUPLICATE; it keeps its place in order[].
+ * EQUIVALENCE, extending the shared decoder's: the flags and rows of all other records are byte-identical to ONE reference
+ * decoder fed the publication sequence with the duplicates left out.
+ * THE CARRY.  The hearings of one reply fall into different calls, so the context keeps a time-sorted carry on the device:
+ * every record of earlier delivered calls (duplicates included) with ts >= hi - horizon, where hi is the largest timestamp
+ * of any record delivered since the decoder was last fresh; the cut is applied at the end of each delivered call, with that
+ * double expression.  A record of a later call is compared against carry entries on both sides in time (hence the fabs).
+ * A hearing that arrives after hi has moved more than horizon past it is published again: that is the bound.
+ * adsb_streams_decoder_reset and adsb_reset clear the carry and hi; adsb_stream_reset (framing only), ADSB_STREAM_END items,
+ * adsb_stream_planes_expire and any call that fails (-ENOSPC, any error) leave both alone.
+ * COST: O(n x records within window) comparisons per call, plus O((n + carried) log) for the merge: the whole carry -- every
+ * record of the last `horizon` seconds -- is read and rewritten by every delivered call, so a long horizon on a dense fleet is
+ * what a call pays for (DESIGN.md 3h measures it).
+ * adsb_streams_set_dedup: window_s and horizon_s in seconds.  Defaults 0.002 and 1.0: 400 km of differential path are 1.3 ms,
+ * the rest is clock error between receivers; the horizon covers the lag between the receivers' deliveries.  window = 0 is
+ * legal: bit-equal timestamps only.  -EINVAL for NaN, negative values or horizon < window; without the flag or without open
+ * streams; and once a call with records has been delivered since the decoder was last fresh. */
+int adsb_streams_set_dedup(adsb_ctx* ctx, double window_s, double horizon_s);
+/* Beside adsb_stream_last_order, with its lifetime rules: dup[t] of the last DELIVERED call.  -1: position t is not a
+ * duplicate; -2: some matching q lies in an earlier call; otherwise the list position of the earliest-published matching q
+ * of this call. */
+int adsb_stream_last_duplicates(adsb_ctx* ctx, const int32_t** dup, int32_t* n);
+/* duplicates: since the decoder was last fresh; carried: entries the carry holds now; hi: as above (0 while nothing has been
+ * delivered).  Any pointer may be NULL.  -EINVAL without the flag or without open streams. */
+int adsb_stream_dedup_stats(adsb_ctx* ctx, int64_t* duplicates, int64_t* carried, double* hi);
 int adsb_stream_set_start(adsb_ctx* ctx, int32_t stream, double start_timestamp);   /* fresh streams only; default 0 */
 /* Row t belongs to out[t] of the last DELIVERED adsb_process_stream_batch[_device] call (*n = that call's *n_out; *rows NULL
  * when 0).  Pinned memory of the context, valid until the next stream-batch call. */
