@@ -69,6 +69,13 @@ assert STREAM_ITEM_DTYPE.itemsize == 32
 MERGED_DTYPE = np.dtype([("last_seen", "<i8"), ("n_streams", "<i4"), ("src_callsign", "<i4"), ("src_altitude", "<i4"),
                          ("src_velocity", "<i4"), ("src_position", "<i4"), ("pad", "<i4")])
 assert MERGED_DTYPE.itemsize == 32
+# one row of adsb_stream_mlat (adsb_mlat_fix): the members of row j are member_stream / member_ts[first .. first + n_rx)
+MLAT_DTYPE = np.dtype([("ts", "<f8"), ("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("t_tx", "<f8"), ("rms_m", "<f8"), ("bits", "u1", (14,)),
+                       ("flags", "<u2"), ("icao", "<i4"), ("n_rx", "<i4"), ("n_heard", "<i4"), ("status", "<i4"), ("iters", "<i4"),
+                       ("first", "<i4")])
+assert MLAT_DTYPE.itemsize == 88
+MLAT_OK, MLAT_NO_CONVERGE, MLAT_SINGULAR = 0, 1, 2       # ADSB_MLAT_*
+MLAT_C = 299702547.0         # ADSB_MLAT_C, m/s
 INT64_MIN = -(1 << 63)       # the cutoff that hides nothing
 STREAM_END = 1               # ADSB_STREAM_END: the stream's last item
 STREAM_FRESH_EOB = -(1 << 61)    # the carried end-of-burst offset of a fresh stream
@@ -90,6 +97,7 @@ EXPORTS = [
     "adsb_planes_seen", "adsb_stream_planes_seen", "adsb_planes_expire", "adsb_stream_planes_expire",
     "adsb_stream_planes_merged", "adsb_stream_last_order", "adsb_streams_decoder_reset",
     "adsb_streams_set_dedup", "adsb_stream_last_duplicates", "adsb_stream_dedup_stats",
+    "adsb_stream_set_ecef", "adsb_stream_mlat", "adsb_stream_mlat_stats", "adsb_geodetic_to_ecef", "adsb_ecef_to_geodetic",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
 ]
 
@@ -118,6 +126,20 @@ class AdsbError(RuntimeError):
 
 
 _lib = None
+
+
+def geodetic_to_ecef(lat_deg, lon_deg, alt_m):
+    """WGS-84 degrees and metres -> ECEF (x, y, z) in metres (adsb_geodetic_to_ecef: plain host arithmetic)."""
+    x, y, z = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    load().adsb_geodetic_to_ecef(float(lat_deg), float(lon_deg), float(alt_m), ctypes.byref(x), ctypes.byref(y), ctypes.byref(z))
+    return x.value, y.value, z.value
+
+
+def ecef_to_geodetic(x, y, z):
+    """ECEF metres -> WGS-84 (latitude, longitude, altitude) in degrees and metres (adsb_ecef_to_geodetic)."""
+    la, lo, al = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    load().adsb_ecef_to_geodetic(float(x), float(y), float(z), ctypes.byref(la), ctypes.byref(lo), ctypes.byref(al))
+    return la.value, lo.value, al.value
 
 
 def load():
@@ -196,6 +218,13 @@ def load():
     lib.adsb_streams_set_dedup.argtypes = [vp, c.c_double, c.c_double]
     lib.adsb_stream_last_duplicates.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
     lib.adsb_stream_dedup_stats.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(c.c_double)]
+    lib.adsb_stream_set_ecef.argtypes = [vp, i32, c.c_double, c.c_double, c.c_double]
+    lib.adsb_stream_mlat.argtypes = [vp, c.c_double, c.c_double, i32, vp, i32, c.POINTER(i32), vp, vp, i32, c.POINTER(i32)]
+    lib.adsb_stream_mlat_stats.argtypes = [vp, c.POINTER(i32), c.POINTER(c.c_double)]
+    lib.adsb_geodetic_to_ecef.argtypes = [c.c_double] * 3 + [c.POINTER(c.c_double)] * 3
+    lib.adsb_geodetic_to_ecef.restype = None
+    lib.adsb_ecef_to_geodetic.argtypes = [c.c_double] * 3 + [c.POINTER(c.c_double)] * 3
+    lib.adsb_ecef_to_geodetic.restype = None
     lib.adsb_stream_decoder_reserve.argtypes = [vp, i64]
     lib.adsb_stream_decoder_stats.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
     lib.adsb_planes.argtypes = [vp, vp, i32, c.POINTER(i32)]
@@ -610,6 +639,35 @@ class Context:
         d, k, h = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0)
         self._chk(self.lib.adsb_stream_dedup_stats(self._h, ctypes.byref(d), ctypes.byref(k), ctypes.byref(h)))
         return d.value, k.value, h.value
+
+    # multilateration on the de-duplication carry (include/adsb_hip.h MULTILATERATION)
+    def set_stream_ecef(self, stream, x, y, z):
+        """The antenna of `stream` in WGS-84 ECEF metres (adsb_stream_set_ecef); geodetic_to_ecef converts."""
+        self._chk(self.lib.adsb_stream_set_ecef(self._h, int(stream), float(x), float(y), float(z)))
+
+    def stream_mlat(self, t_lo=-np.inf, t_hi=np.inf, min_rx=4, cap=0, member_cap=0):
+        """-> (fixes: MLAT_DTYPE[n], member_stream: int32[m], member_ts: float64[m]) for the groups of the carry whose head has
+        t_lo <= ts < t_hi and at least min_rx used hearings (adsb_stream_mlat).  The call is repeated once with the capacity
+        it asks for after -ENOSPC; cap / member_cap: where to start."""
+        cap, member_cap = int(cap), int(member_cap)
+        n, m = ctypes.c_int32(0), ctypes.c_int32(0)
+        for attempt in (0, 1):
+            fixes = np.zeros(cap, dtype=MLAT_DTYPE)
+            ms, mt = np.zeros(member_cap, dtype=np.int32), np.zeros(member_cap, dtype=np.float64)
+            rc = self.lib.adsb_stream_mlat(self._h, float(t_lo), float(t_hi), int(min_rx), fixes.ctypes.data if cap else None, cap,
+                                           ctypes.byref(n), ms.ctypes.data if member_cap else None,
+                                           mt.ctypes.data if member_cap else None, member_cap, ctypes.byref(m))
+            if rc == -28 and attempt == 0:               # -ENOSPC: *n_fixes, *n_members = the numbers needed
+                cap, member_cap = max(cap, n.value), max(member_cap, m.value)
+                continue
+            self._chk(rc)
+            return fixes[:n.value], ms[:m.value], mt[:m.value]
+
+    def stream_mlat_stats(self):
+        """(streams with a position, ts_ulp_m: what the double's spacing at the carry's latest timestamp is worth in metres)"""
+        k, u = ctypes.c_int32(0), ctypes.c_double(0)
+        self._chk(self.lib.adsb_stream_mlat_stats(self._h, ctypes.byref(k), ctypes.byref(u)))
+        return k.value, u.value
 
     def stream_decoder_reserve(self, slots):
         """The capacity of the decoders' store, while it holds nothing (adsb_stream_decoder_reserve)."""

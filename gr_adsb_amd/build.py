@@ -11,8 +11,11 @@ SOURCES = ["adsb_hip.hip"]
 SHARED_SOURCE = "adsb_shared.hip"
 # ADSB_FLAG_STREAM_DEDUP's kernels: a third unit, for the same reason
 DEDUP_SOURCE = "adsb_dedup.hip"
+# adsb_stream_mlat's kernels: a fourth unit, for the same reason
+MLAT_SOURCE = "adsb_mlat.hip"
 DEPS = ["adsb_hip.hip", "adsb_device.h", "adsb_plan.h", os.path.join("..", "..", "include", "adsb_hip.h"),
-        "adsb_shared.hip", "adsb_shared.h", "adsb_shared_device.h", "adsb_dedup.hip", "adsb_dedup.h", "adsb_dedup_device.h"]
+        "adsb_shared.hip", "adsb_shared.h", "adsb_shared_device.h", "adsb_dedup.hip", "adsb_dedup.h", "adsb_dedup_device.h",
+        "adsb_mlat.hip", "adsb_mlat.h", "adsb_mlat_device.h"]
 # -ffp-contract=off: |IQ|^2 must be two rounded products and one rounded add
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread"]
 
@@ -34,6 +37,7 @@ def up_to_date():
 RES = os.path.join(HERE, "kernel_resources.json")
 RES_SHARED = os.path.join(HERE, "kernel_resources_shared.json")
 RES_DEDUP = os.path.join(HERE, "kernel_resources_dedup.json")
+RES_MLAT = os.path.join(HERE, "kernel_resources_mlat.json")
 
 
 def _parse_resources(remarks):
@@ -56,14 +60,14 @@ def _parse_resources(remarks):
 
 def compile_and_link(out, extra_flags=(), verbose=False):
     """The translation units, each compiled with FLAGS + extra_flags side by side, linked into the shared library `out`
-    (libadsb_hip.so, or a side copy: tools/kbench.py) -> [the compiler's output per unit: SOURCES, SHARED_SOURCE, DEDUP_SOURCE].  The objects live
+    (libadsb_hip.so, or a side copy: tools/kbench.py) -> [the compiler's output per unit: SOURCES, SHARED_SOURCE, DEDUP_SOURCE, MLAT_SOURCE].  The objects live
     in a temporary directory."""
     import shutil
     import tempfile
     compile_flags = [f for f in FLAGS if f != "-shared"] + list(extra_flags)
     tmp = tempfile.mkdtemp(prefix="adsb_build_")
     try:
-        units = [(os.path.join(CSRC, s), os.path.join(tmp, s + ".o")) for s in SOURCES + [SHARED_SOURCE, DEDUP_SOURCE]]
+        units = [(os.path.join(CSRC, s), os.path.join(tmp, s + ".o")) for s in SOURCES + [SHARED_SOURCE, DEDUP_SOURCE, MLAT_SOURCE]]
         jobs = []
         for src, obj in units:
             cmd = [hipcc()] + compile_flags + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", obj]
@@ -90,13 +94,14 @@ def compile_and_link(out, extra_flags=(), verbose=False):
 def build(force=False, verbose=False):
     """hipcc -> libadsb_hip.so, and beside it kernel_resources.json: the compiler's per-kernel register / LDS / scratch
     report (tests/test_abi.py holds the limits the pipeline relies on: k_detect must leave the tail kernels room), and
-    kernel_resources_shared.json / kernel_resources_dedup.json: the same for adsb_shared.hip's and adsb_dedup.hip's kernels."""
-    if not force and up_to_date() and all(os.path.exists(p) for p in (RES, RES_SHARED, RES_DEDUP)):
+    kernel_resources_shared.json / kernel_resources_dedup.json / kernel_resources_mlat.json: the same for adsb_shared.hip's,
+    adsb_dedup.hip's and adsb_mlat.hip's kernels."""
+    if not force and up_to_date() and all(os.path.exists(p) for p in (RES, RES_SHARED, RES_DEDUP, RES_MLAT)):
         return LIB
     import json
     remarks = compile_and_link(LIB, verbose=verbose)
     assert len(SOURCES) == 1
-    for path, text in zip((RES, RES_SHARED, RES_DEDUP), remarks):
+    for path, text in zip((RES, RES_SHARED, RES_DEDUP, RES_MLAT), remarks):
         with open(path, "w") as f:
             json.dump(_parse_resources(text), f, indent=1, sort_keys=True)
     return LIB

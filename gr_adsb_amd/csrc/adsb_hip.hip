@@ -16,6 +16,7 @@
 #include <cerrno>
 #include <climits>
 #include <cmath>
+#include <limits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,6 +31,7 @@
 
 #include "adsb_shared.h"
 #include "adsb_dedup.h"
+#include "adsb_mlat.h"
 
 // wavefront-level ordering point used by adsb_device.h: LDS traffic of one wavefront is executed in
 // program order by the hardware, this only stops the compiler from moving LDS accesses across it
@@ -330,6 +332,11 @@ struct FleetDec {
     PinnedBuf h_dup, h_dup_next;                // dup[] of the last delivered call / where a call's arrives (as h_order)
     void fresh() { hi = 0; off = cnt = 0; duplicates = 0; delivered = false; }
   } dd;
+  // adsb_stream_mlat (adsb_mlat.hip): the receivers' ECEF positions (NaN: none set) -- not decoder state: only fleet_open and
+  // fleet_close touch them -- and one call's work buffer (adsb_mlat.h: Layout) with the pinned memory its counts come down to
+  std::vector<double> rx;
+  DevBuf d_mlat;
+  PinnedBuf h_mlat;
 };
 constexpr long long kFleetMinCap = 256, kFleetDefaultCap = 1ll << 16, kFleetMaxCap = 1ll << 27;    // (slot index 2^28 - 1 would sort with kDecNoKey)
 constexpr size_t kFleetSlotBytes = 16 + sizeof(Plane);
@@ -339,6 +346,9 @@ static_assert(offsetof(Rec, w) == 0 && kSortTile == adsb_shared_host::kSortTile,
 static_assert(sizeof(Rec) == adsb_dedup_host::kRecBytes && sizeof(DecRow) == adsb_dedup_host::kRowBytes && offsetof(DecRow, port) == 0 &&
               ADSB_DEC_DUPLICATE == 4u && kDemod == ADSB_BURST_DEMOD && kLongFmt == ADSB_BURST_LONG,
               "adsb_dedup.hip reads a record's flags in word 3 and writes a row's port in byte 0");
+static_assert(sizeof(adsb_mlat_fix) == adsb_mlat_host::kFixBytes && offsetof(adsb_mlat_fix, bits) == 48 && offsetof(adsb_mlat_fix, flags) == 62 &&
+              offsetof(adsb_mlat_fix, icao) == 64 && offsetof(adsb_mlat_fix, first) == 84 && adsb_mlat_host::kEntBytes == adsb_dedup_host::kEntBytes &&
+              ADSB_BURST_LONG == 64u, "adsb_mlat.hip writes adsb_mlat_fix rows and reads the carry's entries");
 // ADSB_FLAG_STREAM_DECODE_SHARED: d_shared carved for a call of n records in n_items items, every part on a 256-byte boundary
 struct SharedBufs {
   unsigned long long *keys = nullptr, *keys_tmp = nullptr;
@@ -1743,15 +1753,16 @@ int fleet_open(adsb_ctx* c, size_t n) {
   F.used = F.live_slots = F.live_planes = F.grows = 0;
   F.call = 0; F.n_rows = 0; F.all = 1;
   F.dd.fresh(); F.dd.window = 0.002; F.dd.horizon = 1.0; F.dd.cur = 0;
+  F.rx.assign(3 * n, std::numeric_limits<double>::quiet_NaN());
   F.open = true;
   return 0;
 }
 int fleet_close(adsb_ctx* c) {
   FleetDec& F = c->fd;
   F.open = false; F.cap = 0; F.n_rows = 0;
-  F.start.clear(); F.gen.clear(); F.slots.clear(); F.planes.clear();
-  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen, &F.d_snap, &F.d_ages, &F.d_merged, &F.d_shared, &F.dd.d_carry[0], &F.dd.d_carry[1], &F.dd.d_call}) HIPCHK(c, b->release());
-  for (PinnedBuf* b : {&F.h_recs, &F.h_rows, &F.h_items, &F.h_cnt, &F.h_shared, &F.h_order, &F.h_order_next, &F.dd.h_dup, &F.dd.h_dup_next}) HIPCHK(c, b->release());
+  F.start.clear(); F.gen.clear(); F.slots.clear(); F.planes.clear(); F.rx.clear();
+  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen, &F.d_snap, &F.d_ages, &F.d_merged, &F.d_shared, &F.dd.d_carry[0], &F.dd.d_carry[1], &F.dd.d_call, &F.d_mlat}) HIPCHK(c, b->release());
+  for (PinnedBuf* b : {&F.h_recs, &F.h_rows, &F.h_items, &F.h_cnt, &F.h_shared, &F.h_order, &F.h_order_next, &F.dd.h_dup, &F.dd.h_dup_next, &F.h_mlat}) HIPCHK(c, b->release());
   return 0;
 }
 
@@ -2172,6 +2183,39 @@ uint32_t adsb_mode_s_aircraft(const uint8_t bits[14], int32_t fec, int32_t* aa_o
   return ret;
 }
 
+// WGS-84
+static constexpr double kWgsA = 6378137.0, kWgsF = 1.0 / 298.257223563, kWgsE2 = kWgsF * (2.0 - kWgsF), kWgsB = kWgsA * (1.0 - kWgsF);
+static constexpr double kRadPerDeg = 3.14159265358979323846 / 180.0;
+
+void adsb_geodetic_to_ecef(double lat_deg, double lon_deg, double alt_m, double* x, double* y, double* z) {
+  const double lat = lat_deg * kRadPerDeg, lon = lon_deg * kRadPerDeg;
+  const double sl = std::sin(lat), cl = std::cos(lat);
+  const double n = kWgsA / std::sqrt(1.0 - kWgsE2 * sl * sl);
+  if (x) *x = (n + alt_m) * cl * std::cos(lon);
+  if (y) *y = (n + alt_m) * cl * std::sin(lon);
+  if (z) *z = (n * (1.0 - kWgsE2) + alt_m) * sl;
+}
+
+void adsb_ecef_to_geodetic(double x, double y, double z, double* lat_deg, double* lon_deg, double* alt_m) {
+  const double p = std::sqrt(x * x + y * y);
+  const double ep2 = kWgsE2 / (1.0 - kWgsE2);
+  const double th = std::atan2(z * kWgsA, p * kWgsB);                 // Bowring's start
+  double st = std::sin(th), ct = std::cos(th);
+  double lat = std::atan2(z + ep2 * kWgsB * st * st * st, p - kWgsE2 * kWgsA * ct * ct * ct);
+  for (int k = 0; k < 3; ++k) {                                       // lat = atan2(z + e^2 N sin lat, p)
+    const double sl = std::sin(lat);
+    const double n = kWgsA / std::sqrt(1.0 - kWgsE2 * sl * sl);
+    lat = std::atan2(z + kWgsE2 * n * sl, p);
+  }
+  const double sl = std::sin(lat), cl = std::cos(lat);
+  const double n = kWgsA / std::sqrt(1.0 - kWgsE2 * sl * sl);
+  // the height along the normal, by whichever of the two projections is the better conditioned
+  const double alt = std::fabs(cl) > 0.5 ? p / cl - n : z / sl - n * (1.0 - kWgsE2);
+  if (lat_deg) *lat_deg = lat / kRadPerDeg;
+  if (lon_deg) *lon_deg = p > 0.0 ? std::atan2(y, x) / kRadPerDeg : 0.0;
+  if (alt_m) *alt_m = alt;
+}
+
 float adsb_snr_db(float peak, float median) {
   // framer.py:157 under NumPy-2 promotion: every operation in float32
   volatile float q = peak / median;
@@ -2539,6 +2583,84 @@ int adsb_stream_dedup_stats(adsb_ctx* c, int64_t* duplicates, int64_t* carried, 
   if (duplicates) *duplicates = c->fd.dd.duplicates;
   if (carried) *carried = c->fd.dd.cnt;
   if (hi) *hi = c->fd.dd.hi;
+  return 0;
+}
+
+int adsb_stream_set_ecef(adsb_ctx* c, int32_t stream, double x, double y, double z) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
+  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_set_ecef: no streams (adsb_streams_open first)");
+  if (stream < 0 || (size_t)stream >= c->fd.rx.size() / 3) return fail(c, -EINVAL, "adsb_stream_set_ecef: no such stream");
+  if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z)) return fail(c, -EINVAL, "adsb_stream_set_ecef: a position is three finite numbers");
+  double* const r = &c->fd.rx[3 * (size_t)stream];
+  r[0] = x; r[1] = y; r[2] = z;
+  return 0;
+}
+
+int adsb_stream_mlat_stats(adsb_ctx* c, int32_t* positioned, double* ts_ulp_m) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
+  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_mlat_stats: no streams (adsb_streams_open first)");
+  if (positioned) {
+    int32_t k = 0;
+    for (size_t s = 0; s < c->fd.rx.size(); s += 3) k += !std::isnan(c->fd.rx[s]);
+    *positioned = k;
+  }
+  if (ts_ulp_m) {
+    const double hi = std::fabs(c->fd.dd.hi);
+    *ts_ulp_m = ADSB_MLAT_C * (std::nextafter(hi, std::numeric_limits<double>::infinity()) - hi);
+  }
+  return 0;
+}
+
+// adsb_mlat.hip's three phases on the carry as it stands; the head count, then the group and member counts, come down
+// between them (as fleet_step's h_cnt).  The work buffer is sized from the carry's length before the first launch.
+int adsb_stream_mlat(adsb_ctx* c, double t_lo, double t_hi, int32_t min_rx, adsb_mlat_fix* fixes, int32_t cap, int32_t* n_fixes,
+                     int32_t* member_stream, double* member_ts, int32_t member_cap, int32_t* n_members) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
+  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_mlat: no streams (adsb_streams_open first)");
+  if (min_rx < adsb_mlat_host::kMinRx) return fail(c, -EINVAL, "adsb_stream_mlat: min_rx < 4 (three-receiver fixes are not provided)");
+  if (std::isnan(t_lo) || std::isnan(t_hi)) return fail(c, -EINVAL, "adsb_stream_mlat: a bound is NaN");
+  if (!n_fixes || !n_members || cap < 0 || member_cap < 0 || (cap > 0 && !fixes) || (member_cap > 0 && (!member_stream || !member_ts)))
+    return fail(c, -EINVAL, "adsb_stream_mlat: n_fixes / n_members, or the arrays for cap / member_cap > 0, missing");
+  int rc;
+  if ((rc = require_idle(c, kCallPending))) return rc;
+  FleetDec& F = c->fd;
+  const FleetDec::Dedup& D = F.dd;
+  *n_fixes = 0; *n_members = 0;
+  const int nc = D.cnt, n_streams = (int)(F.rx.size() / 3);
+  if (nc == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = c->stream;
+  const adsb_mlat_host::Layout L = adsb_mlat_host::layout((size_t)nc, (size_t)n_streams);
+  const size_t rx_bytes = F.rx.size() * sizeof(double);
+  if ((rc = ensure(c, F.d_mlat, L.bytes)) || (rc = ensure_pinned(c, F.h_mlat, rx_bytes + 64))) return rc;
+  char* const work = (char*)F.d_mlat.p;
+  int* const got = (int*)((char*)F.h_mlat.p + rx_bytes);
+  memcpy(F.h_mlat.p, F.rx.data(), rx_bytes);
+  HIPCHK(c, hipMemcpyAsync(work + L.rx, F.h_mlat.p, rx_bytes, hipMemcpyHostToDevice, st));
+  const char* const carry = (const char*)D.d_carry[D.cur].p + (size_t)D.off * adsb_dedup_host::kEntBytes;
+  hipError_t e;
+  if ((e = (hipError_t)adsb_mlat_host::launch_heads(st, carry, nc, t_lo, t_hi, D.window, work, L))) return fail(c, -EIO, "adsb_stream_mlat: the head kernels", e);
+  HIPCHK(c, hipMemcpyAsync(got, work + L.tot_heads, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const int nh = got[1];
+  if (nh < 0 || nh > nc) return fail(c, -EIO, "adsb_stream_mlat: the head count is out of range");
+  if (nh == 0) return 0;
+  if ((e = (hipError_t)adsb_mlat_host::launch_groups(st, carry, nc, nh, D.window, min_rx, n_streams, work, L))) return fail(c, -EIO, "adsb_stream_mlat: the group kernels", e);
+  HIPCHK(c, hipMemcpyAsync(got, work + L.tot_groups, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const int ng = got[1], nm = got[2];
+  if (ng < 0 || ng > nc / adsb_mlat_host::kMinRx || nm < (long long)ng * min_rx || nm > nc) return fail(c, -EIO, "adsb_stream_mlat: the group counts are out of range");
+  *n_fixes = ng; *n_members = nm;
+  if (ng > cap || nm > member_cap) return fail(c, -ENOSPC, "adsb_stream_mlat: cap or member_cap is too small (*n_fixes, *n_members)");
+  if (ng == 0) return 0;
+  if ((e = (hipError_t)adsb_mlat_host::launch_solve(st, carry, nc, ng, D.window, n_streams, work, L))) return fail(c, -EIO, "adsb_stream_mlat: k_mlat_solve", e);
+  HIPCHK(c, hipMemcpyAsync(fixes, work + L.fixes, (size_t)ng * sizeof(adsb_mlat_fix), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(member_stream, work + L.member_stream, (size_t)nm * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(member_ts, work + L.member_ts, (size_t)nm * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
   return 0;
 }
 

@@ -1,0 +1,43 @@
+// adsb_mlat.h -- the launchers of adsb_mlat.hip (adsb_stream_mlat: adsb_mlat_device.h), for adsb_hip.hip, and the sizing rule
+// of the call's work buffer.  Plain pointers only, as adsb_dedup.h: the translation units share no type.  Every call queues
+// its kernels on `stream` (a hipStream_t) and returns the hipError_t of the launches as an int (0: queued).  Internal to
+// libadsb_hip.so.
+#pragma once
+#include <stddef.h>
+
+namespace adsb_mlat_host {
+
+constexpr int kEntBytes = 32, kFixBytes = 88, kChunk = 256, kMinRx = 4;
+
+// The work buffer of one call over a carry of nc entries, every part on a 256-byte boundary, all of it sized before the
+// first launch: heads <= nc; groups are disjoint and hold at least kMinRx used hearings each, so groups <= nc / kMinRx and
+// members <= nc.
+struct Layout {
+  size_t range, tot_heads, tot_groups;    // int[4] each: {lo, hi}; {0, heads, -, -}; {0, groups, members, -}
+  size_t w, cnt, sum;                     // int[nc]: head flags; int[chunks] twice: the compaction's per-chunk arrays
+  size_t heads, nrx, gsel, gfirst;        // int[nc] each
+  size_t rx;                              // double[3 n_streams]: the receivers' ECEF positions, NaN where none is set
+  size_t fixes, member_stream, member_ts; // Fix[nc / kMinRx + 1], int[nc], double[nc]
+  size_t bytes;
+};
+inline Layout layout(size_t nc, size_t n_streams) {
+  Layout L{};
+  const size_t chunks = (nc + kChunk - 1) / kChunk + 1;
+  const size_t part[14] = {16, 16, 16, nc * 4, chunks * 4, chunks * 4, nc * 4, nc * 4, nc * 4, nc * 4, n_streams * 24,
+                           (nc / kMinRx + 1) * (size_t)kFixBytes, nc * 4, nc * 8};
+  size_t* const at[14] = {&L.range, &L.tot_heads, &L.tot_groups, &L.w, &L.cnt, &L.sum, &L.heads, &L.nrx, &L.gsel, &L.gfirst, &L.rx,
+                          &L.fixes, &L.member_stream, &L.member_ts};
+  size_t off = 0;
+  for (int k = 0; k < 14; ++k) { *at[k] = off; off += (part[k] + 255) & ~(size_t)255; }
+  L.bytes = off;
+  return L;
+}
+
+// carry[nc] -> work: the range of [t_lo, t_hi), the heads in it in carry order, their number in tot_heads[1]
+int launch_heads(void* stream, const void* carry, int nc, double t_lo, double t_hi, double window, void* work, const Layout& L);
+// heads[nh] -> nrx[nh]; the groups with nrx >= min_rx in gsel / gfirst, their number and members in tot_groups[1], [2]
+int launch_groups(void* stream, const void* carry, int nc, int nh, double window, int min_rx, int n_streams, void* work, const Layout& L);
+// gsel[ng] -> fixes[ng], member_stream / member_ts
+int launch_solve(void* stream, const void* carry, int nc, int ng, double window, int n_streams, void* work, const Layout& L);
+
+}  // namespace adsb_mlat_host

@@ -150,13 +150,15 @@ class FrontEnd:
         return self.ctx.last_batch_fallbacks
 
     # -- many receivers that go on: streams carried across batch calls -----------------------------------
-    def receivers(self, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False, dedup=False):
+    def receivers(self, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False, dedup=False, positions=None):
         """n receiver streams on this context (Receivers below).  fmt: one of _native.FMT_*, or None: by the arrays' dtype.
         starts / msg_filter: FLAG_STREAM_DECODE contexts, the streams' start timestamps and their decoders' msg_filter.
         ages: the context also has FLAG_PLANE_AGES (ValueError otherwise): .planes(seen=True) and .expire(cutoffs).
         shared: the context also has FLAG_STREAM_DECODE_SHARED (ValueError otherwise): ONE decoder behind all n streams.
-        dedup: True, or (window_s, horizon_s): the context also has FLAG_STREAM_DEDUP (ValueError otherwise)."""
-        return Receivers(self.ctx, n, fmt, starts, msg_filter, ages, shared, dedup)
+        dedup: True, or (window_s, horizon_s): the context also has FLAG_STREAM_DEDUP (ValueError otherwise).
+        positions: [(lat_deg, lon_deg, alt_m), ...], the antennas of streams 0, 1, ... on the WGS-84 ellipsoid (None in the
+        list: that stream has none); needs dedup (ValueError otherwise): Receivers.mlat()."""
+        return Receivers(self.ctx, n, fmt, starts, msg_filter, ages, shared, dedup, positions)
 
     def shard_tensor(self, t, origin, own_lo, own_hi, stream_len, fmt=0, head_cands=0):
         _after_torch(self.ctx, t)
@@ -200,9 +202,12 @@ class Receivers:
     cutoff, and none of them takes ids.  The same reply heard by several receivers counts once per hearing,
     unless dedup (a context that also has FLAG_STREAM_DEDUP; True, or (window_s, horizon_s) for other than 0.002 s and 1.0 s):
     then it is published once, the other hearings' rows have port DEC_DUPLICATE, and .duplicates holds, beside .order, -1 /
-    -2 (the match lies in an earlier push) / the position of the earliest-published match of the last push or finish."""
+    -2 (the match lies in an earlier push) / the position of the earliest-published match of the last push or finish.
+    positions (with dedup): the antennas' (lat_deg, lon_deg, alt_m); mlat() then locates the replies that four or more
+    positioned receivers heard, from their arrival times alone (include/adsb_hip.h MULTILATERATION: pass `starts` relative to
+    a session epoch, not Unix times, or the double's spacing costs 71 m)."""
 
-    def __init__(self, ctx, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False, dedup=False):
+    def __init__(self, ctx, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False, dedup=False, positions=None):
         self.ctx, self.n, self.fmt = ctx, int(n), fmt
         self.decode = bool(getattr(ctx, "flags", 0) & _native.FLAG_STREAM_DECODE)
         self.ages = bool(ages)
@@ -213,6 +218,10 @@ class Receivers:
         self.duplicates = np.zeros(0, dtype=np.int32)
         if self.dedup != bool(getattr(ctx, "flags", 0) & _native.FLAG_STREAM_DEDUP):
             raise ValueError("dedup needs, and its absence excludes, a FLAG_STREAM_DEDUP context")
+        if positions is not None and not self.dedup:
+            raise ValueError("positions need dedup: multilateration reads the de-duplication carry")
+        if positions is not None and len(positions) > self.n:
+            raise ValueError("more positions than streams")
         if self.shared != bool(getattr(ctx, "flags", 0) & _native.FLAG_STREAM_DECODE_SHARED):
             raise ValueError("shared=True needs, and shared=False excludes, a FLAG_STREAM_DECODE | FLAG_STREAM_DECODE_SHARED context")
         if self.ages and not (self.decode and getattr(ctx, "flags", 0) & _native.FLAG_PLANE_AGES):
@@ -227,6 +236,9 @@ class Receivers:
                 ctx.set_stream_start(i, t)
         if self.dedup and dedup is not True:
             ctx.set_streams_dedup(*dedup)
+        for i, pos in enumerate(positions if positions is not None else []):
+            if pos is not None:
+                ctx.set_stream_ecef(i, *_native.geodetic_to_ecef(*pos))
 
     def _run(self, arrays, ids, thresholds, end):
         ids = list(range(len(arrays))) if ids is None else [int(i) for i in ids]
@@ -321,6 +333,22 @@ class Receivers:
                 raise ValueError("a shared decoder has one table: merged() takes no ids")
             ids = [0]
         return self.ctx.merged_planes(ids, cutoff)
+
+    def mlat(self, t_lo=None, t_hi=None, min_rx=4):
+        """receivers(dedup=..., positions=...): the replies of the carry (the last `horizon` seconds) that at least min_rx
+        positioned receivers heard, each located from its arrival times (adsb_stream_mlat) -> (fixes, member_stream, member_ts):
+        fixes has _native.MLAT_DTYPE's fields and latitude / longitude (degrees) / altitude_m, converted on the host; the
+        hearings of fixes[j] are member_*[first : first + n_rx].  t_lo / t_hi: only replies whose first hearing has
+        t_lo <= ts < t_hi; None leaves that side open.  Read status (MLAT_OK), rms_m and n_rx before trusting a row."""
+        if not self.dedup:
+            raise ValueError("mlat() needs receivers(dedup=...)")
+        fixes, ms, mt = self.ctx.stream_mlat(-np.inf if t_lo is None else t_lo, np.inf if t_hi is None else t_hi, min_rx)
+        out = np.zeros(len(fixes), dtype=np.dtype(_native.MLAT_DTYPE.descr + [("latitude", "<f8"), ("longitude", "<f8"), ("altitude_m", "<f8")]))
+        for name in _native.MLAT_DTYPE.names:
+            out[name] = fixes[name]
+        for j, f in enumerate(fixes):
+            out["latitude"][j], out["longitude"][j], out["altitude_m"][j] = _native.ecef_to_geodetic(f["x"], f["y"], f["z"])
+        return out, ms, mt
 
     def table(self, timestamp, ids=None, cutoff=None):
         """The lines the reference's print_planes draws ("Brief") for the merged picture at PDU timestamp `timestamp`."""

@@ -628,6 +628,78 @@ int adsb_stream_last_duplicates(adsb_ctx* ctx, const int32_t** dup, int32_t* n);
 /* duplicates: since the decoder was last fresh; carried: entries the carry holds now; hi: as above (0 while nothing has been
  * delivered).  Any pointer may be NULL.  -EINVAL without the flag or without open streams. */
 int adsb_stream_dedup_stats(adsb_ctx* ctx, int64_t* duplicates, int64_t* carried, double* hi);
+/* MULTILATERATION (ADSB_FLAG_STREAM_DEDUP contexts; entry points only: nothing runs unless a caller asks, and
+ * ADSB_ABI_VERSION is unchanged).  The carry of DE-DUPLICATION holds, for `horizon` seconds, every hearing of every reply with
+ * its arrival time and its stream.  Four hearings and the receivers' positions give the transmitter's position, whether or
+ * not the reply announces one: adsb_stream_mlat groups the carry's hearings and solves each group on the device.  It changes
+ * no state: the carry, hi, the decoder, adsb_stream_last_* and the framer state are untouched, and two calls with nothing
+ * between them are byte-identical.  No reference counterpart (the reference is one receiver).
+ * THE GROUP RULE depends on the carry only, in carry order: ascending ts, ties as the carry keeps them (the merge is stable,
+ * the carry first, a call's records in publication order).  An entry TAKES PART as in DE-DUPLICATION (its record had
+ * ADSB_BURST_DEMOD); the others are skipped everywhere below.  Two payloads are equal as in DE-DUPLICATION: the same length
+ * and the same bits of that length.  An entry is a HEAD iff no entry q in front of it in carry order, from ANY stream, has
+ * an equal payload and ts_head - ts_q <= window.  The head's GROUP is the head plus the entries m behind it in carry order
+ * with an equal payload and ts_m - ts_head <= window; both tests in double with exactly those expressions, window being
+ * the context's de-duplication window.  The head and the first 63 other entries of the group, in carry order, are its
+ * CANDIDATES.  A candidate is USED iff no candidate in front of it has its stream and its stream has a position
+ * (adsb_stream_set_ecef).  n_heard counts the whole group, n_rx the used hearings.  An entry that is neither a head nor in a
+ * head's group belongs to nothing: of a chain a - b - c with c beyond the window from a, b is in a's group and c, which b
+ * precedes within the window, is no head and in no group.  Groups are disjoint.
+ * THE SOLVER.  All arithmetic in double, no contraction.  With R_i the receiver of used hearing i (carry order) and
+ * C = ADSB_MLAT_C: d_i = C * (ts_i - ts_head), the difference first.  Unknowns: the position p and b = C * (ts_head - t_tx).
+ * Residual r_i = |p - R_i| - d_i - b.  Start: c = the mean of the R_i; p0 = c + 10000 * c / |c| (10 km further from the
+ * Earth's centre); b0 = |p0 - R_0|, R_0 being the first used hearing's receiver (the head's, when the head is used).
+ * Gauss-Newton: row i of J is ((p - R_i) / |p - R_i|, -1); solve (J^T J) delta = -J^T r by Cholesky, the pivots in the
+ * order x, y, z, b; a pivot that is not finite and positive ends the solve with ADSB_MLAT_SINGULAR, the iterate as it was.
+ * Otherwise (p, b) += delta, iters += 1, and |delta_p| < 0.001 m ends it with ADSB_MLAT_OK; 32 iterations without that
+ * give ADSB_MLAT_NO_CONVERGE.  rms_m = sqrt(sum r_i^2 / n_rx) at the last iterate, t_tx = ts_head - b / C.  The sums over the
+ * hearings are taken across a wavefront; their order is the implementation's, so positions agree with another evaluation of
+ * this rule to the solve's own sensitivity (tests/test_mlat.py measures it), everything else exactly.
+ * A fix says where the rule's arithmetic ended, not that the aircraft is there: judge it by status, rms_m, n_rx and the
+ * receivers' geometry.  Four receivers in a plane leave the height weak.
+ * PRECISION.  An arrival time is the carry's ts = start + (double)offset / fs.  It carries the sample period (150 m at
+ * 2 Msps, 15 m at 20 Msps) and the double's ulp at the magnitude of start: 238 ns, about 71 m, for Unix-epoch starts.  MLAT
+ * users should pass starts relative to a session epoch: below 2^23 s the ulp is under 1 ns (0.3 m).  The decoder's
+ * last_seen clock works the same either way.  adsb_stream_mlat_stats reports C * ulp(hi), so a caller can see the limit.
+ * Sub-sample arrival times, clock offsets between receivers and altitude-aided three-receiver fixes are not provided.
+ * adsb_stream_set_ecef: the antenna of `stream` in WGS-84 ECEF metres.  Allowed at any time while streams are open; it is
+ * not decoder state: adsb_stream_reset, adsb_streams_decoder_reset and adsb_reset keep it, adsb_streams_close forgets it.
+ * -EINVAL for non-finite values, a bad stream, or a context without ADSB_FLAG_STREAM_DEDUP.  A stream without a position
+ * never contributes a hearing.
+ * adsb_stream_mlat solves every group whose head has t_lo <= ts < t_hi (infinities open a side; the members may lie beyond
+ * t_hi) and n_rx >= min_rx; rows in carry order of the heads; the members of row j are member_stream / member_ts[first ..
+ * first + n_rx), in carry order.  min_rx < 4, NaN bounds, a context without the flag or without open streams: -EINVAL;
+ * -EBUSY while submitted tickets are pending.  cap or member_cap too small: -ENOSPC with the needed counts in *n_fixes and
+ * *n_members and nothing written (fixes == NULL with cap == 0 and member_cap == 0 is a count query).  An empty carry or
+ * range: 0 rows.  The call is ordered behind the last delivered stream-batch call. */
+#define ADSB_MLAT_C 299702547.0 /* m/s: the speed of light / 1.0003 */
+#define ADSB_MLAT_OK 0
+#define ADSB_MLAT_NO_CONVERGE 1
+#define ADSB_MLAT_SINGULAR 2
+typedef struct adsb_mlat_fix { /* 88 bytes */
+  double ts;                   /* the head's timestamp */
+  double x, y, z;              /* the last iterate: WGS-84 ECEF metres (adsb_ecef_to_geodetic) */
+  double t_tx;                 /* the estimated transmit time */
+  double rms_m;                /* the residual at the last iterate */
+  uint8_t bits[14];            /* the head's payload, masked to its length */
+  uint16_t flags;              /* ADSB_BURST_LONG or 0 */
+  int32_t icao;                /* DF 11/17/18: bytes 1..3; DF 0/4/5/16/20/21: the remainder of the whole reply (the address under
+                                  address/parity: adsb_mode_s_syndrome); any other DF: -1 */
+  int32_t n_rx, n_heard;
+  int32_t status;              /* ADSB_MLAT_* */
+  int32_t iters;
+  int32_t first;
+} adsb_mlat_fix;
+int adsb_stream_set_ecef(adsb_ctx* ctx, int32_t stream, double x, double y, double z);
+int adsb_stream_mlat(adsb_ctx* ctx, double t_lo, double t_hi, int32_t min_rx, adsb_mlat_fix* fixes, int32_t cap, int32_t* n_fixes,
+                     int32_t* member_stream, double* member_ts, int32_t member_cap, int32_t* n_members);
+/* positioned: streams with a position; ts_ulp_m: ADSB_MLAT_C * ulp(hi), what the double's spacing at the carry's latest
+ * timestamp is worth in metres.  Either pointer may be NULL.  -EINVAL without the flag or without open streams. */
+int adsb_stream_mlat_stats(adsb_ctx* ctx, int32_t* positioned, double* ts_ulp_m);
+/* WGS-84 (a = 6378137 m, f = 1 / 298.257223563), degrees and metres, plain host arithmetic in double.  The inverse is
+ * Bowring's start followed by three fixed-point rounds on the latitude; at the poles longitude is 0.  No context. */
+void adsb_geodetic_to_ecef(double lat_deg, double lon_deg, double alt_m, double* x, double* y, double* z);
+void adsb_ecef_to_geodetic(double x, double y, double z, double* lat_deg, double* lon_deg, double* alt_m);
 int adsb_stream_set_start(adsb_ctx* ctx, int32_t stream, double start_timestamp);   /* fresh streams only; default 0 */
 /* Row t belongs to out[t] of the last DELIVERED adsb_process_stream_batch[_device] call (*n = that call's *n_out; *rows NULL
  * when 0).  Pinned memory of the context, valid until the next stream-batch call. */

@@ -1,0 +1,135 @@
+// mlat_driver.cpp -- TEST INFRASTRUCTURE ONLY.  Runs adsb_stream_mlat's kernels (gr_adsb_amd/csrc/adsb_mlat_device.h) on the SIMT
+// emulator in hipsim.h, on host memory, over a carry the caller states entry by entry, in the order adsb_mlat.hip queues them
+// and with the host's rule of adsb_hip.hip restated: the work buffer is carved by adsb_mlat.h's layout() before the first
+// launch, the head count and then the group and member counts are read between the phases, -ENOSPC is decided before
+// k_mlat_solve and writes nothing.  Every part of the work buffer has guard bytes behind it.  The host's own code runs only in
+// tests/test_gpu_mlat.py.  Never linked into libadsb_hip.so.
+#include "hipsim.h"
+
+#include <vector>
+
+inline long long __double_as_longlong(double d) { long long r; memcpy(&r, &d, sizeof r); return r; }
+inline double __longlong_as_double(long long v) { double r; memcpy(&r, &v, sizeof r); return r; }
+
+#include "../../gr_adsb_amd/csrc/adsb_dedup_device.h"
+#include "../../gr_adsb_amd/csrc/adsb_mlat.h"
+#include "../../gr_adsb_amd/csrc/adsb_mlat_device.h"
+
+namespace ml = adsb_mlat;
+namespace mh = adsb_mlat_host;
+
+static_assert(sizeof(ml::Fix) == mh::kFixBytes && ml::kEntWords == adsb_dedup::kEntWords && mh::kChunk == ml::kThreads, "the sizes adsb_mlat.h states");
+
+namespace {
+constexpr unsigned char kGuard = 0xA5;
+constexpr size_t kTail = 256;
+
+// the carry's entries as k_dedup_entries writes them; zero_hash: every hash 0, so that only the payload words can tell two
+// replies apart
+std::vector<unsigned long long> make_carry(const double* ts, const unsigned char* bits14, const int* marker, const int* stream, int nc, bool zero_hash) {
+  std::vector<unsigned long long> c((size_t)nc * ml::kEntWords + 1, 0);      // (+1: data() is never null)
+  for (int i = 0; i < nc; ++i) {
+    unsigned long long w2 = 0, w3 = 0;
+    memcpy(&w2, bits14 + (size_t)i * 14, 8);
+    memcpy(&w3, bits14 + (size_t)i * 14 + 8, 6);
+    const int mk = marker[i];
+    const unsigned long long a = mk == 0 ? 0ull : mk == 2 ? w2 : (w2 & 0x00FFFFFFFFFFFFFFull);
+    const unsigned long long b = mk == 2 ? w3 : 0ull;
+    unsigned long long* e = &c[(size_t)i * ml::kEntWords];
+    memcpy(&e[0], &ts[i], 8);
+    e[1] = a; e[2] = b;
+    e[3] = (unsigned long long)(zero_hash ? 0u : adsb_dedup::hash32(a, b)) | ((unsigned long long)((unsigned)stream[i] & 0xFFFFFFu) << 32) |
+           ((unsigned long long)mk << 56);
+  }
+  return c;
+}
+
+struct Work {
+  mh::Layout L;
+  std::vector<unsigned char> raw;
+  std::vector<std::pair<size_t, size_t>> parts;      // offset, bytes in use
+  Work(size_t nc, size_t n_streams) : L(mh::layout(nc, n_streams)) {
+    const size_t chunks = (nc + mh::kChunk - 1) / mh::kChunk + 1;
+    parts = {{L.range, 16}, {L.tot_heads, 16}, {L.tot_groups, 16}, {L.w, nc * 4}, {L.cnt, chunks * 4}, {L.sum, chunks * 4}, {L.heads, nc * 4},
+             {L.nrx, nc * 4}, {L.gsel, nc * 4}, {L.gfirst, nc * 4}, {L.rx, n_streams * 24}, {L.fixes, (nc / mh::kMinRx + 1) * (size_t)mh::kFixBytes},
+             {L.member_stream, nc * 4}, {L.member_ts, nc * 8}};
+    raw.assign(L.bytes + kTail, kGuard);
+  }
+  template <class T> T* at(size_t off) { return (T*)(raw.data() + off); }
+  // every byte between a part's end and the next part's start (or the tail's end) is still the guard's
+  bool ok() const {
+    for (size_t k = 0; k < parts.size(); ++k) {
+      const size_t end = k + 1 < parts.size() ? parts[k + 1].first : raw.size();
+      if (parts[k].first + parts[k].second > end) return false;
+      for (size_t q = parts[k].first + parts[k].second; q < end; ++q) if (raw[q] != kGuard) return false;
+    }
+    return true;
+  }
+};
+
+unsigned cover(long long work, int per, int grid) {
+  const long long g = (work + per - 1) / per;
+  return (unsigned)(grid > 0 ? grid : g < 1 ? 1 : g);
+}
+
+void compact(Work& W, const int* w, const int* span, int min_w, int* tot, int add_lo, int* idx, int* first, int grid) {
+  const unsigned g = (unsigned)(grid > 0 ? grid : 2);
+  hipsim::launch(ml::k_mlat_count, g, (unsigned)ml::kThreads, w, span, min_w, W.at<int>(W.L.cnt), W.at<int>(W.L.sum));
+  hipsim::launch(ml::k_mlat_scan, 1u, (unsigned)ml::kThreads, span, W.at<int>(W.L.cnt), W.at<int>(W.L.sum), tot);
+  hipsim::launch(ml::k_mlat_place, g, (unsigned)ml::kThreads, w, span, min_w, (const int*)W.at<int>(W.L.cnt), (const int*)W.at<int>(W.L.sum), add_lo,
+                 idx, first);
+}
+}  // namespace
+
+extern "C" {
+
+int sim_mlat_tile() { return ml::kTile; }
+int sim_mlat_lds_bytes(int which) { return which == 0 ? ml::kHeadsLdsBytes : which == 1 ? ml::kPlaceLdsBytes : ml::kScanLdsBytes; }
+int sim_mlat_fix_bytes() { return (int)sizeof(ml::Fix); }
+unsigned long long sim_mlat_layout_bytes(long long nc, long long n_streams) { return (unsigned long long)mh::layout((size_t)nc, (size_t)n_streams).bytes; }
+
+// One adsb_stream_mlat call over the carry ts / bits14 / marker / stream [nc] (in carry order; marker 0: takes no part, 1: 56
+// bits, 2: 112 bits) with rx[3 n_streams] (NaN: no position).  heads_out (may be null, nc ints): the heads of the range, their
+// number in *n_heads.  Returns 0, -28 (-ENOSPC: the counts are stated, nothing is written), -22 (arguments), -1: a guard was
+// overwritten or the carry was written, -5: a count out of range.
+int sim_mlat(const double* ts, const unsigned char* bits14, const int* marker, const int* stream, int nc, const double* rx, int n_streams,
+             double window, double t_lo, double t_hi, int min_rx, int grid, int zero_hash, void* fixes, int cap, int* n_fixes, int* member_stream,
+             double* member_ts, int member_cap, int* n_members, int* heads_out, int* n_heads) {
+  if (min_rx < mh::kMinRx || t_lo != t_lo || t_hi != t_hi || nc < 0) return -22;
+  *n_fixes = 0; *n_members = 0;
+  if (n_heads) *n_heads = 0;
+  if (nc == 0) return 0;
+  const std::vector<unsigned long long> carry = make_carry(ts, bits14, marker, stream, nc, zero_hash != 0), before = carry;
+  Work W((size_t)nc, (size_t)n_streams);
+  memcpy(W.at<double>(W.L.rx), rx, (size_t)n_streams * 24);
+  const unsigned long long* c = carry.data();
+  int* const range = W.at<int>(W.L.range);
+  hipsim::launch(ml::k_mlat_range, 1u, (unsigned)ml::kWave, c, nc, t_lo, t_hi, range);
+  hipsim::launch(ml::k_mlat_heads, cover(nc, ml::kThreads, grid), (unsigned)ml::kThreads, c, nc, (const int*)range, window, W.at<int>(W.L.w));
+  compact(W, W.at<int>(W.L.w), range, 1, W.at<int>(W.L.tot_heads), 1, W.at<int>(W.L.heads), nullptr, grid);
+  if (!W.ok() || carry != before) return -1;
+  const int nh = W.at<int>(W.L.tot_heads)[1];
+  if (nh < 0 || nh > nc) return -5;
+  if (n_heads) *n_heads = nh;
+  if (heads_out) memcpy(heads_out, W.at<int>(W.L.heads), (size_t)nh * 4);
+  if (nh == 0) return 0;
+  const int* const hspan = W.at<int>(W.L.tot_heads);
+  hipsim::launch(ml::k_mlat_groups, cover(nh, ml::kWaves, grid), (unsigned)ml::kThreads, c, nc, (const int*)W.at<int>(W.L.heads), hspan, window,
+                 (const double*)W.at<double>(W.L.rx), n_streams, W.at<int>(W.L.nrx));
+  compact(W, W.at<int>(W.L.nrx), hspan, min_rx, W.at<int>(W.L.tot_groups), 0, W.at<int>(W.L.gsel), W.at<int>(W.L.gfirst), grid);
+  if (!W.ok() || carry != before) return -1;
+  const int ng = W.at<int>(W.L.tot_groups)[1], nm = W.at<int>(W.L.tot_groups)[2];
+  if (ng < 0 || ng > nc / mh::kMinRx || nm < (long long)ng * min_rx || nm > nc) return -5;
+  *n_fixes = ng; *n_members = nm;
+  if (ng > cap || nm > member_cap) return -28;
+  if (ng == 0) return 0;
+  hipsim::launch(ml::k_mlat_solve, cover(ng, ml::kWaves, grid), (unsigned)ml::kThreads, c, nc, (const int*)W.at<int>(W.L.heads),
+                 (const int*)W.at<int>(W.L.gsel), (const int*)W.at<int>(W.L.gfirst), (const int*)W.at<int>(W.L.tot_groups), window,
+                 (const double*)W.at<double>(W.L.rx), n_streams, W.at<ml::Fix>(W.L.fixes), W.at<int>(W.L.member_stream), W.at<double>(W.L.member_ts));
+  if (!W.ok() || carry != before) return -1;
+  memcpy(fixes, W.at<ml::Fix>(W.L.fixes), (size_t)ng * sizeof(ml::Fix));
+  memcpy(member_stream, W.at<int>(W.L.member_stream), (size_t)nm * 4);
+  memcpy(member_ts, W.at<double>(W.L.member_ts), (size_t)nm * 8);
+  return 0;
+}
+}
