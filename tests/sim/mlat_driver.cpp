@@ -3,7 +3,10 @@
 // and with the host's rule of adsb_hip.hip restated: the work buffer is carved by adsb_mlat.h's layout() before the first
 // launch, the head count and then the group and member counts are read between the phases, -ENOSPC is decided before
 // k_mlat_solve and writes nothing.  Every part of the work buffer has guard bytes behind it.  The host's own code runs only in
-// tests/test_gpu_mlat.py.  Never linked into libadsb_hip.so.
+// tests/test_gpu_mlat.py.  Its twin is tests/gpu/mlat_device_driver.hip: the same entry point, sim_mlat, over the shipped
+// translation unit and its real launchers on the GPU (tests/test_gpu_mlat_device.py); the two share mlat_host_rule.h -- the
+// parts, the guards and the counts' range checks -- and the carry's words, which sim_mlat_carry below hands to the device
+// driver, so that both see identical bytes.  Never linked into libadsb_hip.so.
 #include "hipsim.h"
 
 #include <vector>
@@ -14,6 +17,7 @@ inline double __longlong_as_double(long long v) { double r; memcpy(&r, &v, sizeo
 #include "../../gr_adsb_amd/csrc/adsb_dedup_device.h"
 #include "../../gr_adsb_amd/csrc/adsb_mlat.h"
 #include "../../gr_adsb_amd/csrc/adsb_mlat_device.h"
+#include "mlat_host_rule.h"
 
 namespace ml = adsb_mlat;
 namespace mh = adsb_mlat_host;
@@ -21,8 +25,8 @@ namespace mh = adsb_mlat_host;
 static_assert(sizeof(ml::Fix) == mh::kFixBytes && ml::kEntWords == adsb_dedup::kEntWords && mh::kChunk == ml::kThreads, "the sizes adsb_mlat.h states");
 
 namespace {
-constexpr unsigned char kGuard = 0xA5;
-constexpr size_t kTail = 256;
+using mlat_rule::kGuard;
+using mlat_rule::kTail;
 
 // the carry's entries as k_dedup_entries writes them; zero_hash: every hash 0, so that only the payload words can tell two
 // replies apart
@@ -48,23 +52,9 @@ struct Work {
   mh::Layout L;
   std::vector<unsigned char> raw;
   std::vector<std::pair<size_t, size_t>> parts;      // offset, bytes in use
-  Work(size_t nc, size_t n_streams) : L(mh::layout(nc, n_streams)) {
-    const size_t chunks = (nc + mh::kChunk - 1) / mh::kChunk + 1;
-    parts = {{L.range, 16}, {L.tot_heads, 16}, {L.tot_groups, 16}, {L.w, nc * 4}, {L.cnt, chunks * 4}, {L.sum, chunks * 4}, {L.heads, nc * 4},
-             {L.nrx, nc * 4}, {L.gsel, nc * 4}, {L.gfirst, nc * 4}, {L.rx, n_streams * 24}, {L.fixes, (nc / mh::kMinRx + 1) * (size_t)mh::kFixBytes},
-             {L.member_stream, nc * 4}, {L.member_ts, nc * 8}};
-    raw.assign(L.bytes + kTail, kGuard);
-  }
+  Work(size_t nc, size_t n_streams) : L(mh::layout(nc, n_streams)), parts(mlat_rule::parts(L, nc, n_streams)) { raw.assign(L.bytes + kTail, kGuard); }
   template <class T> T* at(size_t off) { return (T*)(raw.data() + off); }
-  // every byte between a part's end and the next part's start (or the tail's end) is still the guard's
-  bool ok() const {
-    for (size_t k = 0; k < parts.size(); ++k) {
-      const size_t end = k + 1 < parts.size() ? parts[k + 1].first : raw.size();
-      if (parts[k].first + parts[k].second > end) return false;
-      for (size_t q = parts[k].first + parts[k].second; q < end; ++q) if (raw[q] != kGuard) return false;
-    }
-    return true;
-  }
+  bool ok() const { return mlat_rule::guards_ok(raw.data(), raw.size(), parts); }
 };
 
 unsigned cover(long long work, int per, int grid) {
@@ -88,6 +78,14 @@ int sim_mlat_lds_bytes(int which) { return which == 0 ? ml::kHeadsLdsBytes : whi
 int sim_mlat_fix_bytes() { return (int)sizeof(ml::Fix); }
 unsigned long long sim_mlat_layout_bytes(long long nc, long long n_streams) { return (unsigned long long)mh::layout((size_t)nc, (size_t)n_streams).bytes; }
 
+// The carry's words as sim_mlat builds them, into out_words[4 nc]: what tests/gpu/mlat_device_driver.hip is given.
+void sim_mlat_carry(const double* ts, const unsigned char* bits14, const int* marker, const int* stream, int nc, int zero_hash,
+                    unsigned long long* out_words) {
+  if (nc <= 0) return;
+  const std::vector<unsigned long long> c = make_carry(ts, bits14, marker, stream, nc, zero_hash != 0);
+  memcpy(out_words, c.data(), (size_t)nc * ml::kEntWords * 8);
+}
+
 // One adsb_stream_mlat call over the carry ts / bits14 / marker / stream [nc] (in carry order; marker 0: takes no part, 1: 56
 // bits, 2: 112 bits) with rx[3 n_streams] (NaN: no position).  heads_out (may be null, nc ints): the heads of the range, their
 // number in *n_heads.  Returns 0, -28 (-ENOSPC: the counts are stated, nothing is written), -22 (arguments), -1: a guard was
@@ -109,7 +107,7 @@ int sim_mlat(const double* ts, const unsigned char* bits14, const int* marker, c
   compact(W, W.at<int>(W.L.w), range, 1, W.at<int>(W.L.tot_heads), 1, W.at<int>(W.L.heads), nullptr, grid);
   if (!W.ok() || carry != before) return -1;
   const int nh = W.at<int>(W.L.tot_heads)[1];
-  if (nh < 0 || nh > nc) return -5;
+  if (!mlat_rule::heads_in_range(nh, nc)) return -5;
   if (n_heads) *n_heads = nh;
   if (heads_out) memcpy(heads_out, W.at<int>(W.L.heads), (size_t)nh * 4);
   if (nh == 0) return 0;
@@ -119,7 +117,7 @@ int sim_mlat(const double* ts, const unsigned char* bits14, const int* marker, c
   compact(W, W.at<int>(W.L.nrx), hspan, min_rx, W.at<int>(W.L.tot_groups), 0, W.at<int>(W.L.gsel), W.at<int>(W.L.gfirst), grid);
   if (!W.ok() || carry != before) return -1;
   const int ng = W.at<int>(W.L.tot_groups)[1], nm = W.at<int>(W.L.tot_groups)[2];
-  if (ng < 0 || ng > nc / mh::kMinRx || nm < (long long)ng * min_rx || nm > nc) return -5;
+  if (!mlat_rule::groups_in_range(ng, nm, nc, min_rx)) return -5;
   *n_fixes = ng; *n_members = nm;
   if (ng > cap || nm > member_cap) return -28;
   if (ng == 0) return 0;

@@ -8,12 +8,16 @@ on a rounding edge).  Positions: within TOL of the float64 oracle, and -- the ar
 within TOL plus the oracle's own distance from the truth of the true position.
 
 TOL.  The float64 oracle against its own np.longdouble run over every case of this file that converges differs by at most
-SENS = 5e-7 m (measured: 1.2e-8 m over 95 fixes; test_the_oracles_own_sensitivity prints and bounds it); the device sums the hearings in
+SENS = 5e-7 m (measured: 1.2e-8 m over 97 fixes; test_the_oracles_own_sensitivity prints and bounds it); the device sums the hearings in
 another order than the oracle, so 16 x SENS is allowed, and never less than 2e-3 m, twice the stopping threshold:
 TOL = max(16 x SENS, 2e-3) = 2e-3 m.
 
 What a green run here does NOT cover: the host's own code (adsb_stream_mlat, adsb_stream_set_ecef and their refusals), the
-carry as fleet_step leaves it, and the Python front end -- tests/test_gpu_mlat.py."""
+carry as fleet_step leaves it, and the Python front end -- tests/test_gpu_mlat.py; and everything on the device's side of
+these seams: what hipcc makes of __ballot, __shfl, __shfl_up and the LDS staging, the real launchers' grid sizing (the
+launches here are the driver's own) and the kernels' second grid-stride round under them, which needs more than 524 288
+entries -- tests/test_gpu_mlat_device.py runs this file's cases, unchanged, on the MI355X through
+tests/gpu/mlat_device_driver.hip, compares the device's bytes with this emulation's, and adds the large carry."""
 import ctypes
 import json
 import os
@@ -41,7 +45,7 @@ measured = []                 # (case, float64-vs-longdouble distance) of every 
 
 def mlat_lib():
     csrc = os.path.join(HERE, "..", "gr_adsb_amd", "csrc")
-    srcs = [os.path.join(SIM_DIR, f) for f in ("mlat_driver.cpp", "hipsim.h")] + \
+    srcs = [os.path.join(SIM_DIR, f) for f in ("mlat_driver.cpp", "hipsim.h", "mlat_host_rule.h")] + \
         [os.path.join(csrc, f) for f in ("adsb_mlat_device.h", "adsb_mlat.h", "adsb_dedup_device.h")]
     if not (os.path.exists(MLAT_SO) and all(os.path.getmtime(MLAT_SO) >= os.path.getmtime(s) for s in srcs)):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unknown-pragmas",
@@ -128,9 +132,14 @@ def rx_array(rx, n_streams):
     return a
 
 
-def run(sim, carry, rx, n_streams=None, t_lo=-np.inf, t_hi=np.inf, min_rx=4, grid=0, zero_hash=0, cap=None, member_cap=None, window=WINDOW):
+def run(sim, carry, rx, **kw):
     """-> (rc, fixes, member_stream, member_ts, heads, n_fixes, n_members)"""
-    ts, bits, mk, stream = carry.arrays()
+    return run_arrays(sim, *carry.arrays(), rx, **kw)
+
+
+def run_arrays(sim, ts, bits, mk, stream, rx, n_streams=None, t_lo=-np.inf, t_hi=np.inf, min_rx=4, grid=0, zero_hash=0, cap=None, member_cap=None,
+               window=WINDOW):
+    """run() over the carry's four arrays, in carry order"""
     nc = len(ts)
     n_streams = n_streams or (max([int(stream.max()) if nc else 0] + list(rx)) + 1)
     rxa = rx_array(rx, n_streams)
@@ -443,6 +452,160 @@ def test_random_fleets(sim, world):
     lo, hi = T0 + min(bounds), T0 + max(bounds)
     check(sim, "random", c, rx, n_streams=n_streams, converge=False, min_rx=min_rx, grid=grid)
     check(sim, "random", c, rx, n_streams=n_streams, converge=False, t_lo=lo, t_hi=hi, min_rx=4, grid=grid)
+
+
+# ---- the periodic carry: the compaction's scan beyond 256 chunks, the kernels' second grid-stride round -------------------
+# One period of PERIOD = 65 entries (coprime to 64, 256 and 1024: heads and members drift over every lane, workgroup place and
+# tile place), all within 1 ms, repeated every SPACING = 2^-7 s from EPOCH = 1024 s on, with the same payloads in every period
+# -- a kernel that matched across periods would show.  Every timestamp in [1024, 2048) is a multiple of 2^-42 s, so adding
+# k * 2^-7 is exact and the solver's inputs (differences of arrival times) of period k are bit for bit period 0's.
+EPOCH, SPACING, PERIOD = 1024.0, 2.0 ** -7, 65
+SHORT4 = reply(4, 1)[0]                                   # a short reply whose address lies under address/parity
+
+
+def period0():
+    """-> Carry: a long reply of AIRCRAFT[0] heard by streams 0 .. 5, and once more by stream 2; a short reply of AIRCRAFT[1]
+    heard by streams 0 .. 4; a reply heard by three streams (no fix); a marker-0 entry with the long reply's bytes; 49 fillers."""
+    at = lambda p, s: EPOCH + float(np.sqrt(((np.asarray(p) - np.asarray(RX8[s])) ** 2).sum())) / MR.C      # noqa: E731
+    c = Carry()
+    for s in range(6):
+        c.add(at(AIRCRAFT[0], s), IDENT, IDENT_LONG, s)
+    c.add(at(AIRCRAFT[0], 2) + 1e-4, IDENT, IDENT_LONG, 2)
+    c.add(at(AIRCRAFT[0], 3) + 1e-6, IDENT, IDENT_LONG, 6, part=False)
+    for s in range(5):
+        c.add(at(AIRCRAFT[1], s), SHORT4, False, s)
+    three = reply(17, 2)[0]
+    for s in (5, 6, 7):
+        c.add(EPOCH + 2.003e-4 + s * 1e-6, three, True, s)
+    fb = fillers(PERIOD - len(c.rows), 65)
+    for k in range(len(fb)):
+        c.add(EPOCH + 1e-5 + k * 1.3e-5, fb[k], True, 7 - k % 3)
+    ts = c.arrays()[0]
+    assert len(ts) == PERIOD and (np.diff(ts) > 0).all() and EPOCH < ts[0] and ts[-1] - ts[0] < 1e-3
+    assert SPACING - (ts[-1] - ts[0]) > WINDOW                         # no entry of another period is within the window
+    return c
+
+
+def periodic(n):
+    """-> (ts, bits, marker, stream) of the first n entries of the periodic carry, and period 0's arrays"""
+    p0 = period0().arrays()
+    k = -(-n // PERIOD)
+    shift = np.arange(k) * SPACING
+    ts = (p0[0][None, :] + shift[:, None]).ravel()[:n]
+    whole = n // PERIOD
+    assert ts[-1] < 2 * EPOCH and (ts[:whole * PERIOD].reshape(whole, PERIOD) - shift[:whole, None] == p0[0]).all()      # the shift is exact
+    return (ts, np.tile(p0[1], (k, 1))[:n].copy(), np.tile(p0[2], k)[:n].copy(), np.tile(p0[3], k)[:n].copy()), p0
+
+
+def replay_rows(p0, k, n=PERIOD):
+    """the first n entries of period k, as MR.mlat takes them"""
+    return [(float(p0[0][i] + k * SPACING), None if p0[2][i] == 0 else MR.payload_of(p0[1][i], p0[2][i] == 2), int(p0[3][i])) for i in range(n)]
+
+
+def check_periodic(sim, case, n):
+    """One call over the first n entries of the periodic carry -> (fixes, member_stream, member_ts, heads, period 0's arrays, fixes per period, members per period).
+    Period 0 alone against the replay (check()); every whole period k against period 0's rows of THIS call: the exact fields
+    equal, `first` + members-per-period * k, ts and member_ts + k * SPACING exactly, x / y / z / rms_m bit for bit, t_tx within
+    one spacing of the shifted value; the first, the last and (where there is one) the period holding entry 524 288 against a
+    replay of their own entries; the cut period, if any, against the replay of its entries."""
+    arrays, p0 = periodic(n)
+    c0 = period0()
+    lst0 = c0.replay_list()
+    assert lst0 == replay_rows(p0, 0)
+    truth = [AIRCRAFT[0] if e["flags"] else AIRCRAFT[1] for e in MR.mlat(lst0, WINDOW, RX8)[0]]
+    alone, exp0 = check(sim, case, c0, RX8, truth=truth)               # asserts status == OK of the oracle
+    heads0 = [h for h, _ in MR.groups(lst0, WINDOW)]
+    per_f, per_m, per_h = len(exp0), sum(e["n_rx"] for e in exp0), len(heads0)
+    assert (per_f, per_m) == (2, 11) and sorted(alone["n_heard"].tolist()) == [5, 7]
+
+    rc, fixes, ms, mt, heads, nf, nm = run_arrays(sim, *arrays, RX8)
+    assert rc == 0
+    fixes, ms, mt = fixes[:nf], ms[:nm], mt[:nm]
+    whole, cut = divmod(n, PERIOD)
+    cut_exp = MR.mlat(replay_rows(p0, whole, cut), WINDOW, RX8) if cut else ([], np.zeros(0, np.int32), np.zeros(0))
+    cut_heads = [h for h, _ in MR.groups(replay_rows(p0, whole, cut), WINDOW)] if cut else []
+    assert (nf, nm, len(heads)) == (whole * per_f + len(cut_exp[0]), whole * per_m + len(cut_exp[1]), whole * per_h + len(cut_heads)), case
+    ks = np.arange(whole)
+    assert np.array_equal(heads[:whole * per_h].reshape(whole, per_h), np.array(heads0)[None, :] + PERIOD * ks[:, None]), case
+    assert heads[whole * per_h:].tolist() == [whole * PERIOD + h for h in cut_heads], case
+
+    F = fixes[:whole * per_f].reshape(whole, per_f)
+    assert F[0].tobytes() == alone.tobytes(), case                     # the carry behind period 0 changes nothing of its rows
+    for name in ("bits", "flags", "icao", "n_rx", "n_heard", "status", "iters"):
+        assert (F[name] == F[0][name][None]).all(), (case, name)
+    assert np.array_equal(F["first"], F[0]["first"][None, :] + per_m * ks[:, None]), case
+    assert np.array_equal(F["ts"], F[0]["ts"][None, :] + SPACING * ks[:, None]), case
+    M_s, M_t = ms[:whole * per_m].reshape(whole, per_m), mt[:whole * per_m].reshape(whole, per_m)
+    assert (M_s == M_s[0][None, :]).all() and np.array_equal(M_t, M_t[0][None, :] + SPACING * ks[:, None]), case
+    for name in ("x", "y", "z", "rms_m"):
+        assert np.array_equal(F[name].view(np.uint64), np.broadcast_to(F[0][name].view(np.uint64)[None, :], F[name].shape)), (case, name)
+    shifted = F[0]["t_tx"][None, :] + SPACING * ks[:, None]
+    assert (np.abs(F["t_tx"] - shifted) <= np.spacing(shifted)).all(), case
+
+    for k in sorted({0, whole - 1} | ({524288 // PERIOD} if n > 524288 + PERIOD else set())):
+        rows = F[k].copy()
+        rows["first"] -= per_m * k
+        compare((case, k), rows, M_s[k], M_t[k], *MR.mlat(replay_rows(p0, k), WINDOW, RX8), truth=truth)
+    if cut:
+        rows = fixes[whole * per_f:].copy()
+        rows["first"] -= per_m * whole
+        compare((case, "cut"), rows, ms[whole * per_m:], mt[whole * per_m:], *cut_exp, converge=False)
+    return fixes, ms, mt, heads, p0, per_f, per_m
+
+
+N_SCAN = 256 * 256 + 257          # 258 chunks: k_mlat_scan's threads take two each, thread 128 the last, threads 129 .. 255 none
+
+
+def test_the_scan_with_more_than_256_chunks(sim):
+    """k_mlat_scan with per = 2: a range of 65 793 entries, the smallest that reaches the path (1 012 periods and 13 entries of
+    the next).  The emulator takes 8 s for it (measured where this was written); the device runs the same test in tests/test_gpu_mlat_device.py."""
+    fixes, ms, mt, heads, *_ = check_periodic(sim, "scan", N_SCAN)
+    assert (N_SCAN + 255) // 256 == 258 and len(fixes) >= 2 * (N_SCAN // PERIOD)
+
+
+def carry_words_numpy(ts, bits, mk, stream, zero_hash=0):
+    """The carry's words in NumPy, as tests/sim/mlat_driver.cpp's make_carry states them -- only for a machine where the emulator
+    library cannot be built; test_the_carry_words_in_numpy holds them equal to the emulator's."""
+    n = len(ts)
+    b16 = np.zeros((n, 16), np.uint8)
+    b16[:, :14] = bits
+    w = b16.view("<u8").reshape(n, 2)
+    mk64 = mk.astype(np.uint64)
+    a = np.where(mk == 0, np.uint64(0), np.where(mk == 2, w[:, 0], w[:, 0] & np.uint64(0x00FFFFFFFFFFFFFF)))
+    b = np.where(mk == 2, w[:, 1], np.uint64(0))
+    with np.errstate(over="ignore"):
+        k = a ^ (b * np.uint64(0x9E3779B97F4A7C15))
+        k ^= k >> np.uint64(33)
+        k *= np.uint64(0xFF51AFD7ED558CCD)
+        k ^= k >> np.uint64(33)
+        k *= np.uint64(0xC4CEB9FE1A85EC53)
+        k ^= k >> np.uint64(33)
+    h = np.uint64(0) if zero_hash else (k & np.uint64(0xFFFFFFFF))
+    out = np.zeros((n, 4), np.uint64)
+    out[:, 0] = np.asarray(ts, np.float64).view(np.uint64)
+    out[:, 1], out[:, 2] = a, b
+    out[:, 3] = h | ((stream.astype(np.uint64) & np.uint64(0xFFFFFF)) << np.uint64(32)) | (mk64 << np.uint64(56))
+    return out
+
+
+def emulator_words(sim, ts, bits, mk, stream, zero_hash=0):
+    """-> [n, 4] uint64: sim_mlat_carry's words"""
+    out = np.zeros((len(ts), 4), np.uint64)
+    ts, bits, mk, stream = (np.ascontiguousarray(x) for x in (ts, bits, mk, stream))
+    sim.sim_mlat_carry(ts.ctypes.data_as(vp), bits.ctypes.data_as(vp), mk.ctypes.data_as(vp), stream.ctypes.data_as(vp), ctypes.c_int(len(ts)),
+                       ctypes.c_int(zero_hash), out.ctypes.data_as(vp))
+    return out
+
+
+def test_the_carry_words_in_numpy(sim):
+    """carry_words_numpy = the emulator driver's words: the period (long, short, marker 0) and random bytes, markers and streams"""
+    rng = np.random.default_rng(5)
+    n = 500
+    rand = (EPOCH + np.sort(rng.uniform(0, 1, n)), rng.integers(0, 256, (n, 14)).astype(np.uint8), rng.integers(0, 3, n).astype(np.int32),
+            rng.integers(0, 2 ** 24, n).astype(np.int32))
+    for arrays in (period0().arrays(), rand):
+        for zero_hash in (0, 1):
+            assert emulator_words(sim, *arrays, zero_hash).tobytes() == carry_words_numpy(*arrays, zero_hash).tobytes()
 
 
 def test_the_oracles_own_sensitivity():
