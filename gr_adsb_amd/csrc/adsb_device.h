@@ -3092,23 +3092,57 @@ __global__ void __launch_bounds__(kThreads) k_fleet_fold(FleetArgs a) {
   if (fresh) atomicAdd(&a.count[fleet_item_of(a, (int)(unsigned)k0)].planes, 1);      // (a slot's records are one stream's)
 }
 
+// A slot's stream, and: the slot belongs to an existing stream's current generation (a reset stream's stale slots do not).
+// Both rehashes and both key scans ask this.  (Two functions, not one with the stream as an out-parameter: that form costs
+// k_merge_keys, which goes on using the stream, a 64-bit address for gen[stream].  For the same reason the bodies below take
+// their aggregates by value where a reference changes an instance's code.)
+__device__ __forceinline__ unsigned fleet_stream(unsigned long long key) {
+  return (unsigned)(key >> kFleetAddrBits) & ((1u << kFleetStreamBits) - 1u);
+}
+__device__ __forceinline__ bool fleet_current(unsigned long long key, unsigned stream, const unsigned* gen, int n_streams) {
+  return stream < (unsigned)n_streams && gen[stream] == (unsigned)(key >> (kFleetAddrBits + kFleetStreamBits));
+}
+
 // Growth, purge: the live slots of the old store (their stream still in the key's generation) into the new, empty one.
 // renumber: every announcement made so far gets ordering key 0 -- they all precede the calls to come, and only "earlier
 // than this record" is ever asked -- so that the host can start its call numbers over (at 1) before they run out.
-__global__ void __launch_bounds__(kThreads) k_fleet_rehash(FleetStore from, FleetStore to, const unsigned* gen, int n_streams, int renumber,
-                                                           int* error) {
+// AGES (ADSB_FLAG_PLANE_AGES: k_ages_rehash; the "plane ages" section below says what last_seen is): a plane's last_seen
+// moves with its slot, and where g.cutoffs is set the rehash is the fleet's expiry -- open addressing with linear probing
+// cannot delete in place, so a plane whose last_seen is below cutoffs[stream] (LLONG_MIN where a stream is not selected:
+// nothing is below it) is left behind, `to` an empty store of the SAME size, and counted in removed[stream] (slots and
+// planes: one each), which the host takes off the stream's books.
+struct FleetAges {
+  const long long* from_seen;              // [from.mask + 1]
+  long long* to_seen;                      // [to.mask + 1]
+  const long long* cutoffs;                // [n_streams]; null: no expiry
+  FleetCount* removed;                     // [n_streams], zero before; null iff cutoffs is
+};
+template <bool AGES>
+__device__ __forceinline__ void fleet_rehash_body(FleetStore from, FleetStore to, const unsigned* gen, int n_streams,
+                                                  int renumber, int* error, FleetAges g) {
   for (unsigned i = blockIdx.x * kThreads + threadIdx.x; i <= from.mask; i += gridDim.x * kThreads) {
     const unsigned long long key = from.keys[i];
     if (key == kFleetEmpty) continue;
-    const unsigned stream = (unsigned)(key >> kFleetAddrBits) & ((1u << kFleetStreamBits) - 1u);
-    if (stream >= (unsigned)n_streams || gen[stream] != (unsigned)(key >> (kFleetAddrBits + kFleetStreamBits))) continue;
+    const unsigned stream = fleet_stream(key);
+    if (!fleet_current(key, stream, gen, n_streams)) continue;
+    const bool plane = AGES && (from.planes[i].present & kHasPlane) != 0;
+    if (plane && g.cutoffs && g.from_seen[i] < g.cutoffs[stream]) {
+      atomicAdd(&g.removed[stream].slots, 1);
+      atomicAdd(&g.removed[stream].planes, 1);
+      continue;
+    }
     bool claimed = false;
     const unsigned h = fleet_slot(to, key, true, &claimed);
     if (h == kFleetNone || !claimed) { ADSB_AIR_STORE(error, 1); continue; }
     const unsigned long long ann = from.ann[i];
     to.ann[h] = (renumber && ann != kAirEmpty) ? 0ull : ann;
     to.planes[h] = from.planes[i];
+    if (plane) g.to_seen[h] = g.from_seen[i];
   }
+}
+__global__ void __launch_bounds__(kThreads) k_fleet_rehash(FleetStore from, FleetStore to, const unsigned* gen, int n_streams, int renumber,
+                                                           int* error) {
+  fleet_rehash_body<false>(from, to, gen, n_streams, renumber, error, FleetAges{});
 }
 
 // ---- snapshots of the decoders' plane tables (adsb_planes, adsb_stream_planes): plane_dict read back -------------------------
@@ -3145,6 +3179,13 @@ __device__ __forceinline__ bool planes_live(const PlanesDense& a, unsigned long 
   const Plane* p = &a.planes[addr];
   return p->epoch == a.epoch && (p->present & kHasPlane) != 0;
 }
+// The chunk walk: the first of lane l's two addresses in iteration r of chunk c, and their two keys in one 16-byte load
+__device__ __forceinline__ unsigned planes_pair_addr(const PlanesDense& a, unsigned c, int r, int lane) {
+  return a.lo + c * kPlanesChunk + (unsigned)(r * kPlanesStep + 2 * lane);
+}
+__device__ __forceinline__ stream_v16 planes_pair(const PlanesDense& a, unsigned addr) {
+  return *reinterpret_cast<const stream_v16*>(&a.table[addr]);
+}
 __device__ __forceinline__ void planes_row(DecRow* rows, int cap, unsigned j, const Plane* src, unsigned addr) {
   if (j >= (unsigned)cap) return;
   const Plane p = *src;
@@ -3161,9 +3202,9 @@ __global__ void __launch_bounds__(kThreads) k_planes_tally(PlanesDense a, unsign
   for (unsigned c = blockIdx.x * kWaves + (unsigned)wave; c < n_chunks; c += gridDim.x * kWaves) {
     unsigned n = 0;
     for (int r = 0; r < kPlanesChunk / kPlanesStep; ++r) {
-      const unsigned addr = a.lo + c * kPlanesChunk + (unsigned)(r * kPlanesStep + 2 * lane);
+      const unsigned addr = planes_pair_addr(a, c, r, lane);
       if (addr < a.hi) {
-        const stream_v16 k = *reinterpret_cast<const stream_v16*>(&a.table[addr]);
+        const stream_v16 k = planes_pair(a, addr);
         n += (planes_live(a, k[0], addr) ? 1u : 0u) + (planes_live(a, k[1], addr + 1u) ? 1u : 0u);
       }
     }
@@ -3173,8 +3214,17 @@ __global__ void __launch_bounds__(kThreads) k_planes_tally(PlanesDense a, unsign
 }
 
 // base = the scanned counts.  A chunk without planes is not read again.  Inside an iteration lane l's two addresses precede
-// lane l + 1's.
-__global__ void __launch_bounds__(kThreads) k_planes_emit(PlanesDense a, const unsigned* base, int cap, DecRow* rows) {
+// lane l + 1's.  AGES (ADSB_FLAG_PLANE_AGES: k_ages_emit; seen: the planes' last_seen, by address): seen_out[j] belongs to
+// rows[j], and either output may be null.
+template <bool AGES>
+__device__ __forceinline__ void planes_emit_row(const PlanesDense& a, int cap, unsigned j, unsigned addr, DecRow* rows,
+                                                const long long* seen, long long* seen_out) {
+  if (!AGES || rows) planes_row(rows, cap, j, &a.planes[addr], addr);
+  if (AGES && seen_out && j < (unsigned)cap) seen_out[j] = seen[addr];
+}
+template <bool AGES>
+__device__ __forceinline__ void planes_emit_body(const PlanesDense& a, const unsigned* base, int cap, DecRow* rows, const long long* seen,
+                                                 long long* seen_out) {
   const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
   const unsigned long long lt = (1ull << lane) - 1ull;
   const unsigned n_chunks = planes_chunks(a);
@@ -3182,20 +3232,23 @@ __global__ void __launch_bounds__(kThreads) k_planes_emit(PlanesDense a, const u
     unsigned pos = base[c];
     if (base[c + 1] == pos) continue;
     for (int r = 0; r < kPlanesChunk / kPlanesStep; ++r) {
-      const unsigned addr = a.lo + c * kPlanesChunk + (unsigned)(r * kPlanesStep + 2 * lane);
+      const unsigned addr = planes_pair_addr(a, c, r, lane);
       bool l0 = false, l1 = false;
       if (addr < a.hi) {
-        const stream_v16 k = *reinterpret_cast<const stream_v16*>(&a.table[addr]);
+        const stream_v16 k = planes_pair(a, addr);
         l0 = planes_live(a, k[0], addr);
         l1 = planes_live(a, k[1], addr + 1u);
       }
       const unsigned long long m0 = __ballot(l0), m1 = __ballot(l1);
       const unsigned j = pos + (unsigned)__popcll(m0 & lt) + (unsigned)__popcll(m1 & lt);
-      if (l0) planes_row(rows, cap, j, &a.planes[addr], addr);
-      if (l1) planes_row(rows, cap, j + (l0 ? 1u : 0u), &a.planes[addr + 1u], addr + 1u);
+      if (l0) planes_emit_row<AGES>(a, cap, j, addr, rows, seen, seen_out);
+      if (l1) planes_emit_row<AGES>(a, cap, j + (l0 ? 1u : 0u), addr + 1u, rows, seen, seen_out);
       pos += (unsigned)__popcll(m0) + (unsigned)__popcll(m1);
     }
   }
+}
+__global__ void __launch_bounds__(kThreads) k_planes_emit(PlanesDense a, const unsigned* base, int cap, DecRow* rows) {
+  planes_emit_body<false>(a, base, cap, rows, nullptr, nullptr);
 }
 
 // The fleet (ADSB_FLAG_STREAM_DECODE): k_planes_store_keys scans the store's keys and compacts the 44-bit stream << 24 |
@@ -3210,18 +3263,23 @@ struct PlanesFleet {
   int n_streams;
 };
 constexpr unsigned long long kPlanesKeyMask = (1ull << (kFleetAddrBits + kFleetStreamBits)) - 1ull;
-__global__ void __launch_bounds__(kThreads) k_planes_store_keys(PlanesFleet a, unsigned long long* keys, int cap, int* count) {
+// MERGED (k_merge_keys, the merged picture below; seen: beside the store's slots): the plane's last_seen must not be below
+// the cutoff either, and the key comes out turned round, address << 20 | stream.
+template <bool MERGED>
+__device__ __forceinline__ void planes_keys_body(PlanesFleet a, const long long* seen, long long cutoff, unsigned long long* keys,
+                                                 int cap, int* count) {
   const int lane = (int)(threadIdx.x & 63);
   const unsigned long long lt = (1ull << lane) - 1ull;
   // (the store has a power of two >= 256 slots: a wavefront's 64 slots all exist)
   for (unsigned w0 = blockIdx.x * kThreads + (threadIdx.x & ~63u); w0 <= a.s.mask; w0 += gridDim.x * kThreads) {
     const unsigned i = w0 + (unsigned)lane;
     const unsigned long long key = a.s.keys[i];
+    unsigned stream = 0;
     bool keep = false;
     if (key != kFleetEmpty) {
-      const unsigned stream = (unsigned)(key >> kFleetAddrBits) & ((1u << kFleetStreamBits) - 1u);
-      keep = stream < (unsigned)a.n_streams && a.gen[stream] == (unsigned)(key >> (kFleetAddrBits + kFleetStreamBits)) &&
-             (!a.sel_bits || ((a.sel_bits[stream >> 5] >> (stream & 31u)) & 1u)) && (a.s.planes[i].present & kHasPlane) != 0;
+      stream = fleet_stream(key);
+      keep = fleet_current(key, stream, a.gen, a.n_streams) && (!a.sel_bits || ((a.sel_bits[stream >> 5] >> (stream & 31u)) & 1u)) &&
+             (a.s.planes[i].present & kHasPlane) != 0 && (!MERGED || seen[i] >= cutoff);
     }
     const unsigned long long m = __ballot(keep);
     if (m == 0) continue;
@@ -3229,14 +3287,21 @@ __global__ void __launch_bounds__(kThreads) k_planes_store_keys(PlanesFleet a, u
     if (lane == 0) b0 = atomicAdd(count, __popcll(m));
     b0 = __shfl(b0, 0);
     const int j = b0 + __popcll(m & lt);
-    if (keep && j < cap) keys[j] = key & kPlanesKeyMask;
+    if (keep && j < cap)
+      keys[j] = MERGED ? ((key & ((1ull << kFleetAddrBits) - 1ull)) << kFleetStreamBits) | stream : key & kPlanesKeyMask;
   }
+}
+__global__ void __launch_bounds__(kThreads) k_planes_store_keys(PlanesFleet a, unsigned long long* keys, int cap, int* count) {
+  planes_keys_body<false>(a, nullptr, 0, keys, cap, count);
 }
 
 // sel: the selected streams in ascending order (null: stream i is the i-th); first[i] = the first row whose key is not below
-// sel[i] << 24, first[n_sel] = n
-__global__ void __launch_bounds__(kThreads) k_planes_store_emit(PlanesFleet a, const unsigned long long* sorted, int n, const int* sel,
-                                                                int n_sel, DecRow* rows, int* first, int* error) {
+// sel[i] << 24, first[n_sel] = n.  AGES (ADSB_FLAG_PLANE_AGES: k_ages_store_emit; seen: beside the store's slots):
+// seen_out[j] belongs to rows[j], and rows or seen_out may be null.
+template <bool AGES>
+__device__ __forceinline__ void planes_store_emit_body(PlanesFleet a, const unsigned long long* sorted, int n, const int* sel,
+                                                       int n_sel, DecRow* rows, int* first, int* error, const long long* seen,
+                                                       long long* seen_out) {
   const int t0 = (int)(blockIdx.x * kThreads + threadIdx.x), step = (int)(gridDim.x * kThreads);
   for (int j = t0; j < n; j += step) {
     const unsigned long long key = sorted[j];
@@ -3244,7 +3309,8 @@ __global__ void __launch_bounds__(kThreads) k_planes_store_emit(PlanesFleet a, c
     bool claimed = false;
     const unsigned h = fleet_slot(a.s, ((unsigned long long)a.gen[stream] << (kFleetAddrBits + kFleetStreamBits)) | key, false, &claimed);
     if (h == kFleetNone) { ADSB_AIR_STORE(error, 1); continue; }
-    planes_row(rows, n, (unsigned)j, &a.s.planes[h], (unsigned)key & ((1u << kFleetAddrBits) - 1u));
+    if (!AGES || rows) planes_row(rows, n, (unsigned)j, &a.s.planes[h], (unsigned)key & ((1u << kFleetAddrBits) - 1u));
+    if (AGES && seen_out) seen_out[j] = seen[h];
   }
   for (int i = t0; first && i <= n_sel; i += step) {
     int lo = 0, hi = n;
@@ -3257,6 +3323,10 @@ __global__ void __launch_bounds__(kThreads) k_planes_store_emit(PlanesFleet a, c
     } else lo = n;
     first[i] = lo;
   }
+}
+__global__ void __launch_bounds__(kThreads) k_planes_store_emit(PlanesFleet a, const unsigned long long* sorted, int n, const int* sel,
+                                                                int n_sel, DecRow* rows, int* first, int* error) {
+  planes_store_emit_body<false>(a, sorted, n, sel, n_sel, rows, first, error, nullptr, nullptr);
 }
 
 // ---- plane ages (ADSB_FLAG_PLANE_AGES): last_seen read back, and expiry by last-seen age --------------------------------------
@@ -3270,7 +3340,7 @@ __global__ void __launch_bounds__(kThreads) k_planes_store_emit(PlanesFleet a, c
 //
 // One decoder: one scan in k_planes_tally's access pattern.  A stale plane's first-announcement key becomes kAirEmpty and its
 // entry's epoch 0 (no decoder has epoch 0: no plane); removed: one atomic per wavefront that removed any.
-struct PlanesExpire {
+struct PlanesExpire {                      // (the kernel's argument as the host fills it: the layout stays)
   unsigned long long* table;               // indexed by address
   Plane* planes;
   const long long* seen;
@@ -3278,20 +3348,20 @@ struct PlanesExpire {
   unsigned lo, hi;                         // as PlanesDense
   long long cutoff;
 };
+__device__ __forceinline__ PlanesDense planes_dense(const PlanesExpire& a) { return PlanesDense{a.table, a.planes, a.epoch, a.lo, a.hi}; }
 __device__ __forceinline__ bool planes_stale(const PlanesExpire& a, unsigned long long key, unsigned addr) {
-  if (key == kAirEmpty) return false;
-  const Plane* p = &a.planes[addr];
-  return p->epoch == a.epoch && (p->present & kHasPlane) != 0 && a.seen[addr] < a.cutoff;
+  return planes_live(planes_dense(a), key, addr) && a.seen[addr] < a.cutoff;
 }
 __global__ void __launch_bounds__(kThreads) k_ages_expire(PlanesExpire a, unsigned long long* removed) {
   const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
-  const unsigned n_chunks = (a.hi - a.lo + kPlanesChunk - 1u) / kPlanesChunk;
+  const PlanesDense d = planes_dense(a);
+  const unsigned n_chunks = planes_chunks(d);
   for (unsigned c = blockIdx.x * kWaves + (unsigned)wave; c < n_chunks; c += gridDim.x * kWaves) {
     unsigned n = 0;
     for (int r = 0; r < kPlanesChunk / kPlanesStep; ++r) {
-      const unsigned addr = a.lo + c * kPlanesChunk + (unsigned)(r * kPlanesStep + 2 * lane);
+      const unsigned addr = planes_pair_addr(d, c, r, lane);
       if (addr < a.hi) {
-        const stream_v16 k = *reinterpret_cast<const stream_v16*>(&a.table[addr]);
+        const stream_v16 k = planes_pair(d, addr);
         for (unsigned q = 0; q < 2u; ++q)
           if (planes_stale(a, k[q], addr + q)) {
             a.table[addr + q] = kAirEmpty;
@@ -3305,103 +3375,25 @@ __global__ void __launch_bounds__(kThreads) k_ages_expire(PlanesExpire a, unsign
   }
 }
 
-// k_planes_emit with the planes' last_seen: seen_out[j] belongs to rows[j]; either output may be null
+// The snapshots with the planes' last_seen, and the fleet's expiry: the AGES instances of the bodies above
 __global__ void __launch_bounds__(kThreads) k_ages_emit(PlanesDense a, const unsigned* base, int cap, DecRow* rows,
                                                         const long long* seen, long long* seen_out) {
-  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  const unsigned n_chunks = planes_chunks(a);
-  for (unsigned c = blockIdx.x * kWaves + (unsigned)wave; c < n_chunks; c += gridDim.x * kWaves) {
-    unsigned pos = base[c];
-    if (base[c + 1] == pos) continue;
-    for (int r = 0; r < kPlanesChunk / kPlanesStep; ++r) {
-      const unsigned addr = a.lo + c * kPlanesChunk + (unsigned)(r * kPlanesStep + 2 * lane);
-      bool l0 = false, l1 = false;
-      if (addr < a.hi) {
-        const stream_v16 k = *reinterpret_cast<const stream_v16*>(&a.table[addr]);
-        l0 = planes_live(a, k[0], addr);
-        l1 = planes_live(a, k[1], addr + 1u);
-      }
-      const unsigned long long m0 = __ballot(l0), m1 = __ballot(l1);
-      const unsigned j0 = pos + (unsigned)__popcll(m0 & lt) + (unsigned)__popcll(m1 & lt), j1 = j0 + (l0 ? 1u : 0u);
-      if (l0) {
-        if (rows) planes_row(rows, cap, j0, &a.planes[addr], addr);
-        if (seen_out && j0 < (unsigned)cap) seen_out[j0] = seen[addr];
-      }
-      if (l1) {
-        if (rows) planes_row(rows, cap, j1, &a.planes[addr + 1u], addr + 1u);
-        if (seen_out && j1 < (unsigned)cap) seen_out[j1] = seen[addr + 1u];
-      }
-      pos += (unsigned)__popcll(m0) + (unsigned)__popcll(m1);
-    }
-  }
+  planes_emit_body<true>(a, base, cap, rows, seen, seen_out);
 }
-
-// The fleet: open addressing with linear probing cannot delete in place, so expiry is k_fleet_rehash with a predicate, into
-// an empty store of the SAME size; a flagged context's growth / purge / renumbering rehash is the same kernel without
-// cutoffs, so that last_seen moves with its slot.  cutoffs[stream] (LLONG_MIN where a stream is not selected: nothing is
-// below it); a dropped slot is counted in removed[stream] (slots and planes: one each), which the host takes off the stream's
-// books.  A reset stream's stale slots are dropped as in every rehash.
-struct FleetAges {
-  const long long* from_seen;              // [from.mask + 1]
-  long long* to_seen;                      // [to.mask + 1]
-  const long long* cutoffs;                // [n_streams]; null: no expiry
-  FleetCount* removed;                     // [n_streams], zero before; null iff cutoffs is
-};
 __global__ void __launch_bounds__(kThreads) k_ages_rehash(FleetStore from, FleetStore to, const unsigned* gen, int n_streams,
                                                           int renumber, int* error, FleetAges g) {
-  for (unsigned i = blockIdx.x * kThreads + threadIdx.x; i <= from.mask; i += gridDim.x * kThreads) {
-    const unsigned long long key = from.keys[i];
-    if (key == kFleetEmpty) continue;
-    const unsigned stream = (unsigned)(key >> kFleetAddrBits) & ((1u << kFleetStreamBits) - 1u);
-    if (stream >= (unsigned)n_streams || gen[stream] != (unsigned)(key >> (kFleetAddrBits + kFleetStreamBits))) continue;
-    const bool plane = (from.planes[i].present & kHasPlane) != 0;
-    if (plane && g.cutoffs && g.from_seen[i] < g.cutoffs[stream]) {
-      atomicAdd(&g.removed[stream].slots, 1);
-      atomicAdd(&g.removed[stream].planes, 1);
-      continue;
-    }
-    bool claimed = false;
-    const unsigned h = fleet_slot(to, key, true, &claimed);
-    if (h == kFleetNone || !claimed) { ADSB_AIR_STORE(error, 1); continue; }
-    const unsigned long long ann = from.ann[i];
-    to.ann[h] = (renumber && ann != kAirEmpty) ? 0ull : ann;
-    to.planes[h] = from.planes[i];
-    if (plane) g.to_seen[h] = g.from_seen[i];
-  }
+  fleet_rehash_body<true>(from, to, gen, n_streams, renumber, error, g);
 }
-
-// k_planes_store_emit with the planes' last_seen (seen: beside the store's slots); rows or seen_out may be null
 __global__ void __launch_bounds__(kThreads) k_ages_store_emit(PlanesFleet a, const unsigned long long* sorted, int n,
                                                               const int* sel, int n_sel, DecRow* rows, int* first, int* error,
                                                               const long long* seen, long long* seen_out) {
-  const int t0 = (int)(blockIdx.x * kThreads + threadIdx.x), step = (int)(gridDim.x * kThreads);
-  for (int j = t0; j < n; j += step) {
-    const unsigned long long key = sorted[j];
-    const unsigned stream = (unsigned)(key >> kFleetAddrBits);
-    bool claimed = false;
-    const unsigned h = fleet_slot(a.s, ((unsigned long long)a.gen[stream] << (kFleetAddrBits + kFleetStreamBits)) | key, false, &claimed);
-    if (h == kFleetNone) { ADSB_AIR_STORE(error, 1); continue; }
-    if (rows) planes_row(rows, n, (unsigned)j, &a.s.planes[h], (unsigned)key & ((1u << kFleetAddrBits) - 1u));
-    if (seen_out) seen_out[j] = seen[h];
-  }
-  for (int i = t0; first && i <= n_sel; i += step) {
-    int lo = 0, hi = n;
-    if (i < n_sel) {
-      const unsigned long long want = (unsigned long long)(unsigned)(sel ? sel[i] : i) << kFleetAddrBits;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sorted[mid] < want) lo = mid + 1; else hi = mid;
-      }
-    } else lo = n;
-    first[i] = lo;
-  }
+  planes_store_emit_body<true>(a, sorted, n, sel, n_sel, rows, first, error, seen, seen_out);
 }
 
 // ---- the fleet's merged picture (adsb_stream_planes_merged): one row per aircraft out of every receiver's plane_dict ----------
 // Read-only, as the snapshots are.  A CONTRIBUTING entry is a live plane of a selected stream's current generation whose
-// last_seen is not below the cutoff.  k_merge_keys is k_planes_store_keys with that predicate and the 44-bit key turned
-// round, address << 20 | stream, so that the library's radix sort (eleven nibbles from bit 0) leaves an aircraft's entries
+// last_seen is not below the cutoff.  k_merge_keys is planes_keys_body's MERGED instance: that predicate, and the 44-bit key
+// turned round, address << 20 | stream, so that the library's radix sort (eleven nibbles from bit 0) leaves an aircraft's entries
 // side by side, in ascending stream order.  Row j of the sorted keys is a HEAD when it is the first of its address;
 // k_merge_heads counts the heads of every 64 rows (one wavefront's ballot: no atomic, no LDS), k_dec_sort_scan turns the
 // counts into each 64 rows' first output row and, one entry behind the last, the total; k_merge_emit runs one lane per head:
@@ -3421,28 +3413,7 @@ __device__ __forceinline__ bool merge_head(const unsigned long long* sorted, int
 
 __global__ void __launch_bounds__(kThreads) k_merge_keys(PlanesFleet a, const long long* seen, long long cutoff,
                                                          unsigned long long* keys, int cap, int* count) {
-  const int lane = (int)(threadIdx.x & 63);
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  for (unsigned w0 = blockIdx.x * kThreads + (threadIdx.x & ~63u); w0 <= a.s.mask; w0 += gridDim.x * kThreads) {
-    const unsigned i = w0 + (unsigned)lane;
-    const unsigned long long key = a.s.keys[i];
-    unsigned stream = 0;
-    bool keep = false;
-    if (key != kFleetEmpty) {
-      stream = (unsigned)(key >> kFleetAddrBits) & ((1u << kFleetStreamBits) - 1u);
-      keep = stream < (unsigned)a.n_streams && a.gen[stream] == (unsigned)(key >> (kFleetAddrBits + kFleetStreamBits)) &&
-             (!a.sel_bits || ((a.sel_bits[stream >> 5] >> (stream & 31u)) & 1u)) && (a.s.planes[i].present & kHasPlane) != 0 &&
-             seen[i] >= cutoff;
-    }
-    const unsigned long long m = __ballot(keep);
-    if (m == 0) continue;
-    int b0 = 0;
-    if (lane == 0) b0 = atomicAdd(count, __popcll(m));
-    b0 = __shfl(b0, 0);
-    const int j = b0 + __popcll(m & lt);
-    if (keep && j < cap)
-      keys[j] = ((key & ((1ull << kFleetAddrBits) - 1ull)) << kFleetStreamBits) | stream;
-  }
+  planes_keys_body<true>(a, seen, cutoff, keys, cap, count);
 }
 
 // counts[c] = the heads among rows 64 c .. 64 c + 63; counts[number of chunks] = 0 (the scan leaves the total there)
