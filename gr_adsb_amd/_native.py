@@ -76,6 +76,20 @@ MLAT_DTYPE = np.dtype([("ts", "<f8"), ("x", "<f8"), ("y", "<f8"), ("z", "<f8"), 
 assert MLAT_DTYPE.itemsize == 88
 MLAT_OK, MLAT_NO_CONVERGE, MLAT_SINGULAR = 0, 1, 2       # ADSB_MLAT_*
 MLAT_C = 299702547.0         # ADSB_MLAT_C, m/s
+# adsb_stream_mlat_rule: the rule a caller states (adsb_mlat_rule) and the row beside each fix (adsb_mlat_aux)
+MLAT_SOLVER_GN, MLAT_SOLVER_LM = 0, 1                     # ADSB_MLAT_SOLVER_*
+MLAT_RESTART, MLAT_ALTITUDE = 1, 2                       # ADSB_MLAT_RESTART, ADSB_MLAT_ALTITUDE
+MLAT_AUX_AIDED, MLAT_AUX_RESTARTED, MLAT_AUX_SECOND_KEPT = 1, 2, 4
+MLAT_AUX_DTYPE = np.dtype([("up_m", "<f8"), ("lambda", "<f8"), ("alt_ft", "<i4"), ("tries", "<i4"), ("flags", "<u4"), ("reserved", "<i4")])
+assert MLAT_AUX_DTYPE.itemsize == 32
+
+
+class MLAT_RULE(ctypes.Structure):
+    _fields_ = [("solver", ctypes.c_int32), ("flags", ctypes.c_int32), ("min_rx", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("alt_weight", ctypes.c_double)]
+
+
+assert ctypes.sizeof(MLAT_RULE) == 24
 INT64_MIN = -(1 << 63)       # the cutoff that hides nothing
 STREAM_END = 1               # ADSB_STREAM_END: the stream's last item
 STREAM_FRESH_EOB = -(1 << 61)    # the carried end-of-burst offset of a fresh stream
@@ -97,7 +111,7 @@ EXPORTS = [
     "adsb_planes_seen", "adsb_stream_planes_seen", "adsb_planes_expire", "adsb_stream_planes_expire",
     "adsb_stream_planes_merged", "adsb_stream_last_order", "adsb_streams_decoder_reset",
     "adsb_streams_set_dedup", "adsb_stream_last_duplicates", "adsb_stream_dedup_stats",
-    "adsb_stream_set_ecef", "adsb_stream_mlat", "adsb_stream_mlat_stats", "adsb_geodetic_to_ecef", "adsb_ecef_to_geodetic",
+    "adsb_stream_set_ecef", "adsb_stream_mlat", "adsb_stream_mlat_rule", "adsb_stream_mlat_stats", "adsb_geodetic_to_ecef", "adsb_ecef_to_geodetic",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
 ]
 
@@ -220,6 +234,7 @@ def load():
     lib.adsb_stream_dedup_stats.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(c.c_double)]
     lib.adsb_stream_set_ecef.argtypes = [vp, i32, c.c_double, c.c_double, c.c_double]
     lib.adsb_stream_mlat.argtypes = [vp, c.c_double, c.c_double, i32, vp, i32, c.POINTER(i32), vp, vp, i32, c.POINTER(i32)]
+    lib.adsb_stream_mlat_rule.argtypes = [vp, c.c_double, c.c_double, c.POINTER(MLAT_RULE), vp, vp, i32, c.POINTER(i32), vp, vp, i32, c.POINTER(i32)]
     lib.adsb_stream_mlat_stats.argtypes = [vp, c.POINTER(i32), c.POINTER(c.c_double)]
     lib.adsb_geodetic_to_ecef.argtypes = [c.c_double] * 3 + [c.POINTER(c.c_double)] * 3
     lib.adsb_geodetic_to_ecef.restype = None
@@ -662,6 +677,23 @@ class Context:
                 continue
             self._chk(rc)
             return fixes[:n.value], ms[:m.value], mt[:m.value]
+
+    def stream_mlat_rule(self, rule, t_lo=-np.inf, t_hi=np.inf, cap=0, member_cap=0):
+        """stream_mlat with the rule stated by the caller (adsb_stream_mlat_rule; rule: MLAT_RULE) -> (fixes: MLAT_DTYPE[n],
+        aux: MLAT_AUX_DTYPE[n], member_stream, member_ts).  Asks once more after -ENOSPC, as stream_mlat does."""
+        cap, member_cap = int(cap), int(member_cap)
+        n, m = ctypes.c_int32(0), ctypes.c_int32(0)
+        for attempt in (0, 1):
+            fixes, aux = np.zeros(cap, dtype=MLAT_DTYPE), np.zeros(cap, dtype=MLAT_AUX_DTYPE)
+            ms, mt = np.zeros(member_cap, dtype=np.int32), np.zeros(member_cap, dtype=np.float64)
+            rc = self.lib.adsb_stream_mlat_rule(self._h, float(t_lo), float(t_hi), ctypes.byref(rule), fixes.ctypes.data if cap else None,
+                                                aux.ctypes.data if cap else None, cap, ctypes.byref(n), ms.ctypes.data if member_cap else None,
+                                                mt.ctypes.data if member_cap else None, member_cap, ctypes.byref(m))
+            if rc == -28 and attempt == 0:
+                cap, member_cap = max(cap, n.value), max(member_cap, m.value)
+                continue
+            self._chk(rc)
+            return fixes[:n.value], aux[:n.value], ms[:m.value], mt[:m.value]
 
     def stream_mlat_stats(self):
         """(streams with a position, ts_ulp_m: what the double's spacing at the carry's latest timestamp is worth in metres)"""

@@ -32,6 +32,7 @@
 #include "adsb_shared.h"
 #include "adsb_dedup.h"
 #include "adsb_mlat.h"
+#include "adsb_mlat_rule.h"
 
 // wavefront-level ordering point used by adsb_device.h: LDS traffic of one wavefront is executed in
 // program order by the hardware, this only stops the compiler from moving LDS accesses across it
@@ -333,7 +334,8 @@ struct FleetDec {
     void fresh() { hi = 0; off = cnt = 0; duplicates = 0; delivered = false; }
   } dd;
   // adsb_stream_mlat (adsb_mlat.hip): the receivers' ECEF positions (NaN: none set) -- not decoder state: only fleet_open and
-  // fleet_close touch them -- and one call's work buffer (adsb_mlat.h: Layout) with the pinned memory its counts come down to
+  // fleet_close touch them -- and one call's work buffer (adsb_mlat.h: Layout; adsb_stream_mlat_rule's damped path carves the
+  // same buffer by adsb_mlat_rule.h: RuleLayout) with the pinned memory its counts come down to
   std::vector<double> rx;
   DevBuf d_mlat;
   PinnedBuf h_mlat;
@@ -2658,6 +2660,77 @@ int adsb_stream_mlat(adsb_ctx* c, double t_lo, double t_hi, int32_t min_rx, adsb
   if (ng == 0) return 0;
   if ((e = (hipError_t)adsb_mlat_host::launch_solve(st, carry, nc, ng, D.window, n_streams, work, L))) return fail(c, -EIO, "adsb_stream_mlat: k_mlat_solve", e);
   HIPCHK(c, hipMemcpyAsync(fixes, work + L.fixes, (size_t)ng * sizeof(adsb_mlat_fix), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(member_stream, work + L.member_stream, (size_t)nm * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(member_ts, work + L.member_ts, (size_t)nm * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return 0;
+}
+
+static_assert(sizeof(adsb_mlat_aux) == adsb_mlat_host::kAuxBytes && sizeof(adsb_mlat_rule) == 24 && offsetof(adsb_mlat_aux, alt_ft) == 16 &&
+              offsetof(adsb_mlat_aux, flags) == 24, "adsb_mlat_rule.hip writes adsb_mlat_aux rows");
+
+// adsb_stream_mlat with the rule stated by the caller.  _GN is adsb_stream_mlat itself; _LM is its path with
+// adsb_mlat_rule.hip's groups and solve kernels on a work buffer carved by layout_rule, and the aux rows beside the fixes.
+int adsb_stream_mlat_rule(adsb_ctx* c, double t_lo, double t_hi, const adsb_mlat_rule* rule, adsb_mlat_fix* fixes, adsb_mlat_aux* aux, int32_t cap,
+                          int32_t* n_fixes, int32_t* member_stream, double* member_ts, int32_t member_cap, int32_t* n_members) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
+  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_mlat_rule: no streams (adsb_streams_open first)");
+  if (!rule) return fail(c, -EINVAL, "adsb_stream_mlat_rule: rule is NULL");
+  if (rule->solver != ADSB_MLAT_SOLVER_GN && rule->solver != ADSB_MLAT_SOLVER_LM) return fail(c, -EINVAL, "adsb_stream_mlat_rule: unknown solver");
+  if (rule->flags & ~(ADSB_MLAT_RESTART | ADSB_MLAT_ALTITUDE)) return fail(c, -EINVAL, "adsb_stream_mlat_rule: unknown flags");
+  if (rule->solver == ADSB_MLAT_SOLVER_GN && rule->flags != 0) return fail(c, -EINVAL, "adsb_stream_mlat_rule: flags need ADSB_MLAT_SOLVER_LM");
+  if (rule->reserved != 0) return fail(c, -EINVAL, "adsb_stream_mlat_rule: reserved is not 0");
+  const bool want_alt = (rule->flags & ADSB_MLAT_ALTITUDE) != 0;
+  if (rule->min_rx < (want_alt ? adsb_mlat_host::kMinRxAided : adsb_mlat_host::kMinRx))
+    return fail(c, -EINVAL, "adsb_stream_mlat_rule: min_rx < 4 (< 3 with ADSB_MLAT_ALTITUDE)");
+  if (want_alt && !(std::isfinite(rule->alt_weight) && rule->alt_weight > 0.0))
+    return fail(c, -EINVAL, "adsb_stream_mlat_rule: alt_weight is not finite and > 0");
+  if (rule->solver == ADSB_MLAT_SOLVER_GN) {
+    const int rc = adsb_stream_mlat(c, t_lo, t_hi, rule->min_rx, fixes, cap, n_fixes, member_stream, member_ts, member_cap, n_members);
+    if (rc == 0 && aux)
+      for (int32_t k = 0; k < *n_fixes; ++k) { memset(&aux[k], 0, sizeof aux[k]); aux[k].alt_ft = -1; }
+    return rc;
+  }
+  if (std::isnan(t_lo) || std::isnan(t_hi)) return fail(c, -EINVAL, "adsb_stream_mlat_rule: a bound is NaN");
+  if (!n_fixes || !n_members || cap < 0 || member_cap < 0 || (cap > 0 && !fixes) || (member_cap > 0 && (!member_stream || !member_ts)))
+    return fail(c, -EINVAL, "adsb_stream_mlat_rule: n_fixes / n_members, or the arrays for cap / member_cap > 0, missing");
+  int rc;
+  if ((rc = require_idle(c, kCallPending))) return rc;
+  FleetDec& F = c->fd;
+  const FleetDec::Dedup& D = F.dd;
+  *n_fixes = 0; *n_members = 0;
+  const int nc = D.cnt, n_streams = (int)(F.rx.size() / 3), min_rx = rule->min_rx;
+  if (nc == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = c->stream;
+  const adsb_mlat_host::RuleLayout L = adsb_mlat_host::layout_rule((size_t)nc, (size_t)n_streams);
+  const size_t rx_bytes = F.rx.size() * sizeof(double);
+  if ((rc = ensure(c, F.d_mlat, L.bytes)) || (rc = ensure_pinned(c, F.h_mlat, rx_bytes + 64))) return rc;
+  char* const work = (char*)F.d_mlat.p;
+  int* const got = (int*)((char*)F.h_mlat.p + rx_bytes);
+  memcpy(F.h_mlat.p, F.rx.data(), rx_bytes);
+  HIPCHK(c, hipMemcpyAsync(work + L.rx, F.h_mlat.p, rx_bytes, hipMemcpyHostToDevice, st));
+  const char* const carry = (const char*)D.d_carry[D.cur].p + (size_t)D.off * adsb_dedup_host::kEntBytes;
+  hipError_t e;
+  if ((e = (hipError_t)adsb_mlat_host::launch_heads(st, carry, nc, t_lo, t_hi, D.window, work, L))) return fail(c, -EIO, "adsb_stream_mlat_rule: the head kernels", e);
+  HIPCHK(c, hipMemcpyAsync(got, work + L.tot_heads, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const int nh = got[1];
+  if (nh < 0 || nh > nc) return fail(c, -EIO, "adsb_stream_mlat_rule: the head count is out of range");
+  if (nh == 0) return 0;
+  if ((e = (hipError_t)adsb_mlat_host::launch_groups_rule(st, carry, nc, nh, D.window, min_rx, n_streams, work, L))) return fail(c, -EIO, "adsb_stream_mlat_rule: the group kernels", e);
+  HIPCHK(c, hipMemcpyAsync(got, work + L.tot_groups, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const int ng = got[1], nm = got[2];
+  if (ng < 0 || ng > nc / adsb_mlat_host::kMinRxAided || nm < (long long)ng * min_rx || nm > nc) return fail(c, -EIO, "adsb_stream_mlat_rule: the group counts are out of range");
+  *n_fixes = ng; *n_members = nm;
+  if (ng > cap || nm > member_cap) return fail(c, -ENOSPC, "adsb_stream_mlat_rule: cap or member_cap is too small (*n_fixes, *n_members)");
+  if (ng == 0) return 0;
+  if ((e = (hipError_t)adsb_mlat_host::launch_solve_lm(st, carry, nc, ng, D.window, n_streams, rule->flags, want_alt ? rule->alt_weight : 0.0, work, L)))
+    return fail(c, -EIO, "adsb_stream_mlat_rule: k_mlat_solve_lm", e);
+  HIPCHK(c, hipMemcpyAsync(fixes, work + L.fixes, (size_t)ng * sizeof(adsb_mlat_fix), hipMemcpyDeviceToHost, st));
+  if (aux) HIPCHK(c, hipMemcpyAsync(aux, work + L.aux, (size_t)ng * sizeof(adsb_mlat_aux), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipMemcpyAsync(member_stream, work + L.member_stream, (size_t)nm * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipMemcpyAsync(member_ts, work + L.member_ts, (size_t)nm * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));

@@ -37,6 +37,8 @@ inline Layout layout(size_t nc, size_t n_streams) {
 int launch_heads(void* stream, const void* carry, int nc, double t_lo, double t_hi, double window, void* work, const Layout& L);
 // heads[nh] -> nrx[nh]; the groups with nrx >= min_rx in gsel / gfirst, their number and members in tot_groups[1], [2]
 int launch_groups(void* stream, const void* carry, int nc, int nh, double window, int min_rx, int n_streams, void* work, const Layout& L);
+// launch_groups' second half alone, for a caller that wrote nrx[nh] itself (adsb_mlat_rule.h): the compaction with min_w = min_rx
+int launch_select(void* stream, int nh, int min_rx, void* work, const Layout& L);
 // gsel[ng] -> fixes[ng], member_stream / member_ts
 int launch_solve(void* stream, const void* carry, int nc, int ng, double window, int n_streams, void* work, const Layout& L);
 

@@ -52,6 +52,13 @@ int launch_groups(void* stream, const void* carry, int nc, int nh, double window
   return (int)hipGetLastError();
 }
 
+int launch_select(void* stream, int nh, int min_rx, void* work, const Layout& L) {
+  if (nh <= 0) return 0;
+  compact((hipStream_t)stream, part<int>(work, L.nrx), part<int>(work, L.tot_heads), nh, min_rx, part<int>(work, L.cnt), part<int>(work, L.sum),
+          part<int>(work, L.tot_groups), 0, part<int>(work, L.gsel), part<int>(work, L.gfirst));
+  return (int)hipGetLastError();
+}
+
 int launch_solve(void* stream, const void* carry, int nc, int ng, double window, int n_streams, void* work, const Layout& L) {
   if (ng <= 0) return 0;
   hipLaunchKernelGGL(k_mlat_solve, dim3(cover(ng, kWaves)), dim3(kThreads), 0, (hipStream_t)stream, (const unsigned long long*)carry, nc,

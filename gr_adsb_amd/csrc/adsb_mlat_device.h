@@ -36,6 +36,9 @@
 // Every loop is bounded by the inputs: the binary searches by log2(nc), the scans and the walk by nc, the bit loop by 63,
 // the broadcasts by 64, the solver by kMaxIter.  LDS: k_mlat_heads kHeadsLdsBytes, k_mlat_count / _place kPlaceLdsBytes,
 // k_mlat_scan kScanLdsBytes, the others none.  Device code only; includes nothing.
+// With ADSB_MLAT_HELPERS_ONLY defined the kernels are left out and only the constants, Fix and the device functions remain:
+// adsb_mlat_rule.hip, the unit of adsb_stream_mlat_rule's kernels, walks and sums with them and must not define these
+// kernels a second time.
 #pragma once
 
 namespace adsb_mlat {
@@ -82,6 +85,7 @@ __device__ __forceinline__ int mlat_rank(const unsigned long long* c, int nc, do
   return lo;
 }
 
+#ifndef ADSB_MLAT_HELPERS_ONLY
 __global__ void __launch_bounds__(kWave) k_mlat_range(const unsigned long long* carry, int nc, double t_lo, double t_hi, int* range) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   const int lo = mlat_rank(carry, nc, t_lo), hi = mlat_rank(carry, nc, t_hi);
@@ -222,6 +226,7 @@ __global__ void __launch_bounds__(kThreads) k_mlat_place(const int* w, const int
     __syncthreads();
   }
 }
+#endif  // ADSB_MLAT_HELPERS_ONLY
 
 // One wavefront, one head h.  Behind it lane k < cand holds candidate k of the head's group: its timestamp and stream (lane 0
 // the head itself).  -> n_heard; *cand_out.  Called by all 64 lanes.
@@ -281,6 +286,7 @@ __device__ __forceinline__ bool mlat_used(int lane, int cand, int stream, const 
   return used;
 }
 
+#ifndef ADSB_MLAT_HELPERS_ONLY
 // heads[n]: n = span[1] - span[0] (k_mlat_scan's totals).  nrx[h] = the used hearings of head h's group.
 __global__ void __launch_bounds__(kThreads) k_mlat_groups(const unsigned long long* carry, int nc, const int* heads, const int* span, double window,
                                                           const double* rx, int n_streams, int* nrx) {
@@ -295,6 +301,7 @@ __global__ void __launch_bounds__(kThreads) k_mlat_groups(const unsigned long lo
     if (lane == 0) nrx[h] = k;
   }
 }
+#endif  // ADSB_MLAT_HELPERS_ONLY
 
 __device__ __forceinline__ double wave_sum(double v) {
   for (int d = kWave / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d);
@@ -314,6 +321,7 @@ __device__ __forceinline__ int mlat_remainder(unsigned long long a, unsigned lon
   return (int)v;
 }
 
+#ifndef ADSB_MLAT_HELPERS_ONLY
 // gsel[n] / gfirst[n]: n = span[1] - span[0]; heads[] as for k_mlat_groups.  fixes[n]; member_stream / member_ts at gfirst[g].
 __global__ void __launch_bounds__(kThreads) k_mlat_solve(const unsigned long long* carry, int nc, const int* heads, const int* gsel, const int* gfirst,
                                                          const int* span, double window, const double* rx, int n_streams, Fix* fixes,
@@ -392,5 +400,6 @@ __global__ void __launch_bounds__(kThreads) k_mlat_solve(const unsigned long lon
     }
   }
 }
+#endif  // ADSB_MLAT_HELPERS_ONLY
 
 }  // namespace adsb_mlat

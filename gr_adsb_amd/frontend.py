@@ -334,20 +334,37 @@ class Receivers:
             ids = [0]
         return self.ctx.merged_planes(ids, cutoff)
 
-    def mlat(self, t_lo=None, t_hi=None, min_rx=4):
+    def mlat(self, t_lo=None, t_hi=None, min_rx=4, solver="gauss-newton", restart=True, altitude=False, alt_weight=1.0):
         """receivers(dedup=..., positions=...): the replies of the carry (the last `horizon` seconds) that at least min_rx
         positioned receivers heard, each located from its arrival times (adsb_stream_mlat) -> (fixes, member_stream, member_ts):
         fixes has _native.MLAT_DTYPE's fields and latitude / longitude (degrees) / altitude_m, converted on the host; the
         hearings of fixes[j] are member_*[first : first + n_rx].  t_lo / t_hi: only replies whose first hearing has
-        t_lo <= ts < t_hi; None leaves that side open.  Read status (MLAT_OK), rms_m and n_rx before trusting a row."""
+        t_lo <= ts < t_hi; None leaves that side open.  Read status (MLAT_OK), rms_m and n_rx before trusting a row.
+        solver="damped": THE DAMPED RULE of include/adsb_hip.h (adsb_stream_mlat_rule) -- restart: a second run where the first
+        fails or ends below the receivers; altitude: the reply's own altitude as one more row of weight alt_weight (metres of
+        range per metre of height), which also allows min_rx=3 -- and fixes gains alt_ft, up_m, tries and aux_flags
+        (_native.MLAT_AUX_*).  The other arguments are read with solver="damped" only."""
         if not self.dedup:
             raise ValueError("mlat() needs receivers(dedup=...)")
-        fixes, ms, mt = self.ctx.stream_mlat(-np.inf if t_lo is None else t_lo, np.inf if t_hi is None else t_hi, min_rx)
-        out = np.zeros(len(fixes), dtype=np.dtype(_native.MLAT_DTYPE.descr + [("latitude", "<f8"), ("longitude", "<f8"), ("altitude_m", "<f8")]))
+        if solver not in ("gauss-newton", "damped"):
+            raise ValueError("solver is 'gauss-newton' or 'damped'")
+        lo, hi = -np.inf if t_lo is None else t_lo, np.inf if t_hi is None else t_hi
+        extra = []
+        if solver == "damped":
+            rule = _native.MLAT_RULE(_native.MLAT_SOLVER_LM, (_native.MLAT_RESTART if restart else 0) | (_native.MLAT_ALTITUDE if altitude else 0),
+                                     int(min_rx), 0, float(alt_weight))
+            fixes, aux, ms, mt = self.ctx.stream_mlat_rule(rule, lo, hi)
+            extra = [("alt_ft", "<i4", aux["alt_ft"]), ("up_m", "<f8", aux["up_m"]), ("tries", "<i4", aux["tries"]), ("aux_flags", "<u4", aux["flags"])]
+        else:
+            fixes, ms, mt = self.ctx.stream_mlat(lo, hi, min_rx)
+        out = np.zeros(len(fixes), dtype=np.dtype(_native.MLAT_DTYPE.descr + [("latitude", "<f8"), ("longitude", "<f8"), ("altitude_m", "<f8")] +
+                                                  [(name, kind) for name, kind, _ in extra]))
         for name in _native.MLAT_DTYPE.names:
             out[name] = fixes[name]
         for j, f in enumerate(fixes):
             out["latitude"][j], out["longitude"][j], out["altitude_m"][j] = _native.ecef_to_geodetic(f["x"], f["y"], f["z"])
+        for name, _, col in extra:
+            out[name] = col
         return out, ms, mt
 
     def table(self, timestamp, ids=None, cutoff=None):

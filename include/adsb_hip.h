@@ -661,7 +661,47 @@ int adsb_stream_dedup_stats(adsb_ctx* ctx, int64_t* duplicates, int64_t* carried
  * 2 Msps, 15 m at 20 Msps) and the double's ulp at the magnitude of start: 238 ns, about 71 m, for Unix-epoch starts.  MLAT
  * users should pass starts relative to a session epoch: below 2^23 s the ulp is under 1 ns (0.3 m).  The decoder's
  * last_seen clock works the same either way.  adsb_stream_mlat_stats reports C * ulp(hi), so a caller can see the limit.
- * Sub-sample arrival times, clock offsets between receivers and altitude-aided three-receiver fixes are not provided.
+ * Sub-sample arrival times, clock offsets between receivers, feeding fixes into the plane table and altitudes other than the
+ * reply's own barometric one (DF 18, GNSS height) are not provided.
+ * THE DAMPED RULE (adsb_stream_mlat_rule with ADSB_MLAT_SOLVER_LM; THE SOLVER above is ADSB_MLAT_SOLVER_GN and stays as it is).
+ * Grouping, candidates, USED, d_i, b, the residuals r_i, the rows of J and the arithmetic (double, no contraction) are
+ * unchanged.  c = the mean of the R_i, u = c / |c|, up(p) = (p - c) . u.
+ * A DAMPED RUN from a start p: b = |p - R_0|, lambda = 1e-3, S = sum r^2 over all rows.  At most 64 TRIALS.  A trial forms
+ * A = J^T J and g = J^T r at the iterate, multiplies A's diagonal by (1 + lambda), factors it by Cholesky in the order x, y,
+ * z, b -- a pivot that is not finite and positive ends the run with ADSB_MLAT_SINGULAR, the iterate as it was -- solves
+ * A delta = -g and sets tries += 1.  THE UNTESTED LAST STEP: if |delta_p| < 0.001 m and lambda <= 1e-3 the step is taken as it
+ * is -- the iterate moves, iters += 1 -- and the run ends with ADSB_MLAT_OK: at that damping the step is THE SOLVER's to a
+ * thousandth, and THE SOLVER stops there too; S' against S would be decided by rounding alone there (S sits at its floor), and
+ * a rule that asked would reject such steps at random and count them.  Otherwise the trial evaluates S' = sum r^2 at
+ * (p + delta_p, b + delta_b).  If S' is finite and S' <= S the step is taken: the iterate moves, S = S', iters += 1,
+ * lambda = max(lambda / 10, 1e-12), and |delta_p| < 0.001 m ends the run with ADSB_MLAT_OK.  Otherwise the iterate stays,
+ * lambda *= 10, and lambda > 1e12 ends the run with ADSB_MLAT_NO_CONVERGE.
+ * 64 trials without an end give ADSB_MLAT_NO_CONVERGE.  rms_m = sqrt(sum r_i^2 / n_rx) over the timing rows only, at the
+ * last iterate; t_tx as above.  iters counts the steps taken.
+ * THE RESTART (ADSB_MLAT_RESTART; unaided groups only).  The first run starts at c + 10000 u, as THE SOLVER does.  If it does
+ * not end ADSB_MLAT_OK a second run starts at c + 30000 u; if it ends ADSB_MLAT_OK with up(p) < 0 -- below the receivers: the
+ * mirror image -- a second run starts at the mirror p - (2 up(p)) u.  The second run's result replaces the first's (position,
+ * b, status, iters, lambda, up_m) iff it ends ADSB_MLAT_OK with up >= 0.  tries counts the trials of every run made.
+ * THE ALTITUDE ROW (ADSB_MLAT_ALTITUDE).  The head's payload gives alt_ft by the decoder's own rule: DF 0 / 4 / 16 / 20, bits
+ * 19..31 (13 bits: none if the field is 0, M (0x40) is set or Q (0x10) is clear; else the other 11 bits * 25 - 1000); DF 17
+ * with type code 9..18, bits 40..51 (12 bits: none if Q (0x10) is clear; else the other 11 bits * 25 - 1000); any other reply:
+ * none.  A group with an altitude is AIDED: every run has one more row, r_a = w * (h(p) - 0.3048 * alt_ft) with the Jacobian
+ * row (w * n(p), 0), w = alt_weight: metres of range per metre of height -- pressure altitude is not height above the
+ * ellipsoid, so the caller says how far to trust it.  The row adds w^2 n n^T to the position block of A (before the damping),
+ * w n r_a to g and r_a^2 to S and S'; A's b row and column are unchanged.  h and n come from ONE Bowring step on WGS-84 (a,
+ * f; e2 = f (2 - f), bp = a (1 - f), ep2 = e2 / (1 - e2)), written with sqrt and / only: q = sqrt(x^2 + y^2);
+ * t = (z a) / (q bp); cb = 1 / sqrt(1 + t^2), sb = t cb; T = (z + ep2 bp sb^3) / (q - e2 a cb^3); cp = 1 / sqrt(1 + T^2),
+ * sp = T cp; h = q cp + z sp - a sqrt(1 - e2 sp^2); n = (cp x / q, cp y / q, sp).  (On the polar axis q = 0, nothing is finite
+ * and the run ends ADSB_MLAT_SINGULAR.)  An aided group takes no restart.  A group of three used hearings is solved only when
+ * it is aided; otherwise it is not returned -- it is no row, and it counts neither in *n_fixes nor in *n_members.  Without
+ * ADSB_MLAT_ALTITUDE no payload is read for an altitude and alt_ft is -1.
+ * adsb_stream_mlat_rule is adsb_stream_mlat with the rule stated by the caller: the same range, rows, member lists, ordering
+ * and errors, and it changes no state either.  rule->solver ADSB_MLAT_SOLVER_GN with flags 0 and min_rx >= 4 returns byte for
+ * byte what adsb_stream_mlat(..., min_rx, ...) returns (aux rows, if asked for: alt_ft -1, everything else 0).  -EINVAL also
+ * for: rule NULL; a solver other than _GN / _LM; unknown flag bits; any flag with _GN; reserved != 0; min_rx < 4, or < 3
+ * with ADSB_MLAT_ALTITUDE; with ADSB_MLAT_ALTITUDE an alt_weight that is not finite and > 0.  aux (may be NULL): one row
+ * beside each fix -- up_m: up(p) of the returned position (negative: below the receivers); lambda: the kept run's last
+ * damping; alt_ft; tries; flags: ADSB_MLAT_AUX_AIDED, ADSB_MLAT_AUX_RESTARTED (a second run was made), ADSB_MLAT_AUX_SECOND_KEPT.
  * adsb_stream_set_ecef: the antenna of `stream` in WGS-84 ECEF metres.  Allowed at any time while streams are open; it is
  * not decoder state: adsb_stream_reset, adsb_streams_decoder_reset and adsb_reset keep it, adsb_streams_close forgets it.
  * -EINVAL for non-finite values, a bad stream, or a context without ADSB_FLAG_STREAM_DEDUP.  A stream without a position
@@ -693,6 +733,29 @@ typedef struct adsb_mlat_fix { /* 88 bytes */
 int adsb_stream_set_ecef(adsb_ctx* ctx, int32_t stream, double x, double y, double z);
 int adsb_stream_mlat(adsb_ctx* ctx, double t_lo, double t_hi, int32_t min_rx, adsb_mlat_fix* fixes, int32_t cap, int32_t* n_fixes,
                      int32_t* member_stream, double* member_ts, int32_t member_cap, int32_t* n_members);
+#define ADSB_MLAT_SOLVER_GN 0
+#define ADSB_MLAT_SOLVER_LM 1
+#define ADSB_MLAT_RESTART 1
+#define ADSB_MLAT_ALTITUDE 2
+#define ADSB_MLAT_AUX_AIDED 1u
+#define ADSB_MLAT_AUX_RESTARTED 2u
+#define ADSB_MLAT_AUX_SECOND_KEPT 4u
+typedef struct adsb_mlat_rule { /* 24 bytes */
+  int32_t solver;              /* ADSB_MLAT_SOLVER_* */
+  int32_t flags;               /* ADSB_MLAT_RESTART | ADSB_MLAT_ALTITUDE: ADSB_MLAT_SOLVER_LM only */
+  int32_t min_rx;              /* >= 4; >= 3 with ADSB_MLAT_ALTITUDE */
+  int32_t reserved;            /* 0 */
+  double alt_weight;           /* finite and > 0 with ADSB_MLAT_ALTITUDE; otherwise not read */
+} adsb_mlat_rule;
+typedef struct adsb_mlat_aux { /* 32 bytes */
+  double up_m, lambda;
+  int32_t alt_ft;              /* -1: none */
+  int32_t tries;
+  uint32_t flags;              /* ADSB_MLAT_AUX_* */
+  int32_t reserved;
+} adsb_mlat_aux;
+int adsb_stream_mlat_rule(adsb_ctx* ctx, double t_lo, double t_hi, const adsb_mlat_rule* rule, adsb_mlat_fix* fixes, adsb_mlat_aux* aux,
+                          int32_t cap, int32_t* n_fixes, int32_t* member_stream, double* member_ts, int32_t member_cap, int32_t* n_members);
 /* positioned: streams with a position; ts_ulp_m: ADSB_MLAT_C * ulp(hi), what the double's spacing at the carry's latest
  * timestamp is worth in metres.  Either pointer may be NULL.  -EINVAL without the flag or without open streams. */
 int adsb_stream_mlat_stats(adsb_ctx* ctx, int32_t* positioned, double* ts_ulp_m);
