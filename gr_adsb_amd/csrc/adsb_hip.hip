@@ -335,7 +335,7 @@ struct FleetDec {
   } dd;
   // adsb_stream_mlat (adsb_mlat.hip): the receivers' ECEF positions (NaN: none set) -- not decoder state: only fleet_open and
   // fleet_close touch them -- and one call's work buffer (adsb_mlat.h: Layout; adsb_stream_mlat_rule's damped path carves the
-  // same buffer by adsb_mlat_rule.h: RuleLayout) with the pinned memory its counts come down to
+  // same buffer by adsb_mlat_rule.h: layout_rule) with the pinned memory its counts come down to
   std::vector<double> rx;
   DevBuf d_mlat;
   PinnedBuf h_mlat;
@@ -2543,17 +2543,31 @@ int adsb_stream_reset(adsb_ctx* c, int32_t stream) {
   return 0;               // (a shared decoder is nobody's: adsb_streams_decoder_reset)
 }
 
+// 0 when the context was created with `flag` and has open streams, else -EINVAL with the entry point's (`api`) message
+static int need_streams(adsb_ctx* c, uint32_t flag, const char* flag_name, const char* api) {
+  char msg[160];
+  if (!(c->flags & flag)) {
+    snprintf(msg, sizeof(msg), "context created without %s", flag_name);
+    return fail(c, -EINVAL, msg);
+  }
+  if (!c->fd.open) {
+    snprintf(msg, sizeof(msg), "%s: no streams (adsb_streams_open first)", api);
+    return fail(c, -EINVAL, msg);
+  }
+  return 0;
+}
+static int need_shared_streams(adsb_ctx* c, const char* api) { return need_streams(c, ADSB_FLAG_STREAM_DECODE_SHARED, "ADSB_FLAG_STREAM_DECODE_SHARED", api); }
+static int need_dedup_streams(adsb_ctx* c, const char* api) { return need_streams(c, ADSB_FLAG_STREAM_DEDUP, "ADSB_FLAG_STREAM_DEDUP", api); }
+
 int adsb_streams_decoder_reset(adsb_ctx* c) {
   if (!c) return -EINVAL;
-  if (!(c->flags & ADSB_FLAG_STREAM_DECODE_SHARED)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE_SHARED");
-  if (!c->fd.open) return fail(c, -EINVAL, "adsb_streams_decoder_reset: no streams (adsb_streams_open first)");
+  if (const int rc = need_shared_streams(c, "adsb_streams_decoder_reset")) return rc;
   return fleet_reset_stream(c, 0);
 }
 
 int adsb_stream_last_order(adsb_ctx* c, const int32_t** order, int32_t* n) {
   if (!c) return -EINVAL;
-  if (!(c->flags & ADSB_FLAG_STREAM_DECODE_SHARED)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DECODE_SHARED");
-  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_last_order: no streams (adsb_streams_open first)");
+  if (const int rc = need_shared_streams(c, "adsb_stream_last_order")) return rc;
   if (order) *order = c->fd.n_rows > 0 ? (const int32_t*)c->fd.h_order.p : nullptr;
   if (n) *n = c->fd.n_rows;
   return 0;
@@ -2561,8 +2575,7 @@ int adsb_stream_last_order(adsb_ctx* c, const int32_t** order, int32_t* n) {
 
 int adsb_streams_set_dedup(adsb_ctx* c, double window_s, double horizon_s) {
   if (!c) return -EINVAL;
-  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
-  if (!c->fd.open) return fail(c, -EINVAL, "adsb_streams_set_dedup: no streams (adsb_streams_open first)");
+  if (const int rc = need_dedup_streams(c, "adsb_streams_set_dedup")) return rc;
   if (!(window_s >= 0) || !(horizon_s >= window_s)) return fail(c, -EINVAL, "adsb_streams_set_dedup: 0 <= window_s <= horizon_s, no NaN");
   if (c->fd.dd.delivered) return fail(c, -EINVAL, "adsb_streams_set_dedup: a call has been delivered since the decoder was fresh");
   c->fd.dd.window = window_s; c->fd.dd.horizon = horizon_s;
@@ -2571,8 +2584,7 @@ int adsb_streams_set_dedup(adsb_ctx* c, double window_s, double horizon_s) {
 
 int adsb_stream_last_duplicates(adsb_ctx* c, const int32_t** dup, int32_t* n) {
   if (!c) return -EINVAL;
-  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
-  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_last_duplicates: no streams (adsb_streams_open first)");
+  if (const int rc = need_dedup_streams(c, "adsb_stream_last_duplicates")) return rc;
   if (dup) *dup = c->fd.n_rows > 0 ? (const int32_t*)c->fd.dd.h_dup.p : nullptr;
   if (n) *n = c->fd.n_rows;
   return 0;
@@ -2580,8 +2592,7 @@ int adsb_stream_last_duplicates(adsb_ctx* c, const int32_t** dup, int32_t* n) {
 
 int adsb_stream_dedup_stats(adsb_ctx* c, int64_t* duplicates, int64_t* carried, double* hi) {
   if (!c) return -EINVAL;
-  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
-  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_dedup_stats: no streams (adsb_streams_open first)");
+  if (const int rc = need_dedup_streams(c, "adsb_stream_dedup_stats")) return rc;
   if (duplicates) *duplicates = c->fd.dd.duplicates;
   if (carried) *carried = c->fd.dd.cnt;
   if (hi) *hi = c->fd.dd.hi;
@@ -2590,8 +2601,7 @@ int adsb_stream_dedup_stats(adsb_ctx* c, int64_t* duplicates, int64_t* carried, 
 
 int adsb_stream_set_ecef(adsb_ctx* c, int32_t stream, double x, double y, double z) {
   if (!c) return -EINVAL;
-  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
-  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_set_ecef: no streams (adsb_streams_open first)");
+  if (const int rc = need_dedup_streams(c, "adsb_stream_set_ecef")) return rc;
   if (stream < 0 || (size_t)stream >= c->fd.rx.size() / 3) return fail(c, -EINVAL, "adsb_stream_set_ecef: no such stream");
   if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z)) return fail(c, -EINVAL, "adsb_stream_set_ecef: a position is three finite numbers");
   double* const r = &c->fd.rx[3 * (size_t)stream];
@@ -2601,8 +2611,7 @@ int adsb_stream_set_ecef(adsb_ctx* c, int32_t stream, double x, double y, double
 
 int adsb_stream_mlat_stats(adsb_ctx* c, int32_t* positioned, double* ts_ulp_m) {
   if (!c) return -EINVAL;
-  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
-  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_mlat_stats: no streams (adsb_streams_open first)");
+  if (const int rc = need_dedup_streams(c, "adsb_stream_mlat_stats")) return rc;
   if (positioned) {
     int32_t k = 0;
     for (size_t s = 0; s < c->fd.rx.size(); s += 3) k += !std::isnan(c->fd.rx[s]);
@@ -2615,17 +2624,27 @@ int adsb_stream_mlat_stats(adsb_ctx* c, int32_t* positioned, double* ts_ulp_m) {
   return 0;
 }
 
-// adsb_mlat.hip's three phases on the carry as it stands; the head count, then the group and member counts, come down
-// between them (as fleet_step's h_cnt).  The work buffer is sized from the carry's length before the first launch.
-int adsb_stream_mlat(adsb_ctx* c, double t_lo, double t_hi, int32_t min_rx, adsb_mlat_fix* fixes, int32_t cap, int32_t* n_fixes,
-                     int32_t* member_stream, double* member_ts, int32_t member_cap, int32_t* n_members) {
-  if (!c) return -EINVAL;
-  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
-  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_mlat: no streams (adsb_streams_open first)");
-  if (min_rx < adsb_mlat_host::kMinRx) return fail(c, -EINVAL, "adsb_stream_mlat: min_rx < 4 (three-receiver fixes are not provided)");
-  if (std::isnan(t_lo) || std::isnan(t_hi)) return fail(c, -EINVAL, "adsb_stream_mlat: a bound is NaN");
+static_assert(sizeof(adsb_mlat_aux) == adsb_mlat_host::kAuxBytes && sizeof(adsb_mlat_rule) == 24 && offsetof(adsb_mlat_aux, alt_ft) == 16 &&
+              offsetof(adsb_mlat_aux, flags) == 24, "adsb_mlat_rule.hip writes adsb_mlat_aux rows");
+
+// One multilateration call, behind the argument table of the entry point `api` (whose name its messages carry): the three
+// phases on the carry as it stands; the head count, then the group and member counts, come down between them (as
+// fleet_step's h_cnt); -ENOSPC is decided before the solve.  The work buffer is sized from the carry's length before the first
+// launch.  rule null: adsb_mlat.hip's groups and Gauss-Newton kernels on layout().  rule given: adsb_mlat_rule.hip's groups and
+// damped solve kernels on layout_rule(), the aux rows (aux may be null) beside the fixes.  min_group: the fewest used
+// hearings a selected group can have, which bounds the group count.
+static int mlat_call(adsb_ctx* c, const char* api, double t_lo, double t_hi, int32_t min_rx, int min_group, const adsb_mlat_rule* rule,
+                     adsb_mlat_fix* fixes, adsb_mlat_aux* aux, int32_t cap, int32_t* n_fixes, int32_t* member_stream, double* member_ts,
+                     int32_t member_cap, int32_t* n_members) {
+  namespace mh = adsb_mlat_host;
+  const auto refuse = [&](int code, const char* what, hipError_t he = hipSuccess) {
+    char msg[192];
+    snprintf(msg, sizeof(msg), "%s: %s", api, what);
+    return fail(c, code, msg, he);
+  };
+  if (std::isnan(t_lo) || std::isnan(t_hi)) return refuse(-EINVAL, "a bound is NaN");
   if (!n_fixes || !n_members || cap < 0 || member_cap < 0 || (cap > 0 && !fixes) || (member_cap > 0 && (!member_stream || !member_ts)))
-    return fail(c, -EINVAL, "adsb_stream_mlat: n_fixes / n_members, or the arrays for cap / member_cap > 0, missing");
+    return refuse(-EINVAL, "n_fixes / n_members, or the arrays for cap / member_cap > 0, missing");
   int rc;
   if ((rc = require_idle(c, kCallPending))) return rc;
   FleetDec& F = c->fd;
@@ -2635,7 +2654,7 @@ int adsb_stream_mlat(adsb_ctx* c, double t_lo, double t_hi, int32_t min_rx, adsb
   if (nc == 0) return 0;
   HIPCHK(c, hipSetDevice(c->device));
   const hipStream_t st = c->stream;
-  const adsb_mlat_host::Layout L = adsb_mlat_host::layout((size_t)nc, (size_t)n_streams);
+  const mh::Layout L = rule ? mh::layout_rule((size_t)nc, (size_t)n_streams) : mh::layout((size_t)nc, (size_t)n_streams);
   const size_t rx_bytes = F.rx.size() * sizeof(double);
   if ((rc = ensure(c, F.d_mlat, L.bytes)) || (rc = ensure_pinned(c, F.h_mlat, rx_bytes + 64))) return rc;
   char* const work = (char*)F.d_mlat.p;
@@ -2644,38 +2663,50 @@ int adsb_stream_mlat(adsb_ctx* c, double t_lo, double t_hi, int32_t min_rx, adsb
   HIPCHK(c, hipMemcpyAsync(work + L.rx, F.h_mlat.p, rx_bytes, hipMemcpyHostToDevice, st));
   const char* const carry = (const char*)D.d_carry[D.cur].p + (size_t)D.off * adsb_dedup_host::kEntBytes;
   hipError_t e;
-  if ((e = (hipError_t)adsb_mlat_host::launch_heads(st, carry, nc, t_lo, t_hi, D.window, work, L))) return fail(c, -EIO, "adsb_stream_mlat: the head kernels", e);
+  if ((e = (hipError_t)mh::launch_heads(st, carry, nc, t_lo, t_hi, D.window, work, L))) return refuse(-EIO, "the head kernels", e);
   HIPCHK(c, hipMemcpyAsync(got, work + L.tot_heads, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   const int nh = got[1];
-  if (nh < 0 || nh > nc) return fail(c, -EIO, "adsb_stream_mlat: the head count is out of range");
+  if (nh < 0 || nh > nc) return refuse(-EIO, "the head count is out of range");
   if (nh == 0) return 0;
-  if ((e = (hipError_t)adsb_mlat_host::launch_groups(st, carry, nc, nh, D.window, min_rx, n_streams, work, L))) return fail(c, -EIO, "adsb_stream_mlat: the group kernels", e);
+  if ((e = (hipError_t)(rule ? mh::launch_groups_rule : mh::launch_groups)(st, carry, nc, nh, D.window, min_rx, n_streams, work, L)))
+    return refuse(-EIO, "the group kernels", e);
   HIPCHK(c, hipMemcpyAsync(got, work + L.tot_groups, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   const int ng = got[1], nm = got[2];
-  if (ng < 0 || ng > nc / adsb_mlat_host::kMinRx || nm < (long long)ng * min_rx || nm > nc) return fail(c, -EIO, "adsb_stream_mlat: the group counts are out of range");
+  if (ng < 0 || ng > nc / min_group || nm < (long long)ng * min_rx || nm > nc) return refuse(-EIO, "the group counts are out of range");
   *n_fixes = ng; *n_members = nm;
-  if (ng > cap || nm > member_cap) return fail(c, -ENOSPC, "adsb_stream_mlat: cap or member_cap is too small (*n_fixes, *n_members)");
+  if (ng > cap || nm > member_cap) return refuse(-ENOSPC, "cap or member_cap is too small (*n_fixes, *n_members)");
   if (ng == 0) return 0;
-  if ((e = (hipError_t)adsb_mlat_host::launch_solve(st, carry, nc, ng, D.window, n_streams, work, L))) return fail(c, -EIO, "adsb_stream_mlat: k_mlat_solve", e);
+  if (rule) {
+    const double alt_weight = (rule->flags & ADSB_MLAT_ALTITUDE) ? rule->alt_weight : 0.0;
+    if ((e = (hipError_t)mh::launch_solve_lm(st, carry, nc, ng, D.window, n_streams, rule->flags, alt_weight, work, L))) return refuse(-EIO, "k_mlat_solve_lm", e);
+  } else if ((e = (hipError_t)mh::launch_solve(st, carry, nc, ng, D.window, n_streams, work, L))) {
+    return refuse(-EIO, "k_mlat_solve", e);
+  }
   HIPCHK(c, hipMemcpyAsync(fixes, work + L.fixes, (size_t)ng * sizeof(adsb_mlat_fix), hipMemcpyDeviceToHost, st));
+  if (rule && aux) HIPCHK(c, hipMemcpyAsync(aux, work + L.aux, (size_t)ng * sizeof(adsb_mlat_aux), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipMemcpyAsync(member_stream, work + L.member_stream, (size_t)nm * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipMemcpyAsync(member_ts, work + L.member_ts, (size_t)nm * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   return 0;
 }
 
-static_assert(sizeof(adsb_mlat_aux) == adsb_mlat_host::kAuxBytes && sizeof(adsb_mlat_rule) == 24 && offsetof(adsb_mlat_aux, alt_ft) == 16 &&
-              offsetof(adsb_mlat_aux, flags) == 24, "adsb_mlat_rule.hip writes adsb_mlat_aux rows");
+int adsb_stream_mlat(adsb_ctx* c, double t_lo, double t_hi, int32_t min_rx, adsb_mlat_fix* fixes, int32_t cap, int32_t* n_fixes,
+                     int32_t* member_stream, double* member_ts, int32_t member_cap, int32_t* n_members) {
+  if (!c) return -EINVAL;
+  if (const int rc = need_dedup_streams(c, "adsb_stream_mlat")) return rc;
+  if (min_rx < adsb_mlat_host::kMinRx) return fail(c, -EINVAL, "adsb_stream_mlat: min_rx < 4 (three-receiver fixes are not provided)");
+  return mlat_call(c, "adsb_stream_mlat", t_lo, t_hi, min_rx, adsb_mlat_host::kMinRx, nullptr, fixes, nullptr, cap, n_fixes, member_stream, member_ts,
+                   member_cap, n_members);
+}
 
-// adsb_stream_mlat with the rule stated by the caller.  _GN is adsb_stream_mlat itself; _LM is its path with
-// adsb_mlat_rule.hip's groups and solve kernels on a work buffer carved by layout_rule, and the aux rows beside the fixes.
+// adsb_stream_mlat with the rule stated by the caller.  _GN is adsb_stream_mlat itself, with empty aux rows; _LM is
+// mlat_call with the rule.
 int adsb_stream_mlat_rule(adsb_ctx* c, double t_lo, double t_hi, const adsb_mlat_rule* rule, adsb_mlat_fix* fixes, adsb_mlat_aux* aux, int32_t cap,
                           int32_t* n_fixes, int32_t* member_stream, double* member_ts, int32_t member_cap, int32_t* n_members) {
   if (!c) return -EINVAL;
-  if (!(c->flags & ADSB_FLAG_STREAM_DEDUP)) return fail(c, -EINVAL, "context created without ADSB_FLAG_STREAM_DEDUP");
-  if (!c->fd.open) return fail(c, -EINVAL, "adsb_stream_mlat_rule: no streams (adsb_streams_open first)");
+  if (const int rc = need_dedup_streams(c, "adsb_stream_mlat_rule")) return rc;
   if (!rule) return fail(c, -EINVAL, "adsb_stream_mlat_rule: rule is NULL");
   if (rule->solver != ADSB_MLAT_SOLVER_GN && rule->solver != ADSB_MLAT_SOLVER_LM) return fail(c, -EINVAL, "adsb_stream_mlat_rule: unknown solver");
   if (rule->flags & ~(ADSB_MLAT_RESTART | ADSB_MLAT_ALTITUDE)) return fail(c, -EINVAL, "adsb_stream_mlat_rule: unknown flags");
@@ -2692,49 +2723,8 @@ int adsb_stream_mlat_rule(adsb_ctx* c, double t_lo, double t_hi, const adsb_mlat
       for (int32_t k = 0; k < *n_fixes; ++k) { memset(&aux[k], 0, sizeof aux[k]); aux[k].alt_ft = -1; }
     return rc;
   }
-  if (std::isnan(t_lo) || std::isnan(t_hi)) return fail(c, -EINVAL, "adsb_stream_mlat_rule: a bound is NaN");
-  if (!n_fixes || !n_members || cap < 0 || member_cap < 0 || (cap > 0 && !fixes) || (member_cap > 0 && (!member_stream || !member_ts)))
-    return fail(c, -EINVAL, "adsb_stream_mlat_rule: n_fixes / n_members, or the arrays for cap / member_cap > 0, missing");
-  int rc;
-  if ((rc = require_idle(c, kCallPending))) return rc;
-  FleetDec& F = c->fd;
-  const FleetDec::Dedup& D = F.dd;
-  *n_fixes = 0; *n_members = 0;
-  const int nc = D.cnt, n_streams = (int)(F.rx.size() / 3), min_rx = rule->min_rx;
-  if (nc == 0) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
-  const hipStream_t st = c->stream;
-  const adsb_mlat_host::RuleLayout L = adsb_mlat_host::layout_rule((size_t)nc, (size_t)n_streams);
-  const size_t rx_bytes = F.rx.size() * sizeof(double);
-  if ((rc = ensure(c, F.d_mlat, L.bytes)) || (rc = ensure_pinned(c, F.h_mlat, rx_bytes + 64))) return rc;
-  char* const work = (char*)F.d_mlat.p;
-  int* const got = (int*)((char*)F.h_mlat.p + rx_bytes);
-  memcpy(F.h_mlat.p, F.rx.data(), rx_bytes);
-  HIPCHK(c, hipMemcpyAsync(work + L.rx, F.h_mlat.p, rx_bytes, hipMemcpyHostToDevice, st));
-  const char* const carry = (const char*)D.d_carry[D.cur].p + (size_t)D.off * adsb_dedup_host::kEntBytes;
-  hipError_t e;
-  if ((e = (hipError_t)adsb_mlat_host::launch_heads(st, carry, nc, t_lo, t_hi, D.window, work, L))) return fail(c, -EIO, "adsb_stream_mlat_rule: the head kernels", e);
-  HIPCHK(c, hipMemcpyAsync(got, work + L.tot_heads, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  const int nh = got[1];
-  if (nh < 0 || nh > nc) return fail(c, -EIO, "adsb_stream_mlat_rule: the head count is out of range");
-  if (nh == 0) return 0;
-  if ((e = (hipError_t)adsb_mlat_host::launch_groups_rule(st, carry, nc, nh, D.window, min_rx, n_streams, work, L))) return fail(c, -EIO, "adsb_stream_mlat_rule: the group kernels", e);
-  HIPCHK(c, hipMemcpyAsync(got, work + L.tot_groups, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  const int ng = got[1], nm = got[2];
-  if (ng < 0 || ng > nc / adsb_mlat_host::kMinRxAided || nm < (long long)ng * min_rx || nm > nc) return fail(c, -EIO, "adsb_stream_mlat_rule: the group counts are out of range");
-  *n_fixes = ng; *n_members = nm;
-  if (ng > cap || nm > member_cap) return fail(c, -ENOSPC, "adsb_stream_mlat_rule: cap or member_cap is too small (*n_fixes, *n_members)");
-  if (ng == 0) return 0;
-  if ((e = (hipError_t)adsb_mlat_host::launch_solve_lm(st, carry, nc, ng, D.window, n_streams, rule->flags, want_alt ? rule->alt_weight : 0.0, work, L)))
-    return fail(c, -EIO, "adsb_stream_mlat_rule: k_mlat_solve_lm", e);
-  HIPCHK(c, hipMemcpyAsync(fixes, work + L.fixes, (size_t)ng * sizeof(adsb_mlat_fix), hipMemcpyDeviceToHost, st));
-  if (aux) HIPCHK(c, hipMemcpyAsync(aux, work + L.aux, (size_t)ng * sizeof(adsb_mlat_aux), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(member_stream, work + L.member_stream, (size_t)nm * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(member_ts, work + L.member_ts, (size_t)nm * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return 0;
+  return mlat_call(c, "adsb_stream_mlat_rule", t_lo, t_hi, rule->min_rx, adsb_mlat_host::kMinRxAided, rule, fixes, aux, cap, n_fixes, member_stream,
+                   member_ts, member_cap, n_members);
 }
 
 int adsb_streams_set_decoder(adsb_ctx* c, int32_t msg_filter) {

@@ -13,13 +13,6 @@ using namespace adsb_mlat;
 static_assert(kEntBytes == kEntWords * 8 && kFixBytes == sizeof(Fix) && kChunk == kThreads && kMinRx == 4, "the header's sizes are the device code's");
 
 namespace {
-// grid-stride kernels: enough workgroups to cover `work` units of `per` each, a few per compute unit at the most
-unsigned cover(long long work, int per) {
-  const long long g = (work + per - 1) / per;
-  return (unsigned)(g < 1 ? 1 : g > 2048 ? 2048 : g);
-}
-template <class T> T* part(void* work, size_t off) { return (T*)((char*)work + off); }
-
 // w[n] (n = span[1] - span[0] <= n_max) -> idx / first of the values >= min_w; tot = {0, count, sum, 0}
 void compact(hipStream_t st, const int* w, const int* span, int n_max, int min_w, int* cnt, int* sum, int* tot, int add_lo, int* idx, int* first) {
   const unsigned g = cover(n_max, kThreads);
@@ -43,13 +36,11 @@ int launch_heads(void* stream, const void* carry, int nc, double t_lo, double t_
 
 int launch_groups(void* stream, const void* carry, int nc, int nh, double window, int min_rx, int n_streams, void* work, const Layout& L) {
   if (nh <= 0) return 0;
-  const hipStream_t st = (hipStream_t)stream;
-  const int* const span = part<int>(work, L.tot_heads);
-  hipLaunchKernelGGL(k_mlat_groups, dim3(cover(nh, kWaves)), dim3(kThreads), 0, st, (const unsigned long long*)carry, nc,
-                     (const int*)part<int>(work, L.heads), span, window, (const double*)part<double>(work, L.rx), n_streams, part<int>(work, L.nrx));
-  compact(st, part<int>(work, L.nrx), span, nh, min_rx, part<int>(work, L.cnt), part<int>(work, L.sum), part<int>(work, L.tot_groups), 0,
-          part<int>(work, L.gsel), part<int>(work, L.gfirst));
-  return (int)hipGetLastError();
+  hipLaunchKernelGGL(k_mlat_groups, dim3(cover(nh, kWaves)), dim3(kThreads), 0, (hipStream_t)stream, (const unsigned long long*)carry, nc,
+                     (const int*)part<int>(work, L.heads), (const int*)part<int>(work, L.tot_heads), window,
+                     (const double*)part<double>(work, L.rx), n_streams, part<int>(work, L.nrx));
+  const int e = (int)hipGetLastError();
+  return e ? e : launch_select(stream, nh, min_rx, work, L);
 }
 
 int launch_select(void* stream, int nh, int min_rx, void* work, const Layout& L) {

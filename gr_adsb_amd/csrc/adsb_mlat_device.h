@@ -36,9 +36,9 @@
 // Every loop is bounded by the inputs: the binary searches by log2(nc), the scans and the walk by nc, the bit loop by 63,
 // the broadcasts by 64, the solver by kMaxIter.  LDS: k_mlat_heads kHeadsLdsBytes, k_mlat_count / _place kPlaceLdsBytes,
 // k_mlat_scan kScanLdsBytes, the others none.  Device code only; includes nothing.
-// With ADSB_MLAT_HELPERS_ONLY defined the kernels are left out and only the constants, Fix and the device functions remain:
-// adsb_mlat_rule.hip, the unit of adsb_stream_mlat_rule's kernels, walks and sums with them and must not define these
-// kernels a second time.
+// The device functions stand in front and the seven kernels behind them under one guard: with ADSB_MLAT_HELPERS_ONLY defined
+// the kernels are left out.  adsb_mlat_rule.hip, the unit of adsb_stream_mlat_rule's kernels, walks, factors and names its
+// fixes' addresses with the same functions and must not define these kernels a second time.
 #pragma once
 
 namespace adsb_mlat {
@@ -83,6 +83,158 @@ __device__ __forceinline__ int mlat_rank(const unsigned long long* c, int nc, do
     if (time_key(ent_ts(c, mid)) < key) lo = mid + 1; else hi = mid;
   }
   return lo;
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+  for (int d = kWave / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+// One wavefront, one head h.  Behind it lane k < cand holds candidate k of the head's group: its timestamp and stream (lane 0
+// the head itself).  -> n_heard; *cand_out.  Called by all 64 lanes.
+__device__ __forceinline__ int mlat_walk(const unsigned long long* carry, int nc, int h, double window, int lane, double* ts_out, int* stream_out,
+                                         int* cand_out) {
+  const unsigned long long* e = carry + (long long)h * kEntWords;
+  const double ts_h = __longlong_as_double((long long)e[0]);
+  const unsigned long long a = e[1], b = e[2], m = e[3];
+  double ts_l = ts_h;
+  int stream_l = (int)((m >> 32) & 0xFFFFFFull);
+  int cand = 1, n_heard = 1;
+  for (int base = h + 1; base < nc; base += kWave) {
+    const int i = base + lane;
+    bool in = false, match = false;
+    double t = 0;
+    int s = 0;
+    if (i < nc) {
+      const unsigned long long* q = carry + (long long)i * kEntWords;
+      t = __longlong_as_double((long long)q[0]);
+      in = in_window(t, ts_h, window);
+      const unsigned long long mq = q[3];
+      s = (int)((mq >> 32) & 0xFFFFFFull);
+      match = in && meta_equal(m, mq) && q[1] == a && q[2] == b;
+    }
+    const unsigned long long inside = __ballot(in), mask = __ballot(match);
+    const int hits = __popcll(mask);
+    n_heard += hits;
+    if (hits != 0 && cand < kMaxCand) {               // (wave-uniform)
+      const int k = lane - cand;
+      const bool want = k >= 0 && k < hits;
+      unsigned long long mm = mask;
+      if (want)
+        for (int j = 0; j < k; ++j) mm &= mm - 1ull;  // the k-th set bit: at most 63 rounds
+      const int src = want ? __builtin_ctzll(mm) : lane;
+      const double t_src = __shfl(t, src);
+      const int s_src = __shfl(s, src);
+      if (want) { ts_l = t_src; stream_l = s_src; }
+      cand = cand + hits < kMaxCand ? cand + hits : kMaxCand;
+    }
+    if (inside != ~0ull) break;                       // an entry outside the window, or the carry's end: the list is sorted
+  }
+  *ts_out = ts_l; *stream_out = stream_l; *cand_out = cand;
+  return n_heard;
+}
+
+// Of the candidates, lane by lane: used iff the first of its stream and the stream has a position (rx[3 s] is not NaN).
+__device__ __forceinline__ bool mlat_used(int lane, int cand, int stream, const double* rx, int n_streams) {
+  bool used = lane < cand;
+  for (int j = 0; j < cand; ++j) {                    // at most 64 broadcasts
+    const int sj = __shfl(stream, j);
+    if (j < lane && sj == stream) used = false;
+  }
+  if (used) {
+    if ((unsigned)stream >= (unsigned)n_streams) used = false;
+    else { const double x = rx[3ll * stream]; used = x == x; }
+  }
+  return used;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int d = kWave / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+__device__ __forceinline__ bool pivot_ok(double d) { return d > 0.0 && d <= 1.7976931348623157e308; }
+
+// The remainder of the reply's first nbits bits modulo x^24 + 0xFFF409: the address under address/parity.
+__device__ __forceinline__ int mlat_remainder(unsigned long long a, unsigned long long b, int nbits) {
+  unsigned v = 0;
+  for (int i = 0; i < nbits; ++i) {
+    const int byte = i >> 3;
+    const unsigned by = (unsigned)((byte < 8 ? a >> (8 * byte) : b >> (8 * (byte - 8))) & 0xFFull);
+    v = (v << 1) | ((by >> (7 - (i & 7))) & 1u);
+    if (v & 0x1000000u) v ^= 0x1FFF409u;
+  }
+  return (int)v;
+}
+
+// ---- What k_mlat_solve and adsb_mlat_rule_device.h's k_mlat_solve_lm share.  The functions take and return values; every
+// floating-point expression keeps its operand order (the tests compare bits).
+
+// The used hearings of the group of the head at carry[at]: what both groups kernels count.
+__device__ __forceinline__ int mlat_group_used(const unsigned long long* carry, int nc, int at, double window, int lane, const double* rx,
+                                               int n_streams) {
+  double ts; int stream, cand;
+  (void)mlat_walk(carry, nc, at, window, lane, &ts, &stream, &cand);
+  return __popcll(__ballot(mlat_used(lane, cand, stream, rx, n_streams)));
+}
+
+// One lane's hearing in a selected group: whether its candidate is used, that receiver's position (0 if not) and the range
+// difference d = C (ts - ts_head).
+struct Hearing {
+  bool used;
+  double rxx, rxy, rxz, d;
+};
+
+// The hearing's row of the Jacobian and its residual at the iterate (p, b): the unit vector from the receiver to p and
+// rho - d - b; zeros for a lane that is not used.
+struct Row { double ux, uy, uz, r; };
+__device__ __forceinline__ Row mlat_row(const Hearing H, double px, double py, double pz, double bb) {
+  const double dx = px - H.rxx, dy = py - H.rxy, dz = pz - H.rxz;
+  const double rho = __builtin_sqrt(dx * dx + dy * dy + dz * dz);
+  Row j;
+  j.ux = H.used ? dx / rho : 0.0; j.uy = H.used ? dy / rho : 0.0; j.uz = H.used ? dz / rho : 0.0;
+  j.r = H.used ? rho - H.d - bb : 0.0;
+  return j;
+}
+
+// The Cholesky factor of the symmetric 4 x 4 (a) and the step e that solves a e = -g; ok is false at the first pivot that is
+// not positive and finite.
+struct Step { double e1, e2, e3, e4; bool ok; };
+__device__ __forceinline__ Step mlat_cholesky(double a11, double a12, double a13, double a14, double a22, double a23, double a24, double a33, double a34,
+                                              double a44, double g1, double g2, double g3, double g4) {
+  Step s = {0.0, 0.0, 0.0, 0.0, false};
+  if (!pivot_ok(a11)) return s;
+  const double l11 = __builtin_sqrt(a11), l21 = a12 / l11, l31 = a13 / l11, l41 = a14 / l11;
+  const double d2 = a22 - l21 * l21;
+  if (!pivot_ok(d2)) return s;
+  const double l22 = __builtin_sqrt(d2), l32 = (a23 - l31 * l21) / l22, l42 = (a24 - l41 * l21) / l22;
+  const double d3 = a33 - l31 * l31 - l32 * l32;
+  if (!pivot_ok(d3)) return s;
+  const double l33 = __builtin_sqrt(d3), l43 = (a34 - l41 * l31 - l42 * l32) / l33;
+  const double d4 = a44 - l41 * l41 - l42 * l42 - l43 * l43;
+  if (!pivot_ok(d4)) return s;
+  const double l44 = __builtin_sqrt(d4);
+  const double y1 = -g1 / l11, y2 = (-g2 - l21 * y1) / l22, y3 = (-g3 - l31 * y1 - l32 * y2) / l33;
+  const double y4 = (-g4 - l41 * y1 - l42 * y2 - l43 * y3) / l44;
+  s.e4 = y4 / l44; s.e3 = (y3 - l43 * s.e4) / l33; s.e2 = (y2 - l32 * s.e3 - l42 * s.e4) / l22;
+  s.e1 = (y1 - l21 * s.e2 - l31 * s.e3 - l41 * s.e4) / l11;
+  s.ok = true;
+  return s;
+}
+
+// This lane's range residual at (p, b), 0 for a lane that is not used; and the rms of the group's residuals.
+__device__ __forceinline__ double mlat_residual(const Hearing H, double px, double py, double pz, double bb) {
+  const double fx = px - H.rxx, fy = py - H.rxy, fz = pz - H.rxz;
+  return H.used ? __builtin_sqrt(fx * fx + fy * fy + fz * fz) - H.d - bb : 0.0;
+}
+__device__ __forceinline__ double mlat_rms(double rr, double nn) { return __builtin_sqrt(wave_sum(rr * rr) / nn); }
+
+// The address a fix row states: the AA field of DF 11 / 17 / 18, the remainder under address/parity, else -1.  a, b: the
+// reply's bytes 0 .. 7 and 8 .. 13; lng: 112 bits.
+__device__ __forceinline__ int mlat_icao(unsigned long long a, unsigned long long b, bool lng) {
+  const unsigned df = (unsigned)(a & 0xFFull) >> 3;
+  const unsigned direct = (1u << 11) | (1u << 17) | (1u << 18), parity = (1u << 0) | (1u << 4) | (1u << 5) | (1u << 16) | (1u << 20) | (1u << 21);
+  return ((1u << df) & direct) ? (int)((((a >> 8) & 0xFFull) << 16) | (((a >> 16) & 0xFFull) << 8) | ((a >> 24) & 0xFFull))
+         : ((1u << df) & parity) ? mlat_remainder(a, b, lng ? 112 : 56) : -1;
 }
 
 #ifndef ADSB_MLAT_HELPERS_ONLY
@@ -139,11 +291,6 @@ __global__ void __launch_bounds__(kThreads) k_mlat_heads(const unsigned long lon
     if (live) w[i - i_lo] = part && !found ? 1 : 0;
     __syncthreads();                                  // bound[] is read by all and rewritten by thread 0 in the next round
   }
-}
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-  for (int d = kWave / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
 }
 
 // span[0 .. 2): n = span[1] - span[0] values.  cnt[c] / sum[c]: of chunk c's 256 values, those >= min_w and their sum.
@@ -226,67 +373,7 @@ __global__ void __launch_bounds__(kThreads) k_mlat_place(const int* w, const int
     __syncthreads();
   }
 }
-#endif  // ADSB_MLAT_HELPERS_ONLY
 
-// One wavefront, one head h.  Behind it lane k < cand holds candidate k of the head's group: its timestamp and stream (lane 0
-// the head itself).  -> n_heard; *cand_out.  Called by all 64 lanes.
-__device__ __forceinline__ int mlat_walk(const unsigned long long* carry, int nc, int h, double window, int lane, double* ts_out, int* stream_out,
-                                         int* cand_out) {
-  const unsigned long long* e = carry + (long long)h * kEntWords;
-  const double ts_h = __longlong_as_double((long long)e[0]);
-  const unsigned long long a = e[1], b = e[2], m = e[3];
-  double ts_l = ts_h;
-  int stream_l = (int)((m >> 32) & 0xFFFFFFull);
-  int cand = 1, n_heard = 1;
-  for (int base = h + 1; base < nc; base += kWave) {
-    const int i = base + lane;
-    bool in = false, match = false;
-    double t = 0;
-    int s = 0;
-    if (i < nc) {
-      const unsigned long long* q = carry + (long long)i * kEntWords;
-      t = __longlong_as_double((long long)q[0]);
-      in = in_window(t, ts_h, window);
-      const unsigned long long mq = q[3];
-      s = (int)((mq >> 32) & 0xFFFFFFull);
-      match = in && meta_equal(m, mq) && q[1] == a && q[2] == b;
-    }
-    const unsigned long long inside = __ballot(in), mask = __ballot(match);
-    const int hits = __popcll(mask);
-    n_heard += hits;
-    if (hits != 0 && cand < kMaxCand) {               // (wave-uniform)
-      const int k = lane - cand;
-      const bool want = k >= 0 && k < hits;
-      unsigned long long mm = mask;
-      if (want)
-        for (int j = 0; j < k; ++j) mm &= mm - 1ull;  // the k-th set bit: at most 63 rounds
-      const int src = want ? __builtin_ctzll(mm) : lane;
-      const double t_src = __shfl(t, src);
-      const int s_src = __shfl(s, src);
-      if (want) { ts_l = t_src; stream_l = s_src; }
-      cand = cand + hits < kMaxCand ? cand + hits : kMaxCand;
-    }
-    if (inside != ~0ull) break;                       // an entry outside the window, or the carry's end: the list is sorted
-  }
-  *ts_out = ts_l; *stream_out = stream_l; *cand_out = cand;
-  return n_heard;
-}
-
-// Of the candidates, lane by lane: used iff the first of its stream and the stream has a position (rx[3 s] is not NaN).
-__device__ __forceinline__ bool mlat_used(int lane, int cand, int stream, const double* rx, int n_streams) {
-  bool used = lane < cand;
-  for (int j = 0; j < cand; ++j) {                    // at most 64 broadcasts
-    const int sj = __shfl(stream, j);
-    if (j < lane && sj == stream) used = false;
-  }
-  if (used) {
-    if ((unsigned)stream >= (unsigned)n_streams) used = false;
-    else { const double x = rx[3ll * stream]; used = x == x; }
-  }
-  return used;
-}
-
-#ifndef ADSB_MLAT_HELPERS_ONLY
 // heads[n]: n = span[1] - span[0] (k_mlat_scan's totals).  nrx[h] = the used hearings of head h's group.
 __global__ void __launch_bounds__(kThreads) k_mlat_groups(const unsigned long long* carry, int nc, const int* heads, const int* span, double window,
                                                           const double* rx, int n_streams, int* nrx) {
@@ -295,33 +382,11 @@ __global__ void __launch_bounds__(kThreads) k_mlat_groups(const unsigned long lo
   for (int h = (int)blockIdx.x * kWaves + wv; h < n; h += (int)gridDim.x * kWaves) {
     const int at = heads[h];
     if (at < 0 || at >= nc) { if (lane == 0) nrx[h] = 0; continue; }
-    double ts; int stream, cand;
-    (void)mlat_walk(carry, nc, at, window, lane, &ts, &stream, &cand);
-    const int k = __popcll(__ballot(mlat_used(lane, cand, stream, rx, n_streams)));
+    const int k = mlat_group_used(carry, nc, at, window, lane, rx, n_streams);
     if (lane == 0) nrx[h] = k;
   }
 }
-#endif  // ADSB_MLAT_HELPERS_ONLY
 
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int d = kWave / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-__device__ __forceinline__ bool pivot_ok(double d) { return d > 0.0 && d <= 1.7976931348623157e308; }
-
-// The remainder of the reply's first nbits bits modulo x^24 + 0xFFF409: the address under address/parity.
-__device__ __forceinline__ int mlat_remainder(unsigned long long a, unsigned long long b, int nbits) {
-  unsigned v = 0;
-  for (int i = 0; i < nbits; ++i) {
-    const int byte = i >> 3;
-    const unsigned by = (unsigned)((byte < 8 ? a >> (8 * byte) : b >> (8 * (byte - 8))) & 0xFFull);
-    v = (v << 1) | ((by >> (7 - (i & 7))) & 1u);
-    if (v & 0x1000000u) v ^= 0x1FFF409u;
-  }
-  return (int)v;
-}
-
-#ifndef ADSB_MLAT_HELPERS_ONLY
 // gsel[n] / gfirst[n]: n = span[1] - span[0]; heads[] as for k_mlat_groups.  fixes[n]; member_stream / member_ts at gfirst[g].
 __global__ void __launch_bounds__(kThreads) k_mlat_solve(const unsigned long long* carry, int nc, const int* heads, const int* gsel, const int* gfirst,
                                                          const int* span, double window, const double* rx, int n_streams, Fix* fixes,
@@ -344,6 +409,7 @@ __global__ void __launch_bounds__(kThreads) k_mlat_solve(const unsigned long lon
     const double ts_h = __longlong_as_double((long long)e[0]);
     const double rxx = used ? rx[3ll * stream] : 0.0, rxy = used ? rx[3ll * stream + 1] : 0.0, rxz = used ? rx[3ll * stream + 2] : 0.0;
     const double d = kC * (ts - ts_h);
+    const Hearing H = {used, rxx, rxy, rxz, d};
     const double nn = (double)n_rx;
     // the start: the centroid, 10 km further from the Earth's centre; b0 from the first used hearing's receiver
     const double cx = wave_sum(rxx) / nn, cy = wave_sum(rxy) / nn, cz = wave_sum(rxz) / nn;
@@ -354,36 +420,18 @@ __global__ void __launch_bounds__(kThreads) k_mlat_solve(const unsigned long lon
     double bb = __builtin_sqrt(hx * hx + hy * hy + hz * hz);
     int status = kNoConverge, iters = 0;
     for (int it = 0; it < kMaxIter; ++it) {           // every lane holds the same sums: all leave together
-      const double dx = px - rxx, dy = py - rxy, dz = pz - rxz;
-      const double rho = __builtin_sqrt(dx * dx + dy * dy + dz * dz);
-      const double ux = used ? dx / rho : 0.0, uy = used ? dy / rho : 0.0, uz = used ? dz / rho : 0.0;
-      const double r = used ? rho - d - bb : 0.0;
-      const double a11 = wave_sum(ux * ux), a12 = wave_sum(ux * uy), a13 = wave_sum(ux * uz), a14 = wave_sum(-ux);
-      const double a22 = wave_sum(uy * uy), a23 = wave_sum(uy * uz), a24 = wave_sum(-uy);
-      const double a33 = wave_sum(uz * uz), a34 = wave_sum(-uz), a44 = nn;
-      const double g1 = wave_sum(ux * r), g2 = wave_sum(uy * r), g3 = wave_sum(uz * r), g4 = wave_sum(-r);
-      if (!pivot_ok(a11)) { status = kSingular; break; }
-      const double l11 = __builtin_sqrt(a11), l21 = a12 / l11, l31 = a13 / l11, l41 = a14 / l11;
-      const double d2 = a22 - l21 * l21;
-      if (!pivot_ok(d2)) { status = kSingular; break; }
-      const double l22 = __builtin_sqrt(d2), l32 = (a23 - l31 * l21) / l22, l42 = (a24 - l41 * l21) / l22;
-      const double d3 = a33 - l31 * l31 - l32 * l32;
-      if (!pivot_ok(d3)) { status = kSingular; break; }
-      const double l33 = __builtin_sqrt(d3), l43 = (a34 - l41 * l31 - l42 * l32) / l33;
-      const double d4 = a44 - l41 * l41 - l42 * l42 - l43 * l43;
-      if (!pivot_ok(d4)) { status = kSingular; break; }
-      const double l44 = __builtin_sqrt(d4);
-      const double y1 = -g1 / l11, y2 = (-g2 - l21 * y1) / l22, y3 = (-g3 - l31 * y1 - l32 * y2) / l33;
-      const double y4 = (-g4 - l41 * y1 - l42 * y2 - l43 * y3) / l44;
-      const double e4 = y4 / l44, e3 = (y3 - l43 * e4) / l33, e2 = (y2 - l32 * e3 - l42 * e4) / l22;
-      const double e1 = (y1 - l21 * e2 - l31 * e3 - l41 * e4) / l11;
-      px += e1; py += e2; pz += e3; bb += e4;
+      const Row j = mlat_row(H, px, py, pz, bb);
+      const double a11 = wave_sum(j.ux * j.ux), a12 = wave_sum(j.ux * j.uy), a13 = wave_sum(j.ux * j.uz), a14 = wave_sum(-j.ux);
+      const double a22 = wave_sum(j.uy * j.uy), a23 = wave_sum(j.uy * j.uz), a24 = wave_sum(-j.uy);
+      const double a33 = wave_sum(j.uz * j.uz), a34 = wave_sum(-j.uz), a44 = nn;
+      const double g1 = wave_sum(j.ux * j.r), g2 = wave_sum(j.uy * j.r), g3 = wave_sum(j.uz * j.r), g4 = wave_sum(-j.r);
+      const Step s = mlat_cholesky(a11, a12, a13, a14, a22, a23, a24, a33, a34, a44, g1, g2, g3, g4);
+      if (!s.ok) { status = kSingular; break; }
+      px += s.e1; py += s.e2; pz += s.e3; bb += s.e4;
       ++iters;
-      if (__builtin_sqrt(e1 * e1 + e2 * e2 + e3 * e3) < kStop) { status = kOk; break; }
+      if (__builtin_sqrt(s.e1 * s.e1 + s.e2 * s.e2 + s.e3 * s.e3) < kStop) { status = kOk; break; }
     }
-    const double fx = px - rxx, fy = py - rxy, fz = pz - rxz;
-    const double rr = used ? __builtin_sqrt(fx * fx + fy * fy + fz * fz) - d - bb : 0.0;
-    const double rms = __builtin_sqrt(wave_sum(rr * rr) / nn);
+    const double rms = mlat_rms(mlat_residual(H, px, py, pz, bb), nn);
     if (lane == 0) {
       const unsigned long long a = e[1], b = e[2];
       const bool lng = (e[3] >> 56) == 2ull;
@@ -392,10 +440,7 @@ __global__ void __launch_bounds__(kThreads) k_mlat_solve(const unsigned long lon
       for (int k = 0; k < 8; ++k) o->bits[k] = (unsigned char)(a >> (8 * k));
       for (int k = 0; k < 6; ++k) o->bits[8 + k] = (unsigned char)(b >> (8 * k));
       o->flags = lng ? 64 : 0;
-      const unsigned df = (unsigned)(a & 0xFFull) >> 3;
-      const unsigned direct = (1u << 11) | (1u << 17) | (1u << 18), parity = (1u << 0) | (1u << 4) | (1u << 5) | (1u << 16) | (1u << 20) | (1u << 21);
-      o->icao = ((1u << df) & direct) ? (int)((((a >> 8) & 0xFFull) << 16) | (((a >> 16) & 0xFFull) << 8) | ((a >> 24) & 0xFFull))
-                : ((1u << df) & parity) ? mlat_remainder(a, b, lng ? 112 : 56) : -1;
+      o->icao = mlat_icao(a, b, lng);
       o->n_rx = n_rx; o->n_heard = n_heard; o->status = status; o->iters = iters; o->first = first;
     }
   }

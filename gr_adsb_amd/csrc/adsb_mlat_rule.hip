@@ -15,15 +15,6 @@ using namespace adsb_mlat;
 
 static_assert(kAuxBytes == sizeof(Aux) && kFixBytes == sizeof(Fix) && kMinRxAided == 3, "the header's sizes are the device code's");
 
-namespace {
-// as adsb_mlat.hip's: enough workgroups to cover `work` units of `per` each, 2048 at the most
-unsigned cover(long long work, int per) {
-  const long long g = (work + per - 1) / per;
-  return (unsigned)(g < 1 ? 1 : g > 2048 ? 2048 : g);
-}
-template <class T> T* part(void* work, size_t off) { return (T*)((char*)work + off); }
-}  // namespace
-
 int launch_groups_rule(void* stream, const void* carry, int nc, int nh, double window, int min_rx, int n_streams, void* work, const RuleLayout& L) {
   if (nh <= 0) return 0;
   hipLaunchKernelGGL(k_mlat_groups_rule, dim3(cover(nh, kWaves)), dim3(kThreads), 0, (hipStream_t)stream, (const unsigned long long*)carry, nc,

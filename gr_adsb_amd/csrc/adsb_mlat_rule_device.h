@@ -1,6 +1,7 @@
 // adsb_mlat_rule_device.h -- device code of adsb_stream_mlat_rule's damped solver: THE DAMPED RULE of include/adsb_hip.h
-// (MULTILATERATION), evaluated on adsb_mlat_device.h's mlat_walk / mlat_used / wave_sum as they are.  Everything in front of
-// the solve -- the range, the heads, the compaction -- is adsb_mlat_device.h's; this header adds the two kernels that differ:
+// (MULTILATERATION), evaluated on adsb_mlat_device.h's device functions: the walk, the rows, the 4 x 4 step, the residual, the
+// fix's address.  Everything in front of the solve -- the range, the heads, the compaction -- is adsb_mlat_device.h's; this header
+// adds the two kernels that differ:
 //
 //   k_mlat_groups_rule  k_mlat_groups, but a group of exactly three used hearings whose head's payload gives no altitude gets
 //                       nrx = 0, so that the compaction with min_w = 3 selects the three-hearing groups that can be solved and
@@ -76,9 +77,7 @@ __global__ void __launch_bounds__(kThreads) k_mlat_groups_rule(const unsigned lo
   for (int h = (int)blockIdx.x * kWaves + wv; h < n; h += (int)gridDim.x * kWaves) {
     const int at = heads[h];
     if (at < 0 || at >= nc) { if (lane == 0) nrx[h] = 0; continue; }
-    double ts; int stream, cand;
-    (void)mlat_walk(carry, nc, at, window, lane, &ts, &stream, &cand);
-    int k = __popcll(__ballot(mlat_used(lane, cand, stream, rx, n_streams)));
+    int k = mlat_group_used(carry, nc, at, window, lane, rx, n_streams);
     if (k == 3 && mlat_alt_ft(carry[(long long)at * kEntWords + 1]) == -1) k = 0;
     if (lane == 0) nrx[h] = k;
   }
@@ -106,6 +105,7 @@ __global__ void __launch_bounds__(kThreads) k_mlat_solve_lm(const unsigned long 
     const double ts_h = __longlong_as_double((long long)e[0]);
     const double rxx = used ? rx[3ll * stream] : 0.0, rxy = used ? rx[3ll * stream + 1] : 0.0, rxz = used ? rx[3ll * stream + 2] : 0.0;
     const double d = kC * (ts - ts_h);
+    const Hearing H = {used, rxx, rxy, rxz, d};
     const double nn = (double)n_rx;
     const int alt_ft = (flags & kRuleAltitude) ? mlat_alt_ft(e[1]) : -1;
     const bool aided = alt_ft != -1;
@@ -127,16 +127,13 @@ __global__ void __launch_bounds__(kThreads) k_mlat_solve_lm(const unsigned long 
       int status = kNoConverge, iters = 0;
       double S;
       {
-        const double dx = px - rxx, dy = py - rxy, dz = pz - rxz;
-        const double r = used ? __builtin_sqrt(dx * dx + dy * dy + dz * dz) - d - bb : 0.0;
+        const double r = mlat_residual(H, px, py, pz, bb);
         const double ra = aided ? w * (mlat_height(px, py, pz, nullptr, nullptr, nullptr) - h_want) : 0.0;
         S = wave_sum(r * r) + ra * ra;
       }
       for (int trial = 0; trial < kLmTrials; ++trial) {
-        const double dx = px - rxx, dy = py - rxy, dz = pz - rxz;
-        const double rho = __builtin_sqrt(dx * dx + dy * dy + dz * dz);
-        const double ux = used ? dx / rho : 0.0, uy = used ? dy / rho : 0.0, uz = used ? dz / rho : 0.0;
-        const double r = used ? rho - d - bb : 0.0;
+        const Row j = mlat_row(H, px, py, pz, bb);
+        const double ux = j.ux, uy = j.uy, uz = j.uz, r = j.r;
         double jx = 0.0, jy = 0.0, jz = 0.0, ra = 0.0;             // the altitude row: w n(p), w (h(p) - h_want)
         if (aided) {
           double nx, ny, nz;
@@ -148,21 +145,9 @@ __global__ void __launch_bounds__(kThreads) k_mlat_solve_lm(const unsigned long 
         const double a22 = (wave_sum(uy * uy) + jy * jy) * mu, a23 = wave_sum(uy * uz) + jy * jz, a24 = wave_sum(-uy);
         const double a33 = (wave_sum(uz * uz) + jz * jz) * mu, a34 = wave_sum(-uz), a44 = nn * mu;
         const double g1 = wave_sum(ux * r) + jx * ra, g2 = wave_sum(uy * r) + jy * ra, g3 = wave_sum(uz * r) + jz * ra, g4 = wave_sum(-r);
-        if (!pivot_ok(a11)) { status = kSingular; break; }
-        const double l11 = __builtin_sqrt(a11), l21 = a12 / l11, l31 = a13 / l11, l41 = a14 / l11;
-        const double d2 = a22 - l21 * l21;
-        if (!pivot_ok(d2)) { status = kSingular; break; }
-        const double l22 = __builtin_sqrt(d2), l32 = (a23 - l31 * l21) / l22, l42 = (a24 - l41 * l21) / l22;
-        const double d3 = a33 - l31 * l31 - l32 * l32;
-        if (!pivot_ok(d3)) { status = kSingular; break; }
-        const double l33 = __builtin_sqrt(d3), l43 = (a34 - l41 * l31 - l42 * l32) / l33;
-        const double d4 = a44 - l41 * l41 - l42 * l42 - l43 * l43;
-        if (!pivot_ok(d4)) { status = kSingular; break; }
-        const double l44 = __builtin_sqrt(d4);
-        const double y1 = -g1 / l11, y2 = (-g2 - l21 * y1) / l22, y3 = (-g3 - l31 * y1 - l32 * y2) / l33;
-        const double y4 = (-g4 - l41 * y1 - l42 * y2 - l43 * y3) / l44;
-        const double e4 = y4 / l44, e3 = (y3 - l43 * e4) / l33, e2 = (y2 - l32 * e3 - l42 * e4) / l22;
-        const double e1 = (y1 - l21 * e2 - l31 * e3 - l41 * e4) / l11;
+        const Step st = mlat_cholesky(a11, a12, a13, a14, a22, a23, a24, a33, a34, a44, g1, g2, g3, g4);
+        if (!st.ok) { status = kSingular; break; }
+        const double e1 = st.e1, e2 = st.e2, e3 = st.e3, e4 = st.e4;
         ++tries;
         const double qx = px + e1, qy = py + e2, qz = pz + e3, qb = bb + e4;      // the trial point
         const bool small = __builtin_sqrt(e1 * e1 + e2 * e2 + e3 * e3) < kStop;
@@ -171,8 +156,7 @@ __global__ void __launch_bounds__(kThreads) k_mlat_solve_lm(const unsigned long 
           ++iters; status = kOk;
           break;
         }
-        const double tx = qx - rxx, ty = qy - rxy, tz = qz - rxz;
-        const double rt = used ? __builtin_sqrt(tx * tx + ty * ty + tz * tz) - d - qb : 0.0;
+        const double rt = mlat_residual(H, qx, qy, qz, qb);
         const double rat = aided ? w * (mlat_height(qx, qy, qz, nullptr, nullptr, nullptr) - h_want) : 0.0;
         const double S1 = wave_sum(rt * rt) + rat * rat;
         if (S1 <= 1.7976931348623157e308 && S1 <= S) {            // finite (a NaN compares false) and no worse: the step is taken
@@ -197,9 +181,7 @@ __global__ void __launch_bounds__(kThreads) k_mlat_solve_lm(const unsigned long 
         aflags |= kAuxSecondKept;
       }
     }
-    const double fx = kx - rxx, fy = ky - rxy, fz = kz - rxz;
-    const double rr = used ? __builtin_sqrt(fx * fx + fy * fy + fz * fz) - d - kb : 0.0;
-    const double rms = __builtin_sqrt(wave_sum(rr * rr) / nn);      // the timing rows only
+    const double rms = mlat_rms(mlat_residual(H, kx, ky, kz, kb), nn);      // the timing rows only
     if (lane == 0) {
       const unsigned long long a = e[1], b = e[2];
       const bool lng = (e[3] >> 56) == 2ull;
@@ -208,10 +190,7 @@ __global__ void __launch_bounds__(kThreads) k_mlat_solve_lm(const unsigned long 
       for (int k = 0; k < 8; ++k) o->bits[k] = (unsigned char)(a >> (8 * k));
       for (int k = 0; k < 6; ++k) o->bits[8 + k] = (unsigned char)(b >> (8 * k));
       o->flags = lng ? 64 : 0;
-      const unsigned df = (unsigned)(a & 0xFFull) >> 3;
-      const unsigned direct = (1u << 11) | (1u << 17) | (1u << 18), parity = (1u << 0) | (1u << 4) | (1u << 5) | (1u << 16) | (1u << 20) | (1u << 21);
-      o->icao = ((1u << df) & direct) ? (int)((((a >> 8) & 0xFFull) << 16) | (((a >> 16) & 0xFFull) << 8) | ((a >> 24) & 0xFFull))
-                : ((1u << df) & parity) ? mlat_remainder(a, b, lng ? 112 : 56) : -1;
+      o->icao = mlat_icao(a, b, lng);
       o->n_rx = n_rx; o->n_heard = n_heard; o->status = kstatus; o->iters = kiters; o->first = first;
       Aux* x = aux + g;
       x->up_m = kup; x->lambda = klam; x->alt_ft = alt_ft; x->tries = tries; x->flags = aflags; x->reserved = 0;

@@ -59,26 +59,18 @@ int phase_end(int launched, const DevBuf& d_work, std::vector<unsigned char>& ra
   if (!mlat_rule::guards_ok(raw.data(), raw.size(), parts) || memcmp(back.data(), words, back.size() * 8) != 0) return -1;
   return 0;
 }
-}  // namespace
+// launch_groups or launch_groups_rule
+typedef int (*groups_launcher)(void*, const void*, int, int, double, int, int, void*, const mh::Layout&);
 
-extern "C" {
-
-int sim_mlat_fix_bytes() { return mh::kFixBytes; }
-unsigned long long sim_mlat_layout_bytes(long long nc, long long n_streams) { return (unsigned long long)mh::layout((size_t)nc, (size_t)n_streams).bytes; }
-void dev_mlat_set_carry(carry_fn f) { g_carry = f; }
-int dev_mlat_dead() { return g_dead; }
-
-// sim_mlat (tests/sim/mlat_driver.cpp) over words[4 nc], the carry's entries as the emulator driver's sim_mlat_carry states them
-int dev_mlat_words(const unsigned long long* words, int nc, const double* rx, int n_streams, double window, double t_lo, double t_hi, int min_rx,
-                   void* fixes, int cap, int* n_fixes, int* member_stream, double* member_ts, int member_cap, int* n_members, int* heads_out,
-                   int* n_heads) {
-  if (min_rx < mh::kMinRx || t_lo != t_lo || t_hi != t_hi || nc < 0 || n_streams < 0) return -22;
-  *n_fixes = 0; *n_members = 0;
-  if (n_heads) *n_heads = 0;
-  if (nc == 0) return 0;
-  if (g_dead) return g_dead;
-  const mh::Layout L = mh::layout((size_t)nc, (size_t)n_streams);
-  const std::vector<std::pair<size_t, size_t>> parts = mlat_rule::parts(L, (size_t)nc, (size_t)n_streams);
+// One call over words[4 nc], after the entry point's argument table, on a work buffer carved as L with `parts`: the real
+// launchers in the host's order, phase_end behind each, the counts' range checks (min_group in the groups') and -ENOSPC before
+// the solve.  groups and solve(stream, carry, work) -> the launch's status are what differs between adsb_stream_mlat and
+// adsb_stream_mlat_rule's damped path; aux (may be null): aux_row_bytes per fix from L.aux.
+template <class Solve>
+int call(const unsigned long long* words, int nc, const double* rx, int n_streams, double window, double t_lo, double t_hi, int min_rx, int min_group,
+         const mh::Layout& L, const std::vector<std::pair<size_t, size_t>>& parts, groups_launcher groups, Solve solve, void* fixes, void* aux,
+         size_t aux_row_bytes, int cap, int* n_fixes, int* member_stream, double* member_ts, int member_cap, int* n_members, int* heads_out,
+         int* n_heads) {
   std::vector<unsigned char> raw(L.bytes + kTail, kGuard);
   std::vector<unsigned long long> back((size_t)nc * (mh::kEntBytes / 8));
   DevBuf d_carry, d_work;
@@ -98,19 +90,42 @@ int dev_mlat_words(const unsigned long long* words, int nc, const double* rx, in
   if (heads_out) memcpy(heads_out, ints(L.heads), (size_t)nh * 4);
   if (nh == 0) return 0;
 
-  if ((rc = phase_end(mh::launch_groups(st, d_carry.p, nc, nh, window, min_rx, n_streams, d_work.p, L), d_work, raw, parts, d_carry, words, back)))
-    return rc;
+  if ((rc = phase_end(groups(st, d_carry.p, nc, nh, window, min_rx, n_streams, d_work.p, L), d_work, raw, parts, d_carry, words, back))) return rc;
   const int ng = ints(L.tot_groups)[1], nm = ints(L.tot_groups)[2];
-  if (!mlat_rule::groups_in_range(ng, nm, nc, min_rx)) return -5;
+  if (!mlat_rule::groups_in_range(ng, nm, nc, min_rx, min_group)) return -5;
   *n_fixes = ng; *n_members = nm;
   if (ng > cap || nm > member_cap) return -28;
   if (ng == 0) return 0;
 
-  if ((rc = phase_end(mh::launch_solve(st, d_carry.p, nc, ng, window, n_streams, d_work.p, L), d_work, raw, parts, d_carry, words, back))) return rc;
+  if ((rc = phase_end(solve(st, d_carry.p, ng, d_work.p), d_work, raw, parts, d_carry, words, back))) return rc;
   memcpy(fixes, raw.data() + L.fixes, (size_t)ng * mh::kFixBytes);
+  if (aux) memcpy(aux, raw.data() + L.aux, (size_t)ng * aux_row_bytes);
   memcpy(member_stream, raw.data() + L.member_stream, (size_t)nm * 4);
   memcpy(member_ts, raw.data() + L.member_ts, (size_t)nm * 8);
   return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int sim_mlat_fix_bytes() { return mh::kFixBytes; }
+unsigned long long sim_mlat_layout_bytes(long long nc, long long n_streams) { return (unsigned long long)mh::layout((size_t)nc, (size_t)n_streams).bytes; }
+void dev_mlat_set_carry(carry_fn f) { g_carry = f; }
+int dev_mlat_dead() { return g_dead; }
+
+// sim_mlat (tests/sim/mlat_driver.cpp) over words[4 nc], the carry's entries as the emulator driver's sim_mlat_carry states them
+int dev_mlat_words(const unsigned long long* words, int nc, const double* rx, int n_streams, double window, double t_lo, double t_hi, int min_rx,
+                   void* fixes, int cap, int* n_fixes, int* member_stream, double* member_ts, int member_cap, int* n_members, int* heads_out,
+                   int* n_heads) {
+  if (min_rx < mh::kMinRx || t_lo != t_lo || t_hi != t_hi || nc < 0 || n_streams < 0) return -22;
+  *n_fixes = 0; *n_members = 0;
+  if (n_heads) *n_heads = 0;
+  if (nc == 0) return 0;
+  if (g_dead) return g_dead;
+  const mh::Layout L = mh::layout((size_t)nc, (size_t)n_streams);
+  const auto solve = [&](hipStream_t st, const void* carry, int ng, void* work) { return mh::launch_solve(st, carry, nc, ng, window, n_streams, work, L); };
+  return call(words, nc, rx, n_streams, window, t_lo, t_hi, min_rx, mh::kMinRx, L, mlat_rule::parts(L, (size_t)nc, (size_t)n_streams), mh::launch_groups,
+              solve, fixes, nullptr, 0, cap, n_fixes, member_stream, member_ts, member_cap, n_members, heads_out, n_heads);
 }
 
 // The emulator driver's entry point, argument for argument; -38: dev_mlat_set_carry was not called.

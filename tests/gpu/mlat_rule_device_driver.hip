@@ -3,7 +3,7 @@
 // gr_adsb_amd/csrc/adsb_mlat.hip and adsb_mlat_rule.hip -- each compiled as a unit of its own with the library's flags and
 // linked beside this file into tests/gpu/libadsb_mlat_rule_dev.so (tests/test_gpu_mlat_rule_device.py builds it) -- and their
 // real launchers launch_heads / launch_groups_rule / launch_solve_lm with their own cover().  mlat_device_driver.hip is included
-// whole: its sticky HIP status, its phase_end (guards and carry back whole after every phase) and its sim_mlat, which
+// whole: its sticky HIP status, its call() (the phases, guards and carry back whole after each) and its sim_mlat, which
 // ADSB_MLAT_SOLVER_GN is.  This file launches no kernel itself and includes no device code.  `grid` is accepted and ignored.
 // Never linked into libadsb_hip.so.
 #include "mlat_device_driver.hip"
@@ -45,42 +45,10 @@ int sim_mlat_rule(const double* ts, const unsigned char* bits14, const int* mark
   std::vector<unsigned long long> words((size_t)nc * (mh::kEntBytes / 8), 0);
   g_carry(ts, bits14, marker, stream, nc, zero_hash, words.data());
   const mh::RuleLayout L = mh::layout_rule((size_t)nc, (size_t)n_streams);
-  const std::vector<std::pair<size_t, size_t>> parts = mlat_rule::parts_rule(L, (size_t)nc, (size_t)n_streams);
-  std::vector<unsigned char> raw(L.bytes + kTail, kGuard);
-  std::vector<unsigned long long> back(words.size());
-  DevBuf d_carry, d_work;
-  HIP_OR_RETURN(hipMalloc(&d_carry.p, back.size() * 8));
-  HIP_OR_RETURN(hipMalloc(&d_work.p, raw.size()));
-  HIP_OR_RETURN(hipMemcpy(d_carry.p, words.data(), back.size() * 8, hipMemcpyHostToDevice));
-  HIP_OR_RETURN(hipMemset(d_work.p, kGuard, raw.size()));
-  if (n_streams > 0) HIP_OR_RETURN(hipMemcpy((char*)d_work.p + L.rx, rx, (size_t)n_streams * 24, hipMemcpyHostToDevice));
-  const hipStream_t st = nullptr;
-  const auto ints = [&](size_t off) { return (const int*)(raw.data() + off); };
-  int rc;
-
-  if ((rc = phase_end(mh::launch_heads(st, d_carry.p, nc, t_lo, t_hi, window, d_work.p, L), d_work, raw, parts, d_carry, words.data(), back))) return rc;
-  const int nh = ints(L.tot_heads)[1];
-  if (!mlat_rule::heads_in_range(nh, nc)) return -5;
-  if (n_heads) *n_heads = nh;
-  if (heads_out) memcpy(heads_out, ints(L.heads), (size_t)nh * 4);
-  if (nh == 0) return 0;
-
-  if ((rc = phase_end(mh::launch_groups_rule(st, d_carry.p, nc, nh, window, min_rx, n_streams, d_work.p, L), d_work, raw, parts, d_carry, words.data(),
-                      back)))
-    return rc;
-  const int ng = ints(L.tot_groups)[1], nm = ints(L.tot_groups)[2];
-  if (!mlat_rule::groups_in_range_rule(ng, nm, nc, min_rx)) return -5;
-  *n_fixes = ng; *n_members = nm;
-  if (ng > cap || nm > member_cap) return -28;
-  if (ng == 0) return 0;
-
-  if ((rc = phase_end(mh::launch_solve_lm(st, d_carry.p, nc, ng, window, n_streams, flags, alt_weight, d_work.p, L), d_work, raw, parts, d_carry,
-                      words.data(), back)))
-    return rc;
-  memcpy(fixes, raw.data() + L.fixes, (size_t)ng * mh::kFixBytes);
-  if (aux) memcpy(aux, raw.data() + L.aux, (size_t)ng * mh::kAuxBytes);
-  memcpy(member_stream, raw.data() + L.member_stream, (size_t)nm * 4);
-  memcpy(member_ts, raw.data() + L.member_ts, (size_t)nm * 8);
-  return 0;
+  const auto solve = [&](hipStream_t st, const void* carry, int ng, void* work) {
+    return mh::launch_solve_lm(st, carry, nc, ng, window, n_streams, flags, alt_weight, work, L);
+  };
+  return call(words.data(), nc, rx, n_streams, window, t_lo, t_hi, min_rx, mh::kMinRxAided, L, mlat_rule::parts_rule(L, (size_t)nc, (size_t)n_streams),
+              mh::launch_groups_rule, solve, fixes, aux, mh::kAuxBytes, cap, n_fixes, member_stream, member_ts, member_cap, n_members, heads_out, n_heads);
 }
 }

@@ -1,6 +1,7 @@
 // mlat_driver.cpp -- TEST INFRASTRUCTURE ONLY.  Runs adsb_stream_mlat's kernels (gr_adsb_amd/csrc/adsb_mlat_device.h) on the SIMT
 // emulator in hipsim.h, on host memory, over a carry the caller states entry by entry, in the order adsb_mlat.hip queues them
-// and with the host's rule of adsb_hip.hip restated: the work buffer is carved by adsb_mlat.h's layout() before the first
+// and with the host's rule of adsb_hip.hip restated, once, in call() (mlat_rule_driver.cpp runs the damped path through it
+// too): the work buffer is carved by adsb_mlat.h's layout() before the first
 // launch, the head count and then the group and member counts are read between the phases, -ENOSPC is decided before
 // k_mlat_solve and writes nothing.  Every part of the work buffer has guard bytes behind it.  The host's own code runs only in
 // tests/test_gpu_mlat.py.  Its twin is tests/gpu/mlat_device_driver.hip: the same entry point, sim_mlat, over the shipped
@@ -52,7 +53,7 @@ struct Work {
   mh::Layout L;
   std::vector<unsigned char> raw;
   std::vector<std::pair<size_t, size_t>> parts;      // offset, bytes in use
-  Work(size_t nc, size_t n_streams) : L(mh::layout(nc, n_streams)), parts(mlat_rule::parts(L, nc, n_streams)) { raw.assign(L.bytes + kTail, kGuard); }
+  Work(const mh::Layout& l, std::vector<std::pair<size_t, size_t>> p) : L(l), raw(l.bytes + kTail, kGuard), parts(std::move(p)) {}
   template <class T> T* at(size_t off) { return (T*)(raw.data() + off); }
   bool ok() const { return mlat_rule::guards_ok(raw.data(), raw.size(), parts); }
 };
@@ -68,6 +69,50 @@ void compact(Work& W, const int* w, const int* span, int min_w, int* tot, int ad
   hipsim::launch(ml::k_mlat_scan, 1u, (unsigned)ml::kThreads, span, W.at<int>(W.L.cnt), W.at<int>(W.L.sum), tot);
   hipsim::launch(ml::k_mlat_place, g, (unsigned)ml::kThreads, w, span, min_w, (const int*)W.at<int>(W.L.cnt), (const int*)W.at<int>(W.L.sum), add_lo,
                  idx, first);
+}
+
+// k_mlat_groups or k_mlat_groups_rule
+typedef void (*groups_kernel)(const unsigned long long*, int, const int*, const int*, double, const double*, int, int*);
+
+// One call over the carry, after the entry point's argument table: the launches in the host's order on the work buffer W (carved
+// and given its parts by the caller), the counts read between the phases with min_group in their range check, -ENOSPC before
+// the solve.  groups and solve(W, carry, grid of the solve kernel) are what differs between adsb_stream_mlat and
+// adsb_stream_mlat_rule's damped path; aux (may be null): aux_row_bytes per fix from W.L.aux.
+template <class Solve>
+int call(const double* ts, const unsigned char* bits14, const int* marker, const int* stream, int nc, const double* rx, int n_streams, double window,
+         double t_lo, double t_hi, int min_rx, int min_group, int grid, int zero_hash, Work& W, groups_kernel groups, Solve solve, void* fixes, void* aux,
+         size_t aux_row_bytes, int cap, int* n_fixes, int* member_stream, double* member_ts, int member_cap, int* n_members, int* heads_out,
+         int* n_heads) {
+  const std::vector<unsigned long long> carry = make_carry(ts, bits14, marker, stream, nc, zero_hash != 0), before = carry;
+  memcpy(W.at<double>(W.L.rx), rx, (size_t)n_streams * 24);
+  const unsigned long long* c = carry.data();
+  int* const range = W.at<int>(W.L.range);
+  hipsim::launch(ml::k_mlat_range, 1u, (unsigned)ml::kWave, c, nc, t_lo, t_hi, range);
+  hipsim::launch(ml::k_mlat_heads, cover(nc, ml::kThreads, grid), (unsigned)ml::kThreads, c, nc, (const int*)range, window, W.at<int>(W.L.w));
+  compact(W, W.at<int>(W.L.w), range, 1, W.at<int>(W.L.tot_heads), 1, W.at<int>(W.L.heads), nullptr, grid);
+  if (!W.ok() || carry != before) return -1;
+  const int nh = W.at<int>(W.L.tot_heads)[1];
+  if (!mlat_rule::heads_in_range(nh, nc)) return -5;
+  if (n_heads) *n_heads = nh;
+  if (heads_out) memcpy(heads_out, W.at<int>(W.L.heads), (size_t)nh * 4);
+  if (nh == 0) return 0;
+  const int* const hspan = W.at<int>(W.L.tot_heads);
+  hipsim::launch(groups, cover(nh, ml::kWaves, grid), (unsigned)ml::kThreads, c, nc, (const int*)W.at<int>(W.L.heads), hspan, window,
+                 (const double*)W.at<double>(W.L.rx), n_streams, W.at<int>(W.L.nrx));
+  compact(W, W.at<int>(W.L.nrx), hspan, min_rx, W.at<int>(W.L.tot_groups), 0, W.at<int>(W.L.gsel), W.at<int>(W.L.gfirst), grid);
+  if (!W.ok() || carry != before) return -1;
+  const int ng = W.at<int>(W.L.tot_groups)[1], nm = W.at<int>(W.L.tot_groups)[2];
+  if (!mlat_rule::groups_in_range(ng, nm, nc, min_rx, min_group)) return -5;
+  *n_fixes = ng; *n_members = nm;
+  if (ng > cap || nm > member_cap) return -28;
+  if (ng == 0) return 0;
+  solve(W, c, cover(ng, ml::kWaves, grid));
+  if (!W.ok() || carry != before) return -1;
+  memcpy(fixes, W.at<ml::Fix>(W.L.fixes), (size_t)ng * sizeof(ml::Fix));
+  if (aux) memcpy(aux, W.at<unsigned char>(W.L.aux), (size_t)ng * aux_row_bytes);
+  memcpy(member_stream, W.at<int>(W.L.member_stream), (size_t)nm * 4);
+  memcpy(member_ts, W.at<double>(W.L.member_ts), (size_t)nm * 8);
+  return 0;
 }
 }  // namespace
 
@@ -97,37 +142,14 @@ int sim_mlat(const double* ts, const unsigned char* bits14, const int* marker, c
   *n_fixes = 0; *n_members = 0;
   if (n_heads) *n_heads = 0;
   if (nc == 0) return 0;
-  const std::vector<unsigned long long> carry = make_carry(ts, bits14, marker, stream, nc, zero_hash != 0), before = carry;
-  Work W((size_t)nc, (size_t)n_streams);
-  memcpy(W.at<double>(W.L.rx), rx, (size_t)n_streams * 24);
-  const unsigned long long* c = carry.data();
-  int* const range = W.at<int>(W.L.range);
-  hipsim::launch(ml::k_mlat_range, 1u, (unsigned)ml::kWave, c, nc, t_lo, t_hi, range);
-  hipsim::launch(ml::k_mlat_heads, cover(nc, ml::kThreads, grid), (unsigned)ml::kThreads, c, nc, (const int*)range, window, W.at<int>(W.L.w));
-  compact(W, W.at<int>(W.L.w), range, 1, W.at<int>(W.L.tot_heads), 1, W.at<int>(W.L.heads), nullptr, grid);
-  if (!W.ok() || carry != before) return -1;
-  const int nh = W.at<int>(W.L.tot_heads)[1];
-  if (!mlat_rule::heads_in_range(nh, nc)) return -5;
-  if (n_heads) *n_heads = nh;
-  if (heads_out) memcpy(heads_out, W.at<int>(W.L.heads), (size_t)nh * 4);
-  if (nh == 0) return 0;
-  const int* const hspan = W.at<int>(W.L.tot_heads);
-  hipsim::launch(ml::k_mlat_groups, cover(nh, ml::kWaves, grid), (unsigned)ml::kThreads, c, nc, (const int*)W.at<int>(W.L.heads), hspan, window,
-                 (const double*)W.at<double>(W.L.rx), n_streams, W.at<int>(W.L.nrx));
-  compact(W, W.at<int>(W.L.nrx), hspan, min_rx, W.at<int>(W.L.tot_groups), 0, W.at<int>(W.L.gsel), W.at<int>(W.L.gfirst), grid);
-  if (!W.ok() || carry != before) return -1;
-  const int ng = W.at<int>(W.L.tot_groups)[1], nm = W.at<int>(W.L.tot_groups)[2];
-  if (!mlat_rule::groups_in_range(ng, nm, nc, min_rx)) return -5;
-  *n_fixes = ng; *n_members = nm;
-  if (ng > cap || nm > member_cap) return -28;
-  if (ng == 0) return 0;
-  hipsim::launch(ml::k_mlat_solve, cover(ng, ml::kWaves, grid), (unsigned)ml::kThreads, c, nc, (const int*)W.at<int>(W.L.heads),
-                 (const int*)W.at<int>(W.L.gsel), (const int*)W.at<int>(W.L.gfirst), (const int*)W.at<int>(W.L.tot_groups), window,
-                 (const double*)W.at<double>(W.L.rx), n_streams, W.at<ml::Fix>(W.L.fixes), W.at<int>(W.L.member_stream), W.at<double>(W.L.member_ts));
-  if (!W.ok() || carry != before) return -1;
-  memcpy(fixes, W.at<ml::Fix>(W.L.fixes), (size_t)ng * sizeof(ml::Fix));
-  memcpy(member_stream, W.at<int>(W.L.member_stream), (size_t)nm * 4);
-  memcpy(member_ts, W.at<double>(W.L.member_ts), (size_t)nm * 8);
-  return 0;
+  const mh::Layout L = mh::layout((size_t)nc, (size_t)n_streams);
+  Work W(L, mlat_rule::parts(L, (size_t)nc, (size_t)n_streams));
+  const auto solve = [&](Work& w, const unsigned long long* c, unsigned g) {
+    hipsim::launch(ml::k_mlat_solve, g, (unsigned)ml::kThreads, c, nc, (const int*)w.at<int>(L.heads), (const int*)w.at<int>(L.gsel),
+                   (const int*)w.at<int>(L.gfirst), (const int*)w.at<int>(L.tot_groups), window, (const double*)w.at<double>(L.rx), n_streams,
+                   w.at<ml::Fix>(L.fixes), w.at<int>(L.member_stream), w.at<double>(L.member_ts));
+  };
+  return call(ts, bits14, marker, stream, nc, rx, n_streams, window, t_lo, t_hi, min_rx, mh::kMinRx, grid, zero_hash, W, ml::k_mlat_groups, solve, fixes,
+              nullptr, 0, cap, n_fixes, member_stream, member_ts, member_cap, n_members, heads_out, n_heads);
 }
 }

@@ -131,6 +131,59 @@ def test_gauss_newton_the_argument_table_and_no_space(native):
     ctx.close()
 
 
+def test_every_refusal_names_the_entry_point_that_was_called(native):
+    """Each -EINVAL of adsb_stream_mlat and adsb_stream_mlat_rule, on four open streams and an empty carry (host work only): the
+    return code, and the context's error text -- the texts are those of the source before the two calls shared one body, each
+    with the name of the entry point that was called in front."""
+    ctx = N.Context(G.FS, G.THR, flags=G.SD | G.SH | G.DD)
+    ctx.open_streams(4)
+    nan, inf = float("nan"), float("inf")
+    n, m = ctypes.c_int32(-1), ctypes.c_int32(-1)
+
+    def plain(t_lo=-inf, t_hi=inf, min_rx=4, n_fixes=ctypes.byref(n)):
+        return ctx.lib.adsb_stream_mlat(ctx._h, t_lo, t_hi, min_rx, None, 0, n_fixes, None, None, 0, ctypes.byref(m))
+
+    def ruled(r, t_lo=-inf, t_hi=inf, n_fixes=ctypes.byref(n)):
+        return ctx.lib.adsb_stream_mlat_rule(ctx._h, t_lo, t_hi, ctypes.byref(r) if r is not None else None, None, None, 0, n_fixes, None, None, 0,
+                                             ctypes.byref(m))
+
+    missing = "n_fixes / n_members, or the arrays for cap / member_cap > 0, missing"
+    cases = [("adsb_stream_mlat", lambda: plain(t_lo=nan), "a bound is NaN"),
+             ("adsb_stream_mlat", lambda: plain(t_hi=nan), "a bound is NaN"),
+             ("adsb_stream_mlat", lambda: plain(min_rx=3), "min_rx < 4 (three-receiver fixes are not provided)"),
+             ("adsb_stream_mlat", lambda: plain(n_fixes=None), missing),
+             ("adsb_stream_mlat_rule", lambda: ruled(rule(), t_lo=nan), "a bound is NaN"),
+             ("adsb_stream_mlat_rule", lambda: ruled(rule(), t_hi=nan), "a bound is NaN"),
+             ("adsb_stream_mlat_rule", lambda: ruled(rule(), n_fixes=None), missing),
+             ("adsb_stream_mlat_rule", lambda: ruled(None), "rule is NULL"),
+             ("adsb_stream_mlat_rule", lambda: ruled(rule(min_rx=3)), "min_rx < 4 (< 3 with ADSB_MLAT_ALTITUDE)"),
+             ("adsb_stream_mlat_rule", lambda: ruled(rule(flags=ALTITUDE, min_rx=2)), "min_rx < 4 (< 3 with ADSB_MLAT_ALTITUDE)"),
+             ("adsb_stream_mlat_rule", lambda: ruled(rule(GN, 0, 3)), "min_rx < 4 (< 3 with ADSB_MLAT_ALTITUDE)"),
+             ("adsb_stream_mlat_rule", lambda: ruled(rule(solver=2)), "unknown solver"),
+             ("adsb_stream_mlat_rule", lambda: ruled(rule(flags=4)), "unknown flags"),
+             ("adsb_stream_mlat_rule", lambda: ruled(rule(GN, RESTART)), "flags need ADSB_MLAT_SOLVER_LM"),
+             ("adsb_stream_mlat_rule", lambda: ruled(rule(reserved=7)), "reserved is not 0"),
+             ("adsb_stream_mlat_rule", lambda: ruled(rule(flags=ALTITUDE, alt_weight=0.0)), "alt_weight is not finite and > 0"),
+             ("adsb_stream_mlat_rule", lambda: ruled(rule(flags=ALTITUDE, alt_weight=nan)), "alt_weight is not finite and > 0")]
+    for api, call, what in cases:
+        assert call() == -EINVAL, (api, what)
+        text = ctx.lib.adsb_last_error(ctx._h).decode()
+        assert text.startswith(api + ": ") and text == api + ": " + what, (api, what, text)
+    assert plain() == 0 and ruled(rule()) == 0 and ruled(rule(GN, 0)) == 0 and (n.value, m.value) == (0, 0)      # the empty carry
+    ctx.close()
+    c2 = N.Context(G.FS, G.THR, flags=G.SD | G.SH | G.DD)                  # the two preambles' texts
+    for api, call in (("adsb_stream_mlat", lambda: c2.lib.adsb_stream_mlat(c2._h, -inf, inf, 4, None, 0, ctypes.byref(n), None, None, 0, ctypes.byref(m))),
+                      ("adsb_stream_mlat_rule", lambda: c2.lib.adsb_stream_mlat_rule(c2._h, -inf, inf, ctypes.byref(rule()), None, None, 0, ctypes.byref(n),
+                                                                                      None, None, 0, ctypes.byref(m)))):
+        assert call() == -EINVAL and c2.lib.adsb_last_error(c2._h).decode() == api + ": no streams (adsb_streams_open first)"
+    c2.close()
+    c3 = N.Context(G.FS, G.THR, flags=G.SD | G.SH)
+    c3.open_streams(2)
+    assert c3.lib.adsb_stream_mlat(c3._h, -inf, inf, 4, None, 0, ctypes.byref(n), None, None, 0, ctypes.byref(m)) == -EINVAL
+    assert c3.lib.adsb_last_error(c3._h).decode() == "context created without ADSB_FLAG_STREAM_DEDUP"
+    c3.close()
+
+
 def test_the_front_end(native):
     """Receivers.mlat(solver="damped"): the fixes with alt_ft, up_m, tries and aux_flags added; the defaults are today's rows."""
     fe = frontend.FrontEnd(G.FS, G.THR, flags=G.SD | G.SH | G.DD)
