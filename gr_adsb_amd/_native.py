@@ -1080,7 +1080,7 @@ def shard_tail(recs, sps):
     fl = recs["flags"]
     for i in range(len(recs) - 1, -1, -1):          # behind the head region every record is KEPT: O(1) in practice
         if fl[i] & BURST_KEPT:
-            return int(recs["offset"][i]) + (119 if fl[i] & BURST_LONG_HINT else 63) * sps
+            return int(recs["offset"][i]) + int(gate_window(recs[i:i + 1], sps)[0])
     return EOB_NONE
 
 

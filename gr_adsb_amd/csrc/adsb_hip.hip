@@ -178,6 +178,7 @@ __device__ __forceinline__ adsb_cold_ptr adsb_cold_at(const adsb::DetectArgs* e)
 
 #include "adsb_device.h"
 #include "adsb_plan.h"
+#include "adsb_seam.h"
 #include "../../include/adsb_hip.h"
 
 using namespace adsb;
@@ -2479,7 +2480,6 @@ int adsb_process_batch_device(adsb_ctx* c, int format, const adsb_batch_item* it
 
 static_assert(sizeof(adsb_stream_item) == 32 && offsetof(adsb_stream_item, stream) == 16 && offsetof(adsb_stream_item, threshold) == 24,
               "adsb_stream_item layout");
-static_assert(ADSB_BURST_DEMOD == kStreamRecDemod && ADSB_BURST_LONG_HINT == kStreamRecLongHint, "adsb_plan.h and the header agree on the record flags");
 
 int adsb_streams_open(adsb_ctx* c, int32_t n_streams) {
   if (!c) return -EINVAL;
@@ -3347,15 +3347,52 @@ static int shard_post(adsb_ctx* c, Slot& s, const Summary& sum, int32_t* nres_io
   return 0;
 }
 
+// What every sharded entry point refuses, each stated once: a context with an aircraft table, a device pointer (where the
+// call has one yet) off a 16-byte boundary, and -- the two drivers, by their own name -- a confidence context.  The text
+// goes to `err_to` where that is another context.
+static int shard_refused(adsb_ctx* c, const void* d_data, adsb_ctx* err_to = nullptr) {
+  if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) return fail(err_to ? err_to : c, -EINVAL, "sharded calls are not for ADSB_FLAG_AIRCRAFT_TABLE contexts");
+  if (((uintptr_t)d_data & 15u) != 0) return fail(err_to ? err_to : c, -EINVAL, "device pointer must be 16-byte aligned");
+  return 0;
+}
+static int confidence_refused(adsb_ctx* c, const char* entry, adsb_ctx* err_to) {
+  if (!(c->flags & ADSB_FLAG_CONFIDENCE)) return 0;
+  snprintf(err_to->err, sizeof(err_to->err), "%s: not for ADSB_FLAG_CONFIDENCE contexts", entry);
+  return -EINVAL;
+}
+
 static int shard_plan_checked(adsb_ctx* c, int fmt, const void* d_data, int64_t n, int64_t origin, int64_t own_lo,
                               int64_t own_hi, int64_t stream_len, int32_t head_cands, Plan* pl) {
   if (!c || n < 0 || fmt < 0 || fmt >= ADSB_FMT_COUNT || head_cands < 0) return -EINVAL;
-  if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) return fail(c, -EINVAL, "sharded calls are not for ADSB_FLAG_AIRCRAFT_TABLE contexts");
-  if (((uintptr_t)d_data & 15u) != 0) return fail(c, -EINVAL, "device pointer must be 16-byte aligned");
+  if (int r = shard_refused(c, d_data)) return r;
   *pl = plan_shard(fmt, d_data, n, origin, own_lo, own_hi, stream_len, c->sps, head_cands);
   pl->long_aware = (c->flags & ADSB_FLAG_LONG_AWARE_GATE) != 0;
   if (origin > 0 && pl->scan_lo < 1) return fail(c, -EINVAL, "shard needs at least one sample of back halo");
   return 0;
+}
+
+// a queued shard pass, finished: its slot is the last slot, and its records -- in the slot's pinned buffer -- have passed
+// shard_post
+static int collect_pass(adsb_ctx* c, int32_t ticket, adsb_burst** recs, int32_t* nres) {
+  Slot& s = c->slot[ticket];
+  Summary sum;
+  *nres = 0;
+  int r = finish(c, s, &sum, nres);
+  if (r) return r;
+  c->last_slot = ticket;
+  if ((r = shard_post(c, s, sum, nres))) return r;
+  *recs = (adsb_burst*)s.h_out.p;
+  return 0;
+}
+
+// the tail of the blocking shard calls: the pass, its halo checks, its records
+static int shard_run(adsb_ctx* c, const Plan& pl, bool drop_overlong, adsb_burst* out, int32_t cap, int32_t* n_out) {
+  Summary s;
+  int32_t nres = 0;
+  int rc = run_pipeline(c, pl, &s, &nres);
+  if (rc) return rc;
+  if ((rc = shard_post(c, c->slot[c->last_slot], s, &nres, drop_overlong))) return rc;
+  return deliver(c, nres, out, cap, n_out);
 }
 
 int adsb_shard_device(adsb_ctx* c, int fmt, const void* d_data, int64_t n, int64_t origin, int64_t own_lo,
@@ -3364,30 +3401,21 @@ int adsb_shard_device(adsb_ctx* c, int fmt, const void* d_data, int64_t n, int64
   Plan pl;
   int rc = shard_plan_checked(c, fmt, d_data, n, origin, own_lo, own_hi, stream_len, head_cands, &pl);
   if (rc) return rc;
-  Summary s;
-  int32_t nres = 0;
-  rc = run_pipeline(c, pl, &s, &nres);
-  if (rc) return rc;
-  if ((rc = shard_post(c, c->slot[c->last_slot], s, &nres))) return rc;
-  return deliver(c, nres, out, cap, n_out);
+  return shard_run(c, pl, false, out, cap, n_out);
 }
 
 int adsb_shard_host(adsb_ctx* c, int fmt, const void* host, int64_t n, int64_t origin, int64_t own_lo, int64_t own_hi,
                     int64_t stream_len, int32_t head_cands, uint32_t shard_flags, adsb_burst* out, int32_t cap,
                     int32_t* n_out) {
   if (!c || fmt < 0 || fmt >= ADSB_FMT_COUNT || n < 1 || !host) return -EINVAL;
-  if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) return fail(c, -EINVAL, "sharded calls are not for ADSB_FLAG_AIRCRAFT_TABLE contexts");
+  int rc = shard_refused(c, nullptr);          // (before the upload: no device pointer yet)
+  if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   void* d = nullptr;
-  int rc = upload(c, host, (size_t)n * (size_t)mode_bytes(fmt), &d);
-  if (rc) return rc;
+  if ((rc = upload(c, host, (size_t)n * (size_t)mode_bytes(fmt), &d))) return rc;
   Plan pl;
   if ((rc = shard_plan_checked(c, fmt, d, n, origin, own_lo, own_hi, stream_len, head_cands, &pl))) return rc;
-  Summary s;
-  int32_t nres = 0;
-  if ((rc = run_pipeline(c, pl, &s, &nres))) return rc;
-  if ((rc = shard_post(c, c->slot[c->last_slot], s, &nres, (shard_flags & ADSB_SHARD_DROP_OVERLONG) != 0))) return rc;
-  return deliver(c, nres, out, cap, n_out);
+  return shard_run(c, pl, (shard_flags & ADSB_SHARD_DROP_OVERLONG) != 0, out, cap, n_out);
 }
 
 int adsb_submit_shard_device(adsb_ctx* c, int fmt, const void* d_data, int64_t n, int64_t origin, int64_t own_lo,
@@ -3420,33 +3448,14 @@ int32_t adsb_shard_bounds(int64_t stream_len, int32_t n_shards, int32_t g, int s
   return 0;
 }
 
-// the plain greedy gate (framer.py:121-123,165) over a shard's UNGATED centres with the incoming end-of-burst state: the
-// fallback for a shard whose head region ends inside an unbroken chain of overlapping bursts
-static int32_t gate_from(adsb_burst* recs, int32_t n, int sps, long long* eob_io) {
-  long long eob = *eob_io;
-  int32_t w = 0;
-  for (int32_t i = 0; i < n; ++i) {
-    if (recs[i].offset > eob) {
-      eob = recs[i].offset + ((recs[i].flags & ADSB_BURST_LONG_HINT) ? 119ll : 63ll) * sps;
-      adsb_burst b = recs[i];
-      b.flags = (uint16_t)((b.flags | ADSB_BURST_KEPT) & ~ADSB_BURST_HEAD);
-      recs[w++] = b;
-    }
-  }
-  *eob_io = eob;
-  return w;
-}
-
 int adsb_process_sharded_device(adsb_ctx* c, int fmt, const void* d_data, int64_t n, int64_t abs_offset, int32_t shards,
                                 adsb_burst* out, int32_t cap, int32_t* n_out) {
   if (!c || fmt < 0 || fmt >= ADSB_FMT_COUNT || n < 0 || shards < 1 || cap < 0 || (cap > 0 && !out) || !n_out) return -EINVAL;
-  if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) return fail(c, -EINVAL, "sharded calls are not for ADSB_FLAG_AIRCRAFT_TABLE contexts");
-  if (((uintptr_t)d_data & 15u) != 0) return fail(c, -EINVAL, "device pointer must be 16-byte aligned");
-  int rc = require_idle(c, kCallPending);
-  if (rc) return rc;
+  int rc = shard_refused(c, d_data);
+  if (rc || (rc = require_idle(c, kCallPending))) return rc;
   // the rows of adsb_last_confidence belong to the records of ONE pass in the order that pass delivered them; this driver
   // re-gates and concatenates the records of many passes on the host
-  if (c->flags & ADSB_FLAG_CONFIDENCE) return fail(c, -EINVAL, "adsb_process_sharded_device: not for ADSB_FLAG_CONFIDENCE contexts");
+  if ((rc = confidence_refused(c, "adsb_process_sharded_device", c))) return rc;
   *n_out = 0;
   if (n == 0) return 0;
   // adsb_wait_for_event: EVERY shard pass reads the caller's buffer and the passes run on different streams, so every
@@ -3460,52 +3469,27 @@ int adsb_process_sharded_device(adsb_ctx* c, int fmt, const void* d_data, int64_
   struct Pend { int ticket; long long own_lo, own_hi, lo, hi; };
   Pend pend[ADSB_MAX_IN_FLIGHT];
   int n_pend = 0, head = 0;
-  long long eob = -(1ll << 60);
-  int64_t total = 0;
-  const int kHead = 64;
+  SeamConsumer seam{c->sps, out, cap, abs_offset};
 
-  // collect the oldest pass: fix up its head with the carried state, append what it kept
+  // collect the oldest pass: the seam consumer fixes up its head with the carried state and appends what it kept
   auto collect = [&]() -> int {
     const Pend p = pend[head];
     head = (head + 1) % ADSB_MAX_IN_FLIGHT; --n_pend;
-    Slot& s = c->slot[p.ticket];
-    Summary sum;
-    int32_t nres = 0;
-    int r = finish(c, s, &sum, &nres);
+    adsb_burst* recs = nullptr;
+    int32_t nres = 0, kept = 0;
+    int r = collect_pass(c, p.ticket, &recs, &nres);
     if (r) return r;
-    c->last_slot = p.ticket;
-    if ((r = shard_post(c, s, sum, &nres))) return r;
-    adsb_burst* recs = (adsb_burst*)s.h_out.p;
-    int32_t kept = 0;
-    r = adsb_shard_fixup(recs, nres, c->sps, eob, &kept);
-    if (r == -EAGAIN) {
-      // the head region ended inside a chain: this shard again on the slot that has just become free -- first with the
-      // largest head, then ungated with the plain greedy gate (exact in every case)
-      for (int attempt = 0; attempt < 2 && r == -EAGAIN; ++attempt) {
-        Plan pl;
-        if ((r = shard_plan_checked(c, fmt, (const char*)d_data + (size_t)p.lo * bps, p.hi - p.lo, p.lo, p.own_lo, p.own_hi, n,
-                                    attempt == 0 ? 4096 : 0, &pl))) return r;
-        rearm();
-        if ((r = enqueue(c, s, pl, true))) return r;
-        if ((r = finish(c, s, &sum, &nres))) return r;
-        if ((r = shard_post(c, s, sum, &nres))) return r;
-        recs = (adsb_burst*)s.h_out.p;
-        if (attempt == 0) r = adsb_shard_fixup(recs, nres, c->sps, eob, &kept);
-        else { long long e = eob; kept = gate_from(recs, nres, c->sps, &e); r = 0; }
-      }
-      if (r) return r;
-      c->stats.shard_fallbacks++;
-    } else if (r) return fail(c, r, "adsb_shard_fixup");
-    if (kept > 0) {
-      const adsb_burst& last = recs[kept - 1];
-      eob = last.offset + ((last.flags & ADSB_BURST_LONG_HINT) ? 119ll : 63ll) * c->sps;
-      if (total + kept <= cap) {
-        memcpy(out + total, recs, (size_t)kept * sizeof(adsb_burst));
-        if (abs_offset) for (int32_t i = 0; i < kept; ++i) out[total + i].offset += abs_offset;
-      }
-    }
-    total += kept;
-    s.nres = kept;
+    // a head that ended inside a chain: this shard again on the slot that has just become free
+    int rerun_rc = 0;
+    auto rerun = [&](int head_cands, adsb_burst** rr, int32_t* nn) -> int {
+      Plan pl;
+      int e = shard_plan_checked(c, fmt, (const char*)d_data + (size_t)p.lo * bps, p.hi - p.lo, p.lo, p.own_lo, p.own_hi, n, head_cands, &pl);
+      if (!e) { rearm(); e = enqueue(c, c->slot[p.ticket], pl, true); }
+      if (!e) e = collect_pass(c, p.ticket, rr, nn);
+      return rerun_rc = e;
+    };
+    if ((r = seam.take(recs, nres, rerun, &kept))) return rerun_rc ? r : fail(c, r, "adsb_shard_fixup");   // (a failed re-run keeps its pass's text)
+    c->slot[p.ticket].nres = kept;
     return 0;
   };
 
@@ -3515,7 +3499,7 @@ int adsb_process_sharded_device(adsb_ctx* c, int fmt, const void* d_data, int64_
     if (own_hi <= own_lo) continue;
     if (n_pend == ADSB_MAX_IN_FLIGHT && (rc = collect())) break;
     Plan pl;
-    if ((rc = shard_plan_checked(c, fmt, (const char*)d_data + (size_t)lo * bps, hi - lo, lo, own_lo, own_hi, n, kHead, &pl))) break;
+    if ((rc = shard_plan_checked(c, fmt, (const char*)d_data + (size_t)lo * bps, hi - lo, lo, own_lo, own_hi, n, kHeadFirst, &pl))) break;
     int32_t ticket = -1;
     rearm();
     if ((rc = claim_and_enqueue(c, pl, true, &ticket))) break;
@@ -3527,10 +3511,9 @@ int adsb_process_sharded_device(adsb_ctx* c, int fmt, const void* d_data, int64_
     if (r && !rc) rc = r;
   }
   c->n_ext = 0;                       // consumed by this call, whether a pass was queued or not
+  c->stats.shard_fallbacks += seam.fallbacks;
   if (rc) return rc;
-  *n_out = (int32_t)(total > 0x7FFFFFFF ? 0x7FFFFFFF : total);
-  if (total > cap) return fail(c, -ENOSPC, "output array too small");
-  return 0;
+  return seam.finish(n_out) ? fail(c, -ENOSPC, "output array too small") : 0;
 }
 
 // ---- one process, N devices, one host ring (BASELINE config 4) --------------------------------------------
@@ -3538,7 +3521,7 @@ int adsb_process_sharded_device(adsb_ctx* c, int fmt, const void* d_data, int64_
 // overlapped time shards of it.  One feeder thread per context, inside the cpus local to its GPU: upload of shard i+1 on
 // the context's upload stream beside the shard pass of i and the record download of i-1, ADSB_MAX_IN_FLIGHT deep -- the
 // host-fed pipeline of adsb_submit_format_host with a shard plan.  The calling thread takes the finished shards in STREAM
-// order as they arrive and re-gates each head with the end-of-burst state carried over the seam (adsb_shard_fixup); a head
+// order as they arrive and re-gates each head with the end-of-burst state carried over the seam (adsb_seam.h: SeamConsumer); a head
 // that ends inside an unbroken chain has its shard run again on its own context (largest head, then ungated + the plain
 // greedy gate), after that context's feeder has finished.  No interpreter, no torch.distributed, no mailbox: the only
 // thing that crosses a seam is one int64.
@@ -3565,14 +3548,10 @@ int submit_shard_host(adsb_ctx* c, int fmt, const char* host, const MultiShard& 
 }
 
 int collect_shard(adsb_ctx* c, int32_t ticket, std::vector<adsb_burst>* out) {
-  Slot& s = c->slot[ticket];
-  Summary sum;
+  adsb_burst* recs = nullptr;
   int32_t nres = 0;
-  int r = finish(c, s, &sum, &nres);
+  const int r = collect_pass(c, ticket, &recs, &nres);
   if (r) return r;
-  c->last_slot = ticket;
-  if ((r = shard_post(c, s, sum, &nres))) return r;
-  const adsb_burst* recs = (const adsb_burst*)s.h_out.p;
   try {
     out->assign(recs, recs + nres);
   } catch (...) {                                     // (no exception crosses the ABI or ends a feeder thread)
@@ -3593,19 +3572,19 @@ int adsb_process_sharded_multi(adsb_ctx* const* ctxs, int32_t n_ctx, int fmt, co
     adsb_ctx* c = ctxs[k];
     if (!c) return -EINVAL;
     for (int j = 0; j < k; ++j) if (ctxs[j] == c) return fail(c0, -EINVAL, "adsb_process_sharded_multi: a context listed twice");
-    if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) return fail(c0, -EINVAL, "sharded calls are not for ADSB_FLAG_AIRCRAFT_TABLE contexts");
+    if (shard_refused(c, nullptr, c0)) return -EINVAL;
     // one stream, one set of rules: every context must have been created with the same rate, threshold, gate and scale
     if (c->sps != c0->sps || !(c->thr == c0->thr) || ((c->flags ^ c0->flags) & (ADSB_FLAG_LONG_AWARE_GATE | ADSB_FLAG_FEC_CONSERVATIVE)) ||
         !(c->scale[fmt] == c0->scale[fmt]))
       return fail(c0, -EINVAL, "adsb_process_sharded_multi: contexts differ in rate, threshold, gate, FEC or format scale");
-    if (c->flags & ADSB_FLAG_CONFIDENCE) return fail(c0, -EINVAL, "adsb_process_sharded_multi: not for ADSB_FLAG_CONFIDENCE contexts");
+    if (confidence_refused(c, "adsb_process_sharded_multi", c0)) return -EINVAL;
     if (!c->own_stream) return fail(c0, -EINVAL, "adsb_process_sharded_multi: not for contexts on a caller-owned stream");
     if (require_idle(c, "a submitted call is still pending on one of the contexts", c0)) return -EBUSY;
   }
   *n_out = 0;
   if (stats) memset(stats, 0, sizeof(*stats));
   if (n == 0) return 0;
-  const int sps = c0->sps, kHead = 64;
+  const int sps = c0->sps;
   const int G = n_ctx * shards_per_ctx;
   const auto t_start = std::chrono::steady_clock::now();
 
@@ -3663,7 +3642,7 @@ int adsb_process_sharded_multi(adsb_ctx* const* ctxs, int32_t n_ctx, int fmt, co
       if (n_fly == ADSB_MAX_IN_FLIGHT) collect_oldest();
       if (rc) break;
       int32_t ticket = -1;
-      const int r = submit_shard_host(c, fmt, (const char*)host, sh[(size_t)g], n, kHead, &ticket);
+      const int r = submit_shard_host(c, fmt, (const char*)host, sh[(size_t)g], n, kHeadFirst, &ticket);
       if (r) { rc = r; break; }
       fly[(head + n_fly) % ADSB_MAX_IN_FLIGHT] = Fly{g, ticket};
       ++n_fly;
@@ -3689,9 +3668,8 @@ int adsb_process_sharded_multi(adsb_ctx* const* ctxs, int32_t n_ctx, int fmt, co
   auto join_one = [&](int k) { if (!joined[(size_t)k]) { if (th[(size_t)k].joinable()) th[(size_t)k].join(); joined[(size_t)k] = 1; } };
 
   // the calling thread: finished shards in stream order, head fix-up with the carried state, records to `out`
-  long long eob = -(1ll << 60);
-  int64_t total = 0;
-  int rc = 0, fallbacks = 0;
+  SeamConsumer seam{sps, out, cap, abs_offset};
+  int rc = 0;
   for (int g = 0; g < G; ++g) {
     MultiShard& S = sh[(size_t)g];
     {
@@ -3701,35 +3679,25 @@ int adsb_process_sharded_multi(adsb_ctx* const* ctxs, int32_t n_ctx, int fmt, co
     if (S.rc) { if (!rc) rc = S.rc; continue; }
     if (rc || S.own_hi <= S.own_lo) continue;
     adsb_ctx* c = ctxs[g / shards_per_ctx];
-    int32_t kept = 0;
-    int r = adsb_shard_fixup(S.recs.data(), (int32_t)S.recs.size(), sps, eob, &kept);
-    if (r == -EAGAIN) {
-      // the head region ended inside a chain: this shard again on its own context, once its feeder is through with it
+    // a head that ended inside a chain: this shard again on its own context, once its feeder is through with it
+    auto rerun = [&](int head_cands, adsb_burst** rr, int32_t* nn) -> int {
       join_one(g / shards_per_ctx);
-      for (int attempt = 0; attempt < 2 && r == -EAGAIN; ++attempt) {
-        int32_t ticket = -1;
-        if ((r = submit_shard_host(c, fmt, (const char*)host, S, n, attempt == 0 ? 4096 : 0, &ticket))) break;
-        if ((r = collect_shard(c, ticket, &S.recs))) break;
-        if (attempt == 0) r = adsb_shard_fixup(S.recs.data(), (int32_t)S.recs.size(), sps, eob, &kept);
-        else { long long e = eob; kept = gate_from(S.recs.data(), (int32_t)S.recs.size(), sps, &e); r = 0; }
-      }
-      if (!r) { ++fallbacks; c->stats.shard_fallbacks++; }
-    }
+      int32_t ticket = -1;
+      int e = submit_shard_host(c, fmt, (const char*)host, S, n, head_cands, &ticket);
+      if (!e) e = collect_shard(c, ticket, &S.recs);
+      *rr = S.recs.data(); *nn = (int32_t)S.recs.size();
+      return e;
+    };
+    int32_t kept = 0;
+    const int fb = seam.fallbacks;
+    const int r = seam.take(S.recs.data(), (int32_t)S.recs.size(), rerun, &kept);
     if (r) { rc = r < 0 ? r : -EIO; if (r == -EAGAIN) rc = -EIO; continue; }
-    if (kept > 0) {
-      const adsb_burst& last = S.recs[(size_t)kept - 1];
-      eob = last.offset + ((last.flags & ADSB_BURST_LONG_HINT) ? 119ll : 63ll) * sps;
-      if (total + kept <= cap) {
-        memcpy(out + total, S.recs.data(), (size_t)kept * sizeof(adsb_burst));
-        if (abs_offset) for (int32_t i = 0; i < kept; ++i) out[total + i].offset += abs_offset;
-      }
-    }
-    total += kept;
+    c->stats.shard_fallbacks += seam.fallbacks - fb;
     std::vector<adsb_burst>().swap(S.recs);
   }
   for (int k = 0; k < n_ctx; ++k) join_one(k);
   if (stats) {
-    stats->contexts = n_ctx; stats->shards = G; stats->fallbacks = fallbacks;
+    stats->contexts = n_ctx; stats->shards = G; stats->fallbacks = seam.fallbacks;
     stats->wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     for (int k = 0; k < n_ctx; ++k) {
       stats->feeder_s[k] = feed_s[(size_t)k];
@@ -3742,9 +3710,7 @@ int adsb_process_sharded_multi(adsb_ctx* const* ctxs, int32_t n_ctx, int fmt, co
       if (ctxs[k] != c0 && ctxs[k]->err[0] && !c0->err[0]) snprintf(c0->err, sizeof(c0->err), "context %d: %s", k, ctxs[k]->err);
     return rc;
   }
-  *n_out = (int32_t)(total > 0x7FFFFFFF ? 0x7FFFFFFF : total);
-  if (total > cap) return fail(c0, -ENOSPC, "output array too small");
-  return 0;
+  return seam.finish(n_out) ? fail(c0, -ENOSPC, "output array too small") : 0;
 }
 
 // ---- plain device memory for callers that do not link HIP (C / ctypes clients of the *_device entry points) ---------------
@@ -3772,58 +3738,15 @@ int adsb_device_upload(adsb_ctx* c, void* d, const void* host, size_t bytes) {
   return 0;
 }
 
+// the host gates over delivered records: adsb_seam.h
 int adsb_shard_fixup(adsb_burst* recs, int32_t n, int sps, int64_t eob_in, int32_t* n_kept) {
-  // recs: output of adsb_shard_device(head_cands > 0): every centre of the shard's head (ADSB_BURST_HEAD,
-  // complete, gated or not) followed by the centres a fresh-state gate kept.  Re-gate the head with the
-  // true incoming eob (framer.py:121-123,165) until the first centre that starts an independent chain
-  // -- beyond the reach (offset + gate window) of every head centre before it (trivially true for the first one)
-  // and beyond eob_in: it is accepted whatever came before, so from there on the fresh-state decisions are exact.
-  // A shard that lies entirely in its head region is re-gated completely and never fails; whether its END-OF-BURST
-  // state equals the fresh-state one is a separate question the caller answers with the same criterion
-  // (gr_adsb_amd/_native.py shard_head_sync; sharding.finish_shard falls back to adsb_stitch when it does not).
-  // The window of a record is 63*sps (framer.py:165), or 119*sps for records flagged ADSB_BURST_LONG_HINT by a long-aware context.
   if (n < 0 || (n > 0 && !recs) || sps < 2 || !n_kept) return -EINVAL;
-  int i = 0, w = 0;
-  long long eob = eob_in, reach = -(1ll << 61);
-  bool synced = false;
-  for (; i < n && (recs[i].flags & ADSB_BURST_HEAD); ++i) {
-    const long long p = recs[i].offset;
-    const long long gate = ((recs[i].flags & ADSB_BURST_LONG_HINT) ? 119ll : 63ll) * sps;
-    if (p > reach && p > eob_in) { synced = true; break; }   // also i == 0: the first centre lies beyond eob_in
-    if (p + gate > reach) reach = p + gate;
-    if (p > eob) {
-      eob = p + gate;
-      adsb_burst b = recs[i];
-      b.flags = (uint16_t)((b.flags | ADSB_BURST_KEPT) & ~ADSB_BURST_HEAD);
-      recs[w++] = b;
-    }
-  }
-  if (!synced && i < n) return -EAGAIN;   // the head region ended inside a chain: ask for a larger head
-  for (; i < n; ++i) {
-    if (!(recs[i].flags & ADSB_BURST_KEPT)) continue;
-    adsb_burst b = recs[i];
-    b.flags = (uint16_t)(b.flags & ~ADSB_BURST_HEAD);
-    recs[w++] = b;
-  }
-  *n_kept = w;
-  return 0;
+  return shard_fixup(recs, n, sps, eob_in, n_kept);
 }
 
 int adsb_stitch(adsb_burst* cands, int32_t n, int sps, int32_t* n_kept) {
   if (n < 0 || (n > 0 && !cands) || sps < 2) return -EINVAL;
-  long long eob = -(1ll << 61);
-  int w = 0;
-  for (int i = 0; i < n; ++i) {
-    if (i > 0 && cands[i].offset <= cands[i - 1].offset) return -EINVAL;  // must be in stream order
-    if (cands[i].offset > eob) {                                           // framer.py:121
-      eob = cands[i].offset + ((cands[i].flags & ADSB_BURST_LONG_HINT) ? 119ll : 63ll) * sps;   // framer.py:165 (+ §8f-4)
-      adsb_burst b = cands[i];
-      b.flags |= ADSB_BURST_KEPT;
-      cands[w++] = b;
-    }
-  }
-  if (n_kept) *n_kept = w;
-  return 0;
+  return stitch(cands, n, sps, n_kept);
 }
 
 int adsb_host_alloc(void** p, size_t bytes) {

@@ -6,7 +6,13 @@
 // Citations: /root/reference/python/adsb/framer.py, demod.py.
 #pragma once
 
+#include "../../include/adsb_hip.h"      // the record flag bits
+
 namespace adsb {
+
+// Samples the re-trigger gate stays closed behind a record: 63 symbols (framer.py:165), 119 behind a record that a
+// long-aware context flagged ADSB_BURST_LONG_HINT.  THE statement of the window for every host-side gate.
+inline long long gate_window(unsigned flags, int sps) { return ((flags & ADSB_BURST_LONG_HINT) ? 119ll : 63ll) * sps; }
 
 struct Plan {
   int mode;                 // 0 complex64 IQ, 1 float |IQ|^2
@@ -243,9 +249,8 @@ inline void fill_stream_copies(SG& g, SV& v, const StreamItem& it, long long pos
 // emulator driver).  A record is left out when its burst ends at or beyond the end of the item's buffer -- its last bits
 // were sliced from samples that had not arrived: shard_post's rule (ADSB_SHARD_DROP_OVERLONG) -- and so is, by the kernel,
 // a pulse still high there (Summary.flags bit 2): both are counted in *overlong.  *eob moves to the end of the last
-// DELIVERED record's gate window (framer.py:165; 119 symbols behind a long-hinted record of a long-aware context).
+// DELIVERED record's gate window (gate_window).
 // off(r) / flags(r): a record's stream offset and its 16 flag bits.  Returns the number of records kept in dst (may be src).
-constexpr unsigned kStreamRecDemod = 1u, kStreamRecLongHint = 0x2000u;         // ADSB_BURST_DEMOD, ADSB_BURST_LONG_HINT
 template <class R, class Off, class Fl>
 inline int stream_deliver(const R* src, int n, R* dst, const Plan& pl, unsigned sum_flags, int sps, Off off, Fl flags,
                           long long* eob, long long* overlong) {
@@ -255,8 +260,8 @@ inline int stream_deliver(const R* src, int n, R* dst, const Plan& pl, unsigned 
   for (int i = 0; i < n; ++i) {
     const long long o = off(src[i]);
     const unsigned f = flags(src[i]);
-    if ((f & kStreamRecDemod) && o + 119ll * sps + sps / 2 >= buf_end) { ++*overlong; continue; }
-    *eob = o + ((f & kStreamRecLongHint) ? 119ll : 63ll) * sps;
+    if ((f & ADSB_BURST_DEMOD) && o + 119ll * sps + sps / 2 >= buf_end) { ++*overlong; continue; }
+    *eob = o + gate_window(f, sps);
     dst[w++] = src[i];
   }
   return w;

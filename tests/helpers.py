@@ -228,6 +228,33 @@ def preamble_train_iq(n, spacing=32, sps=2, seed=3):
     return iq
 
 
+def seam_chain_iq(n=1 << 15, seam=1 << 14, seed=4):
+    """complex64 IQ at 2 Msps for a sharded call of two shards (the seam at `seam`): noise floor, a train of bare preambles every
+    32 symbols from 576 samples before the seam to 200 preambles behind it -- the gate keeps every other one, the last one in
+    front of the seam 64 samples before it, so the second shard's first centre lies inside the carried window (a fresh-state
+    gate keeps the wrong half of the train) and its first 64 centres all lie inside that chain: its head fix-up asks for a
+    larger head -- and ONE preamble on its own well behind the chain: with the largest head (more centres than the shard
+    has) the fix-up finds it as the start of an independent chain and succeeds."""
+    rng = np.random.default_rng(seed)
+    a = (rng.random(n, dtype=np.float32) * np.float32(0.02)).astype(np.float32)          # |IQ|^2 <= 4e-4, threshold 0.01
+    for s in list(range(seam - 576, seam + 200 * 64, 64)) + [n - 1500]:
+        for c in (0, 2, 7, 9):
+            a[s + c] = np.float32(1.0) + np.float32(0.25) * rng.random(dtype=np.float32)
+    iq = np.zeros(n, dtype=np.complex64)
+    iq.real = a
+    iq.imag = (rng.random(n, dtype=np.float32) * np.float32(0.01)).astype(np.float32)
+    return iq
+
+
+def assert_second_head_fallback(native, got, whole, fallbacks):
+    """the sharded result of seam_chain_iq: the whole-buffer call's records byte for byte apart from ADSB_BURST_HEAD, and
+    exactly one shard that fell back"""
+    want = whole.copy()
+    want["flags"] &= np.uint16(~native.BURST_HEAD & 0xFFFF)
+    assert len(want) > 100 and got.tobytes() == want.tobytes()
+    assert fallbacks == 1, fallbacks
+
+
 def rise_storm_iq8(n, seed=0, offset_binary=False, hi=100, lo=2, half=1):
     """Interleaved 8-bit IQ (2n values) whose |IQ|^2 crosses a threshold of 0.01 (scale 1/128) up to 512 times per 1024-sample
     tile: blocks of 16 * half samples that are either alternating high / low sample by sample (8 * half rises), a bare

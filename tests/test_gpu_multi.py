@@ -7,7 +7,7 @@ oracle), the case whose every seam falls inside an unbroken chain (each shard ta
 import numpy as np
 import pytest
 
-from helpers import preamble_train_iq, assert_recs_equal
+from helpers import preamble_train_iq, assert_recs_equal, seam_chain_iq, assert_second_head_fallback
 
 pytestmark = pytest.mark.gpu
 
@@ -62,6 +62,18 @@ def test_one_process_n_contexts_equal_one_blocking_call(native, fs, bps, log2n, 
     # the contexts stay usable for ordinary calls, in any order
     for cx in reversed(md.contexts):
         assert _clear_head(native, cx.process_iq(iq)).tobytes() == whole.tobytes()
+    md.close()
+
+
+def test_one_process_larger_head_synchronises(native):
+    """The fallback's middle step (helpers.seam_chain_iq): two contexts of one shard each, the second context's shard is run
+    again with the largest head and synchronises on the preamble behind the chain."""
+    from gr_adsb_amd.frontend import MultiDevice
+    iq = seam_chain_iq()
+    md = MultiDevice(2e6, 0.01, devices=[0, 0])
+    whole = md.contexts[0].process_iq(iq)
+    got = md.process_host(native.FMT_FC32, iq, 1)
+    assert_second_head_fallback(native, got, whole, md.last_stats["fallbacks"])
     md.close()
 
 

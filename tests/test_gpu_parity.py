@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 from helpers import (SCHEDULES, Golden, every_byte_pair_stream, preamble_train_iq, assert_recs_equal, assert_recs_match_golden, bulk_golden_names, golden_names,
-                     large_golden_names, pathological_names, rate_golden_names, schedules_of, snr_bits, unpack)
+                     large_golden_names, pathological_names, rate_golden_names, schedules_of, snr_bits, unpack, seam_chain_iq,
+                     assert_second_head_fallback)
 
 pytestmark = pytest.mark.gpu
 
@@ -854,6 +855,18 @@ def test_sharded_driver_in_c_equals_single_call(native, torch_mod, fs, bps, log2
     off = fe.process_sharded_tensor(native.FMT_FC32, t, shards, abs_offset=12345)
     assert np.array_equal(off["offset"], whole["offset"] + 12345) and np.array_equal(off["bits"], whole["bits"])
     assert fe.process_iq_tensor(t).tobytes() == whole.tobytes()
+
+
+def test_sharded_driver_larger_head_synchronises(native, torch_mod):
+    """The fallback's middle step: the second shard's first 64 centres lie inside one chain, its re-run with the largest head
+    reaches the preamble that stands on its own behind the chain (helpers.seam_chain_iq)."""
+    from gr_adsb_amd.frontend import FrontEnd
+    fe = FrontEnd(2e6, 0.01)
+    t = to_dev(torch_mod, seam_chain_iq())
+    whole = fe.process_iq_tensor(t)
+    before = fe.stats()["shard_fallbacks"]
+    got = fe.process_sharded_tensor(native.FMT_FC32, t, 2)
+    assert_second_head_fallback(native, got, whole, fe.stats()["shard_fallbacks"] - before)
 
 
 def test_sharded_driver_other_formats(native, torch_mod):

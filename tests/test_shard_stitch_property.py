@@ -9,10 +9,11 @@ Round-1 bug pinned here: a shard lying entirely inside its head region published
 its true tail depended on the incoming eob (VERDICT r01 weak #1, ADVICE r01 medium)."""
 import numpy as np
 import pytest
-from hypothesis import HealthCheck, given, settings, strategies as st
+from hypothesis import HealthCheck, given, settings
 
 from gr_adsb_amd import _native as N
 from gr_adsb_amd import sharding
+from shard_worlds import device_shard, partition, truth, ungated_shard, worlds
 
 
 @pytest.fixture(scope="module")
@@ -21,38 +22,10 @@ def native():
     return N
 
 
-def device_shard(offs, long_hint, sps, head_n):
-    """What adsb_shard_device(head_cands=head_n) returns for a shard whose matched centres are `offs`: the gate run
-    from fresh state (KEPT), the first head_n centres delivered whether kept or not (HEAD)."""
-    n = len(offs)
-    gate = np.where(long_hint, 119, 63) * sps
-    kept = np.zeros(n, dtype=bool)
-    eob = -(1 << 61)
-    for i in range(n):
-        if offs[i] > eob:
-            kept[i] = True
-            eob = int(offs[i]) + int(gate[i])
-    head = np.arange(n) < head_n
-    sel = kept | head
-    recs = np.zeros(int(sel.sum()), dtype=N.BURST_DTYPE)
-    recs["offset"] = offs[sel]
-    recs["flags"] = (np.where(kept[sel], N.BURST_KEPT, 0) | np.where(head[sel], N.BURST_HEAD, 0)
-                     | np.where(long_hint[sel], N.BURST_LONG_HINT, 0)).astype(np.uint16)
-    return recs
-
-
-def ungated_shard(offs, long_hint):
-    recs = np.zeros(len(offs), dtype=N.BURST_DTYPE)
-    recs["offset"] = offs
-    recs["flags"] = np.where(long_hint, N.BURST_LONG_HINT, 0).astype(np.uint16)
-    return recs
-
-
 def run_world(offs, long_hint, cuts, sps, head_n):
     """Partition by owner ranges (cuts = sorted stream offsets where a new shard begins), run every rank's
     finish_shard with in-process stand-ins for the two collectives, return (concatenated result, fallbacks)."""
-    edges = [-(1 << 60)] + list(cuts) + [1 << 60]
-    parts = [(offs >= lo) & (offs < hi) for lo, hi in zip(edges[:-1], edges[1:])]
+    parts = partition(offs, cuts)
     world = len(parts)
     dev = [device_shard(offs[m], long_hint[m], sps, head_n) for m in parts]
     ung = [ungated_shard(offs[m], long_hint[m]) for m in parts]
@@ -67,11 +40,6 @@ def run_world(offs, long_hint, cuts, sps, head_n):
     fb = sharding.STATS["fallbacks"] - before
     assert fb in (0, world)                         # every rank takes the same decision
     return np.concatenate(out) if out else np.zeros(0, dtype=N.BURST_DTYPE), fb // max(1, world)
-
-
-def truth(offs, long_hint, sps):
-    c = ungated_shard(offs, long_hint)
-    return N.stitch(c, sps)
 
 
 def test_judge_repro_three_short_shards(native):
@@ -97,25 +65,6 @@ def test_all_head_shard_with_a_chain_head_needs_no_fallback(native):
     # empty shards in between pass the state through
     got, fb = run_world(offs, lh, [960, 970, 980, 1000, 1550, 1560], 2, sharding.HEAD_CANDS)
     assert got["offset"].tolist() == [950, 1500, 1700] and fb == 0
-
-
-@st.composite
-def worlds(draw):
-    sps = draw(st.sampled_from([2, 4, 8, 20]))
-    gate = 63 * sps
-    n = draw(st.integers(0, 60))
-    # gaps around the two gate windows, so that chains, chain breaks and exact ties all occur
-    gaps = draw(st.lists(st.one_of(st.integers(1, 3), st.integers(gate - 2, gate + 2), st.integers(119 * sps - 2, 119 * sps + 2),
-                                   st.integers(1, 3 * gate)), min_size=n, max_size=n))
-    offs = np.cumsum(np.asarray(gaps, dtype=np.int64)) + 1000 if n else np.zeros(0, dtype=np.int64)
-    long_hint = np.asarray(draw(st.lists(st.booleans(), min_size=n, max_size=n)), dtype=bool) if draw(st.booleans()) \
-        else np.zeros(n, dtype=bool)
-    hi = int(offs[-1]) + 10 if n else 2000
-    # shard boundaries anywhere, including shards one sample long
-    ncut = draw(st.integers(0, 12))
-    cuts = sorted(set(draw(st.lists(st.integers(990, hi), min_size=ncut, max_size=ncut))))
-    head_n = draw(st.sampled_from([1, 2, 3, 8, 64]))
-    return offs, long_hint, cuts, sps, head_n
 
 
 @settings(max_examples=600, deadline=None, suppress_health_check=[HealthCheck.too_slow])
