@@ -15,7 +15,7 @@ DEDUP_SOURCE = "adsb_dedup.hip"
 MLAT_SOURCE = "adsb_mlat.hip"
 # adsb_stream_mlat_rule's kernels (the damped solver): a fifth unit, for the same reason
 MLAT_RULE_SOURCE = "adsb_mlat_rule.hip"
-DEPS = ["adsb_hip.hip", "adsb_device.h", "adsb_plan.h", "adsb_seam.h", os.path.join("..", "..", "include", "adsb_hip.h"),
+DEPS = ["adsb_hip.hip", "adsb_env_hip.h", "adsb_device.h", "adsb_plan.h", "adsb_seam.h", os.path.join("..", "..", "include", "adsb_hip.h"),
         "adsb_shared.hip", "adsb_shared.h", "adsb_shared_device.h", "adsb_dedup.hip", "adsb_dedup.h", "adsb_dedup_device.h",
         "adsb_mlat.hip", "adsb_mlat.h", "adsb_mlat_device.h",
         "adsb_mlat_rule.hip", "adsb_mlat_rule.h", "adsb_mlat_rule_device.h"]

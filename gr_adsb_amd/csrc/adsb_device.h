@@ -42,6 +42,11 @@
 #ifndef ADSB_ROUTE
 #define ADSB_ROUTE(id, offset) ((void)0)
 #endif
+// ADSB_MEDIAN_PATH(id): a test hook at every data-dependent turn of noise_median (id: the MedianPath below).  Empty here, like
+// ADSB_ROUTE; tests/sim/sim_driver.cpp defines it to log which turns the median of which window took.
+#ifndef ADSB_MEDIAN_PATH
+#define ADSB_MEDIAN_PATH(id) ((void)0)
+#endif
 // ADSB_AIR_MIN / _LOAD / _STORE: the aircraft table's accesses, agent-scope atomics (the table is shared by every XCD: a
 // plain load could hit a stale line of another XCD's L2).  A host build without HIP (the SIMT emulator of tests/sim, whose
 // fibers run one at a time) gets plain memory operations.
@@ -74,6 +79,20 @@ inline unsigned long long adsb_fleet_cas(unsigned long long* p, unsigned long lo
 #endif
 #define ADSB_FLEET_CAS(p, e, d) adsb_fleet_cas((p), (e), (d))
 #endif
+// ADSB_QUIET(v): the float v itself, a signalling NaN as the quiet NaN (same sign and payload) arithmetic would make of it:
+// v_max_f32 v, v, v.  Defined here and not asked of the includer, so that the environment an includer has to provide stays
+// as it was; a host build without HIP multiplies by a one the compiler cannot see through.
+#ifndef ADSB_QUIET
+#if defined(__HIP__)
+#define ADSB_QUIET(v) __builtin_canonicalizef(v)
+#else
+inline float adsb_quiet_host(float v) {
+  volatile float one = 1.0f, r = v * one;
+  return r;
+}
+#define ADSB_QUIET(v) adsb_quiet_host(v)
+#endif
+#endif
 // ADSB_COLD_AT(e): the argument block *e of a device TABLE (const DetectArgs* e, not written during the launch) as the pointer
 // type adsb_cold() returns.  The product maps it to the constant address space behind an empty asm statement; a host build
 // (the SIMT emulator) reads the entry where it lies.
@@ -91,6 +110,29 @@ enum Route : int {
   kRouteLongFast = 4,     // k_longrun: burst_finish, whole footprint inside the buffer
   kRouteLongClipped = 5,  // k_longrun: burst_finish, clipped noise window or burst near the end of the buffer
   kRouteCount = 6
+};
+
+// The turns of noise_median, as ADSB_MEDIAN_PATH names them: what became of the hint, where the bit-wise select left, and how
+// the upper middle of an even window was found.  (A window that is empty or holds a NaN has no upper-middle outcome; a hint
+// that was proved exact skips the select and has no exit.)
+enum MedianPath : int {
+  kMedHintNone = 0,       // no hint, or one outside [0x00800000, 0xFF000000): not tried
+  kMedHintExact = 1,      // QUANT only: the hint IS the key of rank kt
+  kMedHintBelow = 2,      // the key lies in [hint - 2^23, hint)
+  kMedHintAbove = 3,      // the key lies in [hint, hint + 2^23)
+  kMedHintRefused = 4,    // tried, and the key is not within 2^23 of it: the select starts from the full range
+  kMedExitOne16 = 5,      // one key left in an interval of 2^16 / 2^12 / 2^8 keys
+  kMedExitOne12 = 6,
+  kMedExitOne8 = 7,
+  kMedExitCrowd16 = 8,    // four or more keys, all equal, in an interval of 2^16 / 2^12 / 2^8 keys
+  kMedExitCrowd12 = 9,
+  kMedExitCrowd8 = 10,
+  kMedExitBit0 = 11,      // the select ran to bit 0
+  kMedUpperOdd = 12,      // odd window: there is no upper middle
+  kMedUpperExactAgain = 13,   // the exact hint's second count says the value occurs again
+  kMedUpperCount = 14,    // a count says the value occurs again
+  kMedUpperNext = 15,     // the smallest key above the lower middle
+  kMedianPathCount = 16
 };
 
 constexpr int kThreads = 256;            // 4 wavefronts per workgroup: the tail kernels and the one-launch small pass
@@ -472,6 +514,7 @@ __device__ __forceinline__ float noise_median(int nwin, bool val0, bool val1, fl
     if (c_lt <= kt && c_le > kt) { exact = true; exact_again = c_le >= kt + 2; }
   }
   if (exact) {
+    ADSB_MEDIAN_PATH(kMedHintExact);
     A = h; have = true; full = false;
   } else
   if (h >= 0x00800000u && h < 0xFF000000u) {                 // wave-uniform; h +- 2^23 cannot wrap
@@ -479,9 +522,14 @@ __device__ __forceinline__ float noise_median(int nwin, bool val0, bool val1, fl
     const unsigned T2 = c1 <= kt ? h + 0x00800000u : h - 0x00800000u;
     const int c2 = below(T2);                                  // <= kt: the key is >= T2
     if ((c1 <= kt) != (c2 <= kt)) {                            // the key lies between h and T2: in [lo, lo + 2^23)
+      ADSB_MEDIAN_PATH(c1 <= kt ? kMedHintAbove : kMedHintBelow);
       lo = c1 <= kt ? h : T2;
       full = false;
+    } else {
+      ADSB_MEDIAN_PATH(kMedHintRefused);
     }
+  } else {
+    ADSB_MEDIAN_PATH(kMedHintNone);
   }
   if (full) {                                                // no guess, or not near it: bits 31 .. 23 from the full range
 #pragma unroll
@@ -506,13 +554,13 @@ __device__ __forceinline__ float noise_median(int nwin, bool val0, bool val1, fl
       const unsigned sp = 1u << (bit - 3);
       const bool in0 = k0 - lo < sp, in1 = k1 - lo < sp;
       const int inside = adsb_uniform(__popcll(__ballot(in0)) + __popcll(__ballot(in1)));
-      if (inside == 1) { single = true; span = sp; break; }
+      if (inside == 1) { ADSB_MEDIAN_PATH(kMedExitOne16 + ((19 - bit) >> 2)); single = true; span = sp; break; }
       if (inside >= 4) {                                      // wave-uniform
         unsigned mn = in0 ? k0 : 0xFFFFFFFFu, mx = in0 ? k0 : 0u;
         if (in1) { mn = k1 < mn ? k1 : mn; mx = k1 > mx ? k1 : mx; }
         mn = adsb_wave_min_u32(mn);
         mx = adsb_wave_max_u32(mx);
-        if (mn == mx) { A = mn; have = true; break; }
+        if (mn == mx) { ADSB_MEDIAN_PATH(kMedExitCrowd16 + ((19 - bit) >> 2)); A = mn; have = true; break; }
       }
     }
   }
@@ -524,7 +572,10 @@ __device__ __forceinline__ float noise_median(int nwin, bool val0, bool val1, fl
     A = m0 ? a0 : a1;
     have = true;
   }
-  if (!have) A = lo;                                         // key of the lower middle
+  if (!have) {                                               // the select ran to bit 0: lo is the key of the lower middle
+    ADSB_MEDIAN_PATH(kMedExitBit0);
+    A = lo;
+  }
   hint = A;
   float med;
   if (nwin == 0) med = __builtin_bit_cast(float, 0xFFC00000u);       // np.median([]) == 0/0: default NaN, sign set
@@ -532,15 +583,20 @@ __device__ __forceinline__ float noise_median(int nwin, bool val0, bool val1, fl
   // (a median of zero is +0.0 whatever the signs of the zeros in the window: np.median is np.mean of the middle element(s),
   // whose sum starts from +0.0 -- 0.0 + -0.0 = +0.0 -- so the result never depends on how -0.0 and +0.0 were ordered; the
   // key order here puts -0.0 below +0.0, the rounded add of +0.0 below makes that invisible.  x + 0.0 == x for every other x)
-  else if (nwin & 1) med = __fadd_rn(key_f32(A), 0.0f);
-  else {
+  else if (nwin & 1) {
+    ADSB_MEDIAN_PATH(kMedUpperOdd);
+    med = __fadd_rn(key_f32(A), 0.0f);
+  } else {
     // upper middle: A again if it occurs often enough (impossible when A was alone in its interval), else the
     // smallest key above A
     bool again = false;
     if (exact) again = exact_again;
     else if (!single) again = __popcll(__ballot(k0 <= A)) + __popcll(__ballot(k1 <= A)) >= kt + 2;
     unsigned B = A;
-    if (!again) {                                            // wave-uniform
+    if (again) {
+      ADSB_MEDIAN_PATH(exact ? kMedUpperExactAgain : kMedUpperCount);
+    } else {                                                 // wave-uniform
+      ADSB_MEDIAN_PATH(kMedUpperNext);
       unsigned m = (k0 > A) ? k0 : 0xFFFFFFFFu;
       if (k1 > A && k1 < m) m = k1;
       B = adsb_wave_min_u32(m);
@@ -1127,14 +1183,24 @@ __device__ __forceinline__ unsigned unit_mask(const float* p, float thr) {
 // The 16-chip preamble test (framer.py:137-147) for a centre whose taps all lie in the LDS window: chip k is
 // tp[k*half] > tp[0]/2 and the chips must spell 1010000101000000.  Chips 0, 2, 7, 9 are compared one by one (a NaN
 // tap fails); the twelve others must all be "not above", i.e. their maximum is not above: five v_max3 and one v_max
-// (a NaN among them counts as a low chip and is skipped by the maximum, which is the same thing) and ONE compare.
+// (a QUIET NaN among them counts as a low chip and is skipped by the maximum, which is the same thing) and ONE compare.
+// A SIGNALLING NaN is not skipped: the maximum of three answers it with a quiet NaN, and whatever the other two operands
+// and the maximum so far held is lost -- a low chip that is high would go unseen and the preamble match (measured on the
+// MI355X and on the emulator: tests/test_units.py).  RAW: the taps are samples as the caller handed them over (|IQ|^2 floats,
+// MODE 1) and may hold one, so the twelve are quieted first (ADSB_QUIET: one instruction each, only for a candidate centre).
+// Every other format COMPUTES its samples, and arithmetic never returns a signalling NaN: !RAW spends nothing.
 // HALF > 0: samples per chip known at compile time -- the taps become ds_read2_b32 with immediate offsets.
-template <int HALF>
+template <int HALF, bool RAW = true>
 __device__ __forceinline__ bool chips_match(const float* tp, int half_rt) {
   const int h = HALF ? HALF : half_rt;
   float tap[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) tap[k] = tp[k * h];
+  if constexpr (RAW) {
+#pragma unroll
+    for (int k = 1; k < 16; ++k)
+      if (!((kTemplate >> k) & 1u)) tap[k] = ADSB_QUIET(tap[k]);
+  }
   const float hp = __fmul_rn(tap[0], 0.5f);                  // tap 0 IS in0[pulse_idx]; /2 is exact
   const bool hi = (tap[0] > hp) & (tap[2] > hp) & (tap[7] > hp) & (tap[9] > hp);
   float mx = adsb_fmax3(tap[1], tap[3], tap[4]);
@@ -1303,7 +1369,7 @@ __device__ __forceinline__ void detect_body(const DetectArgs& a, const int block
           bool match = true;
           // all 16 taps inside the LDS window (one LDS round trip): always, at the instantiated rates up to 8 Msps
           if ((HALF >= 1 && kMaxCentre + 15 * HALF < kWWin) || p + 15 * half < kWWin) {
-            match = chips_match<HALF>(s_x + p, half);
+            match = chips_match<HALF, MODE == 1>(s_x + p, half);
           } else {                                       // rare: taps past the window come from global memory
             const float hp = __fmul_rn(s_x[p], 0.5f);
             unsigned chips = 0;

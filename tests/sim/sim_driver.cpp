@@ -13,6 +13,13 @@ static void sim_route(int id, long long offset) {
   if ((threadIdx.x & 63u) == 0 && id >= 0 && id < 8) g_route_off[id].push_back(offset);
 }
 #define ADSB_ROUTE(id, offset) sim_route((id), (long long)(offset))
+// ADSB_MEDIAN_PATH (adsb_device.h): the turns noise_median took, one bit per adsb::MedianPath, OR-ed by lane 0 of the
+// wavefront; k_sim_median clears it before a window and reads it after
+static unsigned g_median_path = 0;
+static void sim_median_path(int id) {
+  if ((threadIdx.x & 63u) == 0 && id >= 0 && id < 32) g_median_path |= 1u << id;
+}
+#define ADSB_MEDIAN_PATH(id) sim_median_path((int)(id))
 
 #include "../../gr_adsb_amd/csrc/adsb_device.h"
 #include "../../gr_adsb_amd/csrc/adsb_plan.h"
@@ -251,4 +258,103 @@ int sim_slice(const float* in0, long long n, const long long* tag_idx, int ntags
   free(dbuf);
   return 0;
 }
+}  // extern "C"
+
+// ---- single device functions on chosen inputs (tests/test_median.py, tests/test_units.py); tests/gpu/detect_units_driver.hip
+// has the same entry points on the MI355X, so the emulator's twins of the environment (hipsim.h) and the product's versions
+// (adsb_env_hip.h) are held to one plain definition each ----------------------------------------------------------------------
+
+// one wavefront per chain: windows [chain_start[c], chain_start[c + 1]) in order, the hint carried from one to the next.
+// windows[w][128]: lane l holds samples l and l + 64, valid below nwin[w], exactly as burst_from_window forms them
+template <bool QUANT>
+__global__ void k_sim_median(const float* windows, const int* nwin, const int* chain_start, const unsigned* hint0, int n_chains,
+                             unsigned* med_out, unsigned* hint_out, unsigned* path_out) {
+  const int lane = threadIdx.x & 63, c = (int)blockIdx.x;
+  if (c >= n_chains) return;
+  unsigned hint = hint0[c];
+  for (int w = chain_start[c]; w < chain_start[c + 1]; ++w) {
+    const int n = nwin[w];
+    const bool val0 = lane < n, val1 = lane + 64 < n;
+    const float v0 = val0 ? windows[(size_t)w * 128 + lane] : 0.0f;
+    const float v1 = val1 ? windows[(size_t)w * 128 + lane + 64] : 0.0f;
+    if (lane == 0) g_median_path = 0;
+    const float med = noise_median<QUANT>(n, val0, val1, v0, v1, hint);
+    if (lane == 0) {
+      med_out[w] = __builtin_bit_cast(unsigned, med);
+      hint_out[w] = hint;
+      if (path_out) path_out[w] = g_median_path;
+    }
+  }
+}
+extern "C" void sim_noise_median(int quant, const float* windows, const int* nwin, const int* chain_start, const unsigned* hint0,
+                      int n_chains, unsigned* med_out, unsigned* hint_out, unsigned* path_out) {
+  if (n_chains <= 0) return;
+  if (quant) hipsim::launch(k_sim_median<true>, (unsigned)n_chains, 64u, windows, nwin, chain_start, hint0, n_chains, med_out, hint_out, path_out);
+  else hipsim::launch(k_sim_median<false>, (unsigned)n_chains, 64u, windows, nwin, chain_start, hint0, n_chains, med_out, hint_out, path_out);
+}
+extern "C" int sim_median_path_count() { return kMedianPathCount; }
+
+// chips_match<HALF> (half = 1, 2, 4, 10) or, for half < 0, the run-time instance with -half samples per chip, on taps[n][16]:
+// the taps are laid out at their stride, every float between them is +inf.  raw = 0: the instance for computed samples (every
+// format but |IQ|^2 floats), whose taps must hold no signalling NaN
+template <int HALF, bool RAW>
+static void chips_rows(int h, const float* taps, int n, unsigned char* out) {
+  std::vector<float> buf((size_t)15 * h + 1);
+  for (int i = 0; i < n; ++i) {
+    for (float& v : buf) v = INFINITY;
+    for (int k = 0; k < 16; ++k) buf[(size_t)k * h] = taps[(size_t)i * 16 + k];
+    out[i] = chips_match<HALF, RAW>(buf.data(), h) ? 1 : 0;
+  }
+}
+template <bool RAW>
+static int chips_by_half(int half, const float* taps, int n, unsigned char* out) {
+  if (half == 1) chips_rows<1, RAW>(1, taps, n, out);
+  else if (half == 2) chips_rows<2, RAW>(2, taps, n, out);
+  else if (half == 4) chips_rows<4, RAW>(4, taps, n, out);
+  else if (half == 10) chips_rows<10, RAW>(10, taps, n, out);
+  else if (half < 0 && half >= -64) chips_rows<0, RAW>(-half, taps, n, out);
+  else return -1;
+  return 0;
+}
+extern "C" int sim_chips_match(int half, int raw, const float* taps, int n, unsigned char* out) {
+  return raw ? chips_by_half<true>(half, taps, n, out) : chips_by_half<false>(half, taps, n, out);
+}
+
+// the wave primitives on rows of 64 lanes: one wavefront per row, every lane's result stored
+__global__ void k_sim_min_max(const unsigned* in, unsigned* mn, unsigned* mx) {
+  const size_t i = (size_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  mn[i] = adsb_wave_min_u32(in[i]);
+  mx[i] = adsb_wave_max_u32(in[i]);
+}
+__global__ void k_sim_scan(const unsigned* in, unsigned* out) {
+  const size_t i = (size_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  out[i] = adsb_wave_incl_scan(in[i]);
+}
+__global__ void k_sim_lane_up1(const unsigned* in, const unsigned* fill, unsigned* out) {
+  const size_t i = (size_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  out[i] = adsb_lane_up1(in[i], fill[blockIdx.x]);
+}
+__global__ void k_sim_above4(const unsigned* acc, const float* x, const float* thr, unsigned* out) {
+  const size_t i = (size_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  out[i] = adsb_above4(acc[i], x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3], thr[blockIdx.x]);
+}
+extern "C" void sim_wave_min_max(const unsigned* in, int rows, unsigned* mn, unsigned* mx) {
+  if (rows > 0) hipsim::launch(k_sim_min_max, (unsigned)rows, 64u, in, mn, mx);
+}
+extern "C" void sim_wave_incl_scan(const unsigned* in, int rows, unsigned* out) {
+  if (rows > 0) hipsim::launch(k_sim_scan, (unsigned)rows, 64u, in, out);
+}
+// fill[rows]: the value lane 0 of each row receives
+extern "C" void sim_lane_up1(const unsigned* in, const unsigned* fill, int rows, unsigned* out) {
+  if (rows > 0) hipsim::launch(k_sim_lane_up1, (unsigned)rows, 64u, in, fill, out);
+}
+// acc[rows][64], x[rows][64][4] (a, b, c, d: a is the highest of the four new bits), thr[rows] (wave-uniform) -> out[rows][64]
+extern "C" void sim_above4(const unsigned* acc, const float* x, const float* thr, int rows, unsigned* out) {
+  if (rows > 0) hipsim::launch(k_sim_above4, (unsigned)rows, 64u, acc, x, thr, out);
+}
+extern "C" void sim_bitrep32(const unsigned* x, int n, unsigned long long* out) {
+  for (int i = 0; i < n; ++i) out[i] = adsb_bitrep32(x[i]);
+}
+extern "C" void sim_mag2(const float* x, const float* y, long long n, float* out) {
+  for (long long i = 0; i < n; ++i) out[i] = adsb_mag2(x[i], y[i]);
 }

@@ -203,3 +203,106 @@ class long_aware_gate:
 
     def __exit__(self, *a):
         lib().sim_set_long_aware(0)
+
+
+# the turns of noise_median (adsb_device.h: enum MedianPath), logged by the emulator's ADSB_MEDIAN_PATH: bit k of a path word
+MEDIAN_PATHS = ("hint_none", "hint_exact", "hint_below", "hint_above", "hint_refused",
+                "one_16", "one_12", "one_8", "crowd_16", "crowd_12", "crowd_8", "bit_0",
+                "upper_odd", "upper_exact_again", "upper_count", "upper_next")
+
+
+class Units:
+    """Single device functions on chosen inputs, through the entry points tests/sim/sim_driver.cpp and
+    tests/gpu/detect_units_driver.hip share: Units(simlib.lib()) runs the emulator's twins of the device environment,
+    Units(<the device driver's library>) the product's versions on the GPU."""
+
+    def __init__(self, library, check=None):
+        self.lib, self.check = library, check or (lambda: None)
+        self.lib.sim_chips_match.restype = ctypes.c_int
+
+    @staticmethod
+    def _p(a):
+        return a.ctypes.data_as(ctypes.c_void_p)
+
+    def noise_median(self, quant, windows, nwin, chain_start, hint0, want_paths=True):
+        """-> (median bits, hint after each window, path word of each window or None)"""
+        windows = np.ascontiguousarray(windows, dtype=np.float32)
+        nwin, chain_start = np.ascontiguousarray(nwin, dtype=np.int32), np.ascontiguousarray(chain_start, dtype=np.int32)
+        hint0 = np.ascontiguousarray(hint0, dtype=np.uint32)
+        total = len(nwin)
+        assert windows.shape == (total, 128) and chain_start[-1] == total and len(hint0) == len(chain_start) - 1
+        med, hint = np.full(total, 0xDEADBEEF, dtype=np.uint32), np.full(total, 0xDEADBEEF, dtype=np.uint32)
+        path = np.zeros(total, dtype=np.uint32) if want_paths else None
+        self.lib.sim_noise_median(ctypes.c_int(1 if quant else 0), self._p(windows), self._p(nwin), self._p(chain_start),
+                                  self._p(hint0), ctypes.c_int(len(hint0)), self._p(med), self._p(hint),
+                                  self._p(path) if want_paths else None)
+        self.check()
+        return med, hint, path
+
+    def chips_match(self, half, taps, raw=True):
+        """half: 1, 2, 4, 10 = that instance of chips_match; -h = the run-time instance at h samples per chip.  raw=False: the
+        instance for computed samples (taps without a signalling NaN)"""
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        assert taps.ndim == 2 and taps.shape[1] == 16
+        out = np.full(len(taps), 0xEE, dtype=np.uint8)
+        rc = self.lib.sim_chips_match(ctypes.c_int(half), ctypes.c_int(1 if raw else 0), self._p(taps), ctypes.c_int(len(taps)), self._p(out))
+        self.check()
+        assert rc == 0 and set(np.unique(out)) <= {0, 1}
+        return out.astype(bool)
+
+    def wave_min_max(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        assert rows.ndim == 2 and rows.shape[1] == 64
+        mn, mx = np.full_like(rows, 0x5A5A5A5A), np.full_like(rows, 0x5A5A5A5A)
+        self.lib.sim_wave_min_max(self._p(rows), ctypes.c_int(len(rows)), self._p(mn), self._p(mx))
+        self.check()
+        return mn, mx
+
+    def wave_incl_scan(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        assert rows.ndim == 2 and rows.shape[1] == 64
+        out = np.full_like(rows, 0x5A5A5A5A)
+        self.lib.sim_wave_incl_scan(self._p(rows), ctypes.c_int(len(rows)), self._p(out))
+        self.check()
+        return out
+
+    def lane_up1(self, rows, fill):
+        rows, fill = np.ascontiguousarray(rows, dtype=np.uint32), np.ascontiguousarray(fill, dtype=np.uint32)
+        assert rows.ndim == 2 and rows.shape[1] == 64 and fill.shape == (len(rows),)
+        out = np.full_like(rows, 0x5A5A5A5A)
+        self.lib.sim_lane_up1(self._p(rows), self._p(fill), ctypes.c_int(len(rows)), self._p(out))
+        self.check()
+        return out
+
+    def above4(self, acc, x, thr):
+        """acc uint32[rows][64], x float32[rows][64][4], thr float32[rows] (one threshold per wavefront)"""
+        acc, x = np.ascontiguousarray(acc, dtype=np.uint32), np.ascontiguousarray(x, dtype=np.float32)
+        thr = np.ascontiguousarray(thr, dtype=np.float32)
+        assert acc.shape == (len(thr), 64) and x.shape == (len(thr), 64, 4)
+        out = np.full_like(acc, 0x5A5A5A5A)
+        self.lib.sim_above4(self._p(acc), self._p(x), self._p(thr), ctypes.c_int(len(thr)), self._p(out))
+        self.check()
+        return out
+
+    def bitrep32(self, x):
+        x = np.ascontiguousarray(x, dtype=np.uint32)
+        out = np.full(len(x), 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)
+        self.lib.sim_bitrep32(self._p(x), ctypes.c_int(len(x)), self._p(out))
+        self.check()
+        return out
+
+    def mag2(self, x, y):
+        x, y = np.ascontiguousarray(x, dtype=np.float32), np.ascontiguousarray(y, dtype=np.float32)
+        assert x.shape == y.shape and x.ndim == 1
+        out = np.full(len(x), 0x5A5A5A5A, dtype=np.uint32).view(np.float32)
+        self.lib.sim_mag2(self._p(x), self._p(y), ctypes.c_longlong(len(x)), self._p(out))
+        self.check()
+        return out
+
+    def convert8(self, mode, iq8, scale):
+        """body_convert<mode> of interleaved 8-bit IQ -> float32 |IQ|^2; len(iq8) % 16 == 0"""
+        raw = np.ascontiguousarray(iq8).view(np.uint32)
+        out = np.full(2 * len(raw), 0x5A5A5A5A, dtype=np.uint32).view(np.float32)
+        self.lib.sim_convert8(ctypes.c_int(mode), self._p(raw), ctypes.c_longlong(len(raw)), ctypes.c_float(scale), self._p(out))
+        self.check()
+        return out

@@ -102,7 +102,9 @@ def test_int16_edges_and_random(scale):
     assert_bits(O.mag2_iq16(q, scale), ref_iq16(q, scale), "int16, scale %r" % scale)
 
 
-def test_complex64_subnormal_and_near_overflow():
+def complex64_pairs():
+    """(re, im) float32: every sign and pairing of magnitudes from the smallest subnormal to the largest finite value, and
+    65536 random pairs over the whole exponent range"""
     rng = np.random.default_rng(64)
     mags = [0.0, 2.0 ** -149, 2.0 ** -140, 2.0 ** -126, 2.0 ** -75, 2.0 ** -63, 2.0 ** -62, 1.0, 2.0 ** 63, 1.8446743e19,
             2.0 ** 64, 3.4028235e38]
@@ -110,6 +112,11 @@ def test_complex64_subnormal_and_near_overflow():
     a, b = np.meshgrid(v, v)
     r = np.concatenate([a.ravel(), np.ldexp(rng.random(1 << 16), rng.integers(-150, 128, 1 << 16)).astype(np.float32)])
     i = np.concatenate([b.ravel(), np.ldexp(rng.random(1 << 16), rng.integers(-150, 128, 1 << 16)).astype(np.float32)])
+    return r, i
+
+
+def test_complex64_subnormal_and_near_overflow():
+    r, i = complex64_pairs()
     iq = np.empty(len(r), np.complex64)
     iq.real, iq.imag = r, i
     with np.errstate(all="ignore"):
