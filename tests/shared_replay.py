@@ -16,6 +16,14 @@ def time_order(ts):
     return np.array(sorted(range(len(ts)), key=lambda t: (ts[t], t)), np.int64)
 
 
+def time_key_np(ts):
+    """The monotone map k_shared_keys and the de-duplication step state (time_key), in NumPy: ascending keys <=> ascending
+    doubles -- a set sign bit flips every bit, a clear one sets it -- and -0.0 takes +0.0's key."""
+    b = np.ascontiguousarray(ts, dtype=np.float64).view(np.uint64).copy()
+    b[b == np.uint64(1 << 63)] = 0
+    return np.where((b >> np.uint64(63)) != 0, ~b, b | np.uint64(1 << 63))
+
+
 class Replay:
     """ONE decode_replay.Decoder and ONE aircraft_replay table fed every call in the order (ts, t); results at list positions,
     with plane_dict's last_seen kept beside the planes."""

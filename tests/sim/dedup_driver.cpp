@@ -152,4 +152,79 @@ int sim_dedup_call(void* h, const unsigned char* bits14, const long long* offset
   memcpy(dup_out, dup.p(), (size_t)n * sizeof(int));
   return 0;
 }
+
+// The four k_dedup_* kernels ALONE, in fleet_step's order, on stated arrays (tests/gpu/dedup_device_driver.hip is this entry on
+// the device).  In: the call's records in time order sorted_recs[n][4] with sorted_ts[n] and order[n] (a permutation: place ->
+// list position), first[n_items + 1] and item_stream[n_items]; the carry's words carry[nc][4]; recs[n][4] / rows[n][9]: the
+// delivered records and rows k_dedup_mark works on, at list positions.  Out: ent_out[n][4] (k_dedup_entries), dup_out[n] and
+// sorted_out[n][4] (the time-ordered records behind k_dedup_find), merged_out[nc + n][4] and state_out (a State, 16 bytes:
+// k_dedup_merge), recs_out[n][4] and rows_out[n][9] (k_dedup_mark).  n == 0: nothing is run, as in the call.
+// 0; -1: a guard byte, or a byte of order[], first[] or item_stream[], was overwritten; -5: a bad argument; -6: the carry was
+// written to, or the cut k_dedup_merge states does not add up.
+int sim_dedup_step(const unsigned long long* sorted_recs, const double* sorted_ts, const int* order, int n, const int* first,
+                   const int* item_stream, int n_items, const unsigned long long* carry_in, int nc, double window, double horizon, int grid,
+                   const unsigned long long* recs_in, const unsigned long long* rows_in, unsigned long long* ent_out, int* dup_out,
+                   unsigned long long* sorted_out, unsigned long long* merged_out, void* state_out, unsigned long long* recs_out,
+                   unsigned long long* rows_out) {
+  if (n < 0 || nc < 0 || grid < 1) return -5;
+  if (n == 0) return 0;
+  if (n_items <= 0 || first[0] != 0 || first[n_items] != n || !(window >= 0) || !(horizon >= 0)) return -5;
+  for (int i = 0; i < n_items; ++i)
+    if (first[i] > first[i + 1]) return -5;
+  {
+    std::vector<char> hit((size_t)n, 0);
+    for (int k = 0; k < n; ++k) {
+      const int t = order[k];
+      if (t < 0 || t >= n || hit[(size_t)t]) return -5;
+      hit[(size_t)t] = 1;
+    }
+  }
+  const size_t rw = dd::kRecWords, ew = dd::kEntWords, ww = dd::kRowWords;
+  Guarded<unsigned long long> srecs((size_t)n * rw, 0), carry((size_t)nc * ew, 0), ent((size_t)n * ew, 0xA5), merged((size_t)(nc + n) * ew, 0xA5),
+      recs((size_t)n * rw, 0), rows((size_t)n * ww, 0);
+  Guarded<double> sts((size_t)n, 0);
+  Guarded<int> ord((size_t)n, 0), fst((size_t)n_items + 1, 0), streams((size_t)n_items, 0), dup((size_t)n, 0xA5);
+  Guarded<dd::State> state(1, 0xA5);
+  memcpy(srecs.p(), sorted_recs, (size_t)n * rw * 8);
+  memcpy(sts.p(), sorted_ts, (size_t)n * 8);
+  memcpy(ord.p(), order, (size_t)n * 4);
+  memcpy(fst.p(), first, ((size_t)n_items + 1) * 4);
+  memcpy(streams.p(), item_stream, (size_t)n_items * 4);
+  if (nc) memcpy(carry.p(), carry_in, (size_t)nc * ew * 8);
+  memcpy(recs.p(), recs_in, (size_t)n * rw * 8);
+  memcpy(rows.p(), rows_in, (size_t)n * ww * 8);
+  const auto all_ok = [&] {
+    return srecs.ok() && carry.ok() && ent.ok() && merged.ok() && recs.ok() && rows.ok() && sts.ok() && ord.ok() && fst.ok() && streams.ok() &&
+           dup.ok() && state.ok() && memcmp(ord.p(), order, (size_t)n * 4) == 0 && memcmp(fst.p(), first, ((size_t)n_items + 1) * 4) == 0 &&
+           memcmp(streams.p(), item_stream, (size_t)n_items * 4) == 0;
+  };
+  const auto carry_same = [&] { return nc == 0 || memcmp(carry.p(), carry_in, (size_t)nc * ew * 8) == 0; };
+
+  hipsim::launch(dd::k_dedup_entries, (unsigned)grid, (unsigned)dd::kThreads, (const unsigned long long*)srecs.p(), (const double*)sts.p(),
+                 (const int*)ord.p(), n, (const int*)fst.p(), (const int*)streams.p(), n_items, ent.p());
+  if (!all_ok()) return -1;
+  if (memcmp(srecs.p(), sorted_recs, (size_t)n * rw * 8) != 0) return -1;      // k_dedup_entries only reads the records
+  memcpy(ent_out, ent.p(), (size_t)n * ew * 8);
+  hipsim::launch(dd::k_dedup_find, (unsigned)grid, (unsigned)dd::kThreads, (const unsigned long long*)ent.p(), n,
+                 (const unsigned long long*)carry.p(), nc, window, (const int*)ord.p(), srecs.p(), dup.p());
+  if (!all_ok()) return -1;
+  if (!carry_same()) return -6;
+  if (memcmp(ent.p(), ent_out, (size_t)n * ew * 8) != 0) return -1;            // ... and k_dedup_find only reads the entries
+  memcpy(dup_out, dup.p(), (size_t)n * 4);
+  memcpy(sorted_out, srecs.p(), (size_t)n * rw * 8);
+  hipsim::launch(dd::k_dedup_merge, (unsigned)grid, (unsigned)dd::kThreads, (const unsigned long long*)carry.p(), nc,
+                 (const unsigned long long*)ent.p(), n, horizon, merged.p(), state.p());
+  if (!all_ok()) return -1;
+  if (!carry_same()) return -6;
+  if (memcmp(ent.p(), ent_out, (size_t)n * ew * 8) != 0) return -1;
+  memcpy(merged_out, merged.p(), (size_t)(nc + n) * ew * 8);
+  memcpy(state_out, state.p(), sizeof(dd::State));
+  hipsim::launch(dd::k_dedup_mark, (unsigned)grid, (unsigned)dd::kThreads, (const int*)dup.p(), n, recs.p(), rows.p());
+  if (!all_ok() || memcmp(dup.p(), dup_out, (size_t)n * 4) != 0) return -1;
+  memcpy(recs_out, recs.p(), (size_t)n * rw * 8);
+  memcpy(rows_out, rows.p(), (size_t)n * ww * 8);
+  const dd::State s = state.p()[0];
+  if (s.off < 0 || s.cnt < 1 || s.off + s.cnt != nc + n) return -6;
+  return 0;
+}
 }

@@ -2,10 +2,15 @@
 kernels (tests/sim/dedup_driver.cpp: adsb_dedup_device.h's four kernels inside the shared decoder's call, the host's rule for
 the carry restated) against tests/golden/g_dedup.npz -- ONE unmodified reference decoder fed the publication sequence without
 the duplicates (tools/make_golden_dedup.py) -- and against the plain-Python rule of tests/dedup_replay.py; the scan across
-the wavefront, workgroup and LDS-tile seams; the carry's edges; the new translation unit's build facts.
+the wavefront, workgroup and LDS-tile seams; the carry's edges; the four kernels alone (sim_dedup_step) against a plain
+statement of every output byte; the new translation unit's build facts.
 
 What a green run here does NOT cover: the host's own branch of fleet_step, the entry points and their refusals, and
-adsb_stream_reset beside the carry -- tests/test_gpu_dedup.py."""
+adsb_stream_reset beside the carry -- tests/test_gpu_dedup.py; and everything on the device's side of these seams: what hipcc
+makes of k_dedup_find's LDS tiles and its __syncthreads() inside block-uniform loops, the real launchers' grid sizing (the
+launches here are the driver's own) and the kernels' second grid-stride round under them, which needs more than 524 288
+records -- tests/test_gpu_dedup_device.py runs this file's section "the kernels alone", unchanged, on the MI355X through
+tests/gpu/dedup_device_driver.hip, and adds one step of 526 500 records built by period (periodic_step)."""
 import ctypes
 import json
 import os
@@ -20,6 +25,7 @@ import decode_streams as S
 import dedup_replay as DR
 import shared_replay as SR
 import test_decode as TD
+import test_mlat as TM
 import test_shared_decode as TS
 from gr_adsb_amd import _native as N
 
@@ -467,6 +473,513 @@ def test_one_stream_is_the_shared_decoder(sim):
         assert (dup == -1).all() and fl.tobytes() == pfl.tobytes() and r.tobytes() == pr.tobytes() and np.array_equal(order, porder)
     assert f.stats()[0] == 0 and int(sim.sim_shared_digest(f.fleet)) == plain.digest()
     f.close(), plain.close()
+
+
+# ---- the kernels alone -----------------------------------------------------------------------------------------------------
+# sim_dedup_step runs k_dedup_entries, _find, _merge and _mark on stated arrays, and every byte it returns has a plain statement
+# here that never passes through the code under test: the entries are test_mlat.carry_words_numpy's words, dup[] is
+# dedup_replay.find_duplicates', the merged buffer is NumPy's stable argsort over time_key, the cut is one float64 expression.
+# The tests of this section (ALONE names them) use nothing of `sim` but sim_dedup_step: tests/test_gpu_dedup_device.py imports
+# them unchanged and runs them on the device.  Each case first asserts, from the plain rule alone, that it reaches what it is
+# meant to reach (Step.ranges: the three bounds k_dedup_find's workgroups share).
+STATE_DTYPE = np.dtype([("off", "<i4"), ("cnt", "<i4"), ("hi", "<f8")])
+W_DEMOD, W_LONG = np.uint64(N.BURST_DEMOD << 48), np.uint64(N.BURST_LONG << 48)
+WG = 256                      # places per workgroup of k_dedup_find
+GRIDS = (1, 3)
+
+
+def words_of(ts, bits, mk, stream):
+    if len(ts) == 0:
+        return np.zeros((0, 4), np.uint64)
+    return TM.carry_words_numpy(np.ascontiguousarray(ts, dtype=np.float64), np.ascontiguousarray(bits, dtype=np.uint8), np.asarray(mk, np.int32),
+                                np.asarray(stream, np.int32))
+
+
+def merge_and_cut(carry_words, ent, horizon):
+    """-> (the merged buffer, the State): the stable merge of carry then call by time_key, hi the later of the two lists' last
+    timestamps, off the count of entries with ts < hi - horizon in float64"""
+    both = np.concatenate([carry_words, ent])
+    merged = both[np.argsort(SR.time_key_np(both[:, 0].view(np.float64)), kind="stable")]
+    ts = both[:, 0].view(np.float64)
+    nc = len(carry_words)
+    hi = ts[-1] if nc == 0 or ts[-1] >= ts[nc - 1] else ts[nc - 1]
+    state = np.zeros(1, STATE_DTYPE)
+    off = int((ts < hi - np.float64(horizon)).sum())
+    state["off"], state["cnt"], state["hi"] = off, len(both) - off, hi
+    return merged, state
+
+
+def random_words(rng, shape):
+    return rng.integers(0, 1 << 63, shape).astype(np.uint64) * np.uint64(2) + rng.integers(0, 2, shape).astype(np.uint64)
+
+
+def records_of(rng, bits, dem, long_):
+    """[n][4] record words: the PDU in words 2 and 3, ADSB_BURST_DEMOD and ADSB_BURST_LONG as stated, every other bit random"""
+    n = len(bits)
+    recs = random_words(rng, (n, 4))
+    b16 = np.zeros((n, 16), np.uint8)
+    b16[:, :14] = bits
+    w = b16.view("<u8").reshape(n, 2)
+    flags = recs[:, 3] & ~(np.uint64(0xFFFFFFFFFFFF) | W_DEMOD | W_LONG)
+    recs[:, 2] = w[:, 0]
+    recs[:, 3] = w[:, 1] | flags | np.where(dem, W_DEMOD, np.uint64(0)) | np.where(long_, W_LONG, np.uint64(0))
+    return recs
+
+
+class Step:
+    """One sim_dedup_step: hearings (bits[m][14], ts[m], stream[m], dem[m], long[m]) of which those named by in_call are the
+    call's list -- in the arrays' order, a stream's hearings contiguous -- and the others the carry, in time order.  Builds the
+    entry's arguments and states every output."""
+
+    def __init__(self, bits, ts, stream, in_call, window=0.002, horizon=1.0, dem=None, long_=None, extra_items=(), seed=1):
+        rng = np.random.default_rng(seed)
+        bits, ts, stream = np.asarray(bits, np.uint8), np.asarray(ts, np.float64), np.asarray(stream, np.int32)
+        m = len(bits)
+        dem = np.ones(m, bool) if dem is None else np.asarray(dem, bool)
+        long_ = (bits[:, 0] >> 3) >= 16 if long_ is None else np.asarray(long_, bool)
+        mk = np.where(dem, np.where(long_, 2, 1), 0).astype(np.int32)
+        pay = [None if mk[i] == 0 else (112, bits[i].tobytes()) if mk[i] == 2 else (56, bits[i, :7].tobytes()) for i in range(m)]
+        call = np.zeros(m, bool)
+        call[in_call] = True
+        ci, ki = np.flatnonzero(call), np.flatnonzero(~call)
+        ki = ki[np.argsort(SR.time_key_np(ts[ki]), kind="stable")]
+        self.window, self.horizon, self.n, self.nc = float(window), float(horizon), len(ci), len(ki)
+        n = self.n
+        assert n > 0
+        # the carry
+        self.carry_ts = ts[ki]
+        self.carry = words_of(ts[ki], bits[ki], mk[ki], stream[ki])
+        carry_list = [(float(ts[i]), pay[i], int(stream[i])) for i in ki]
+        # the call's list, its items and its time order
+        self.item_stream, self.first = call_list(stream[ci], n, extra_items)
+        self.ts = ts[ci]
+        self.exp_dup, order = DR.find_duplicates([pay[i] for i in ci], self.ts, stream[ci], carry_list, self.window)
+        self.order = np.asarray(order, np.int32)
+        assert np.array_equal(self.order, SR.time_order(self.ts))
+        self.sorted_recs = records_of(rng, bits[ci], dem[ci], long_[ci])[self.order]
+        self.sorted_ts = np.ascontiguousarray(self.ts[self.order])
+        o = self.order
+        self.exp_ent = words_of(self.sorted_ts, bits[ci][o], mk[ci][o], stream[ci][o])
+        self.state_the_rest(rng)
+
+    @classmethod
+    def stated(cls, sorted_recs, sorted_ts, order, first, item_stream, carry, window, horizon, exp_ent, exp_dup, seed=1):
+        """A step whose arguments, entries and dup[] the caller states (a case too large for __init__'s Python lists)"""
+        self = cls.__new__(cls)
+        self.window, self.horizon, self.n, self.nc = float(window), float(horizon), len(sorted_ts), len(carry)
+        self.sorted_recs, self.sorted_ts, self.order = np.ascontiguousarray(sorted_recs), np.ascontiguousarray(sorted_ts), np.asarray(order, np.int32)
+        self.first, self.item_stream = np.asarray(first, np.int32), np.asarray(item_stream, np.int32)
+        self.carry, self.carry_ts = carry, carry[:, 0].copy().view(np.float64)
+        self.exp_ent, self.exp_dup = exp_ent, np.asarray(exp_dup, np.int32)
+        self.state_the_rest(np.random.default_rng(seed))
+        return self
+
+    def state_the_rest(self, rng):
+        """from the arguments, the entries and dup[]: the time-ordered records behind k_dedup_find, the merged buffer and the
+        cut, and delivered records and rows of random words with what k_dedup_mark must leave of them"""
+        n, o = self.n, self.order
+        self.exp_sorted = self.sorted_recs.copy()
+        self.exp_sorted[self.exp_dup[o] != -1, 3] &= ~W_DEMOD
+        self.exp_merged, self.exp_state = merge_and_cut(self.carry, self.exp_ent, self.horizon)
+        self.recs, self.rows = random_words(rng, (n, 4)), random_words(rng, (n, 9))
+        self.recs[:, 3] &= ~W_DEMOD                                      # as the decode step leaves a duplicate's: k_dedup_mark sets it
+        marked = self.exp_dup != -1
+        self.exp_recs, self.exp_rows = self.recs.copy(), self.rows.copy()
+        self.exp_recs[marked, 3] |= W_DEMOD
+        self.exp_rows[marked, 0] = (self.exp_rows[marked, 0] & ~np.uint64(0xFF)) | np.uint64(N.DEC_DUPLICATE)
+
+    def place_of(self, t):
+        """the place in the time order of list position t"""
+        return int(np.flatnonzero(self.order == t)[0])
+
+    def ranges(self, place):
+        """(base, last, q_lo, c_lo, c_hi) of the workgroup that holds `place`, from the rule alone: q_lo the first place in
+        front of base within the window of base's timestamp, [c_lo, c_hi) the carry entries that are neither in front of
+        base's window nor behind last's."""
+        base = place // WG * WG
+        last = min(base + WG, self.n) - 1
+        t0, t1 = self.sorted_ts[base], self.sorted_ts[last]
+        near = np.flatnonzero(np.abs(t0 - self.sorted_ts[:base]) <= self.window)
+        q_lo = int(near[0]) if len(near) else base
+        c = self.carry_ts
+        c_lo = int(((c < t0) & ~(np.abs(t0 - c) <= self.window)).sum())
+        c_hi = int(((c <= t1) | (np.abs(t1 - c) <= self.window)).sum())
+        return base, last, q_lo, c_lo, c_hi
+
+    def carry_index(self, ts, stream):
+        """the carry's entry with that timestamp and stream"""
+        st = ((self.carry[:, 3] >> np.uint64(32)) & np.uint64(0xFFFFFF)).astype(np.int64)
+        hit = np.flatnonzero((self.carry_ts == ts) & (st == stream))
+        assert len(hit) == 1
+        return int(hit[0])
+
+    def run(self, sim, grid, rc=0):
+        n, nc = self.n, self.nc
+        out = dict(ent=np.zeros((n, 4), np.uint64), dup=np.zeros(n, np.int32), sorted=np.zeros((n, 4), np.uint64),
+                   merged=np.zeros((nc + n, 4), np.uint64), state=np.zeros(1, STATE_DTYPE), recs=np.zeros((n, 4), np.uint64),
+                   rows=np.zeros((n, 9), np.uint64))
+        carry = np.ascontiguousarray(self.carry) if nc else np.zeros((1, 4), np.uint64)
+        ins = [np.ascontiguousarray(x) for x in (self.sorted_recs, self.sorted_ts, self.order, self.first, self.item_stream, carry, self.recs,
+                                                 self.rows)]
+        p = [x.ctypes.data_as(vp) for x in ins]
+        got = sim.sim_dedup_step(p[0], p[1], p[2], ctypes.c_int(n), p[3], p[4], ctypes.c_int(len(self.item_stream)), p[5], ctypes.c_int(nc),
+                                 ctypes.c_double(self.window), ctypes.c_double(self.horizon), ctypes.c_int(grid), p[6], p[7],
+                                 *[out[k].ctypes.data_as(vp) for k in ("ent", "dup", "sorted", "merged", "state", "recs", "rows")])
+        assert got == rc, "guard or read-only input (-1), argument (-5), carry or cut (-6), a HIP status (<= -1000): %d" % got
+        return out
+
+    def check(self, sim, grids=GRIDS):
+        """every output of the entry against its statement, as bytes, with each grid"""
+        for grid in grids:
+            got = self.run(sim, grid)
+            assert got["ent"].tobytes() == self.exp_ent.tobytes(), ("entries", grid, np.flatnonzero((got["ent"] != self.exp_ent).any(1))[:5])
+            bad = np.flatnonzero(got["dup"] != self.exp_dup)
+            assert got["dup"].tobytes() == self.exp_dup.tobytes(), ("dup", grid, bad[:5], got["dup"][bad[:5]], self.exp_dup[bad[:5]])
+            assert got["sorted"].tobytes() == self.exp_sorted.tobytes(), ("the time-ordered records", grid)
+            assert got["merged"].tobytes() == self.exp_merged.tobytes(), ("merged", grid, np.flatnonzero((got["merged"] != self.exp_merged).any(1))[:5])
+            assert got["state"].tobytes() == self.exp_state.tobytes(), ("state", grid, got["state"], self.exp_state)
+            assert got["recs"].tobytes() == self.exp_recs.tobytes(), ("the marked records", grid)
+            assert got["rows"].tobytes() == self.exp_rows.tobytes(), ("the marked rows", grid)
+        return self
+
+
+def ts_of(offset):
+    """k_shared_keys' expression with every stream's start at T0"""
+    return T0 + np.asarray(offset, np.int64).astype(np.float64) / FS
+
+
+@pytest.mark.parametrize("n", [2, 65, 257, TILE + 1])
+def test_alone_one_reply_heard_by_many_streams(sim, n):
+    """In one call: the last hearing's workgroup stages every hearing in front of it.  With the first hearing in the carry:
+    every hearing of the call is -2.  With n - 1 hearings in the carry and the earliest in time arriving last: the carry range
+    is all of them, and all of them lie BEHIND the call's one record."""
+    b, off, s = one_reply(n)
+    w = Step(b, ts_of(off), s, np.arange(n))
+    base, last, q_lo, _, _ = w.ranges(n - 1)
+    assert last == n - 1 and q_lo == 0 and w.exp_dup[0] == -1 and (w.exp_dup[1:] == 0).all()
+    w.check(sim)
+    rev = np.arange(1, n)[::-1]                                        # the list in descending stream order: not the time order
+    idx = np.concatenate([[0], rev])
+    w = Step(b[idx], ts_of(off[idx]), s[idx], np.arange(1, n))
+    assert (w.exp_dup == -2).all() and np.array_equal(w.order, np.arange(n - 1)[::-1]) and w.ranges(0)[3:] == (0, 1)
+    w.check(sim)
+    w = Step(b, ts_of(off), s, [0])
+    assert w.exp_dup.tolist() == [-2] and w.ranges(0)[3:] == (0, n - 1) and (w.carry_ts > w.ts[0]).all()
+    w.check(sim)
+
+
+@pytest.mark.parametrize("front,between", [(TILE + 76, 5), (TILE + 300, 260), (2 * TILE + 9, 1)])
+def test_alone_the_earliest_match_lies_in_a_later_partial_tile(sim, front, between):
+    """seam_world in one call -- B's match A is staged at least one tile into the range, in the last, partial tile, and for
+    (TILE + 300, 260) B's workgroup starts behind A -- and against the carry, where the same holds of the carry's range.  In
+    both, the decoy on B's own stream lies in the first tile and must not count: where it is the only candidate, B is new."""
+    b, off, s, (decoy, a, a2, bb) = seam_world(front, between)
+    n = len(b)
+    ts = ts_of(off)
+    w = Step(b, ts, s, np.arange(n))
+    base, last, q_lo, _, _ = w.ranges(w.place_of(bb))
+    pa, pd = w.place_of(a), w.place_of(decoy)
+    assert q_lo == 0 and pd - q_lo < TILE <= pa - q_lo and (pa - q_lo) // TILE == (last - 1 - q_lo) // TILE and (last - q_lo) % TILE != 0
+    assert base > pa or (front, between) != (TILE + 300, 260)           # ... there B's workgroup starts behind A
+    assert w.exp_dup[decoy] == -1 and w.exp_dup[a] == decoy and w.exp_dup[a2] == decoy and w.exp_dup[bb] == a
+    w.check(sim)
+    # against the carry: everything but B is there; the call is B and a hearing earlier than all of the carry
+    hb, hts, hs = np.concatenate([b, [IDENT]]), np.concatenate([ts, ts_of([900])]), np.concatenate([s, [4]]).astype(np.int32)
+    w = Step(hb, hts, hs, [bb, n])
+    assert w.exp_dup.tolist() == [-2, -2]
+    w.check(sim)
+    # ... the carry's only hearing on another stream is A (A2 is on B's own now): found one tile into [c_lo, c_hi) or further
+    s2 = s.copy()
+    s2[a2] = 1
+    w = Step(b, ts, s2, [bb])
+    _, _, _, c_lo, c_hi = w.ranges(0)
+    ia, idec = w.carry_index(ts[a], 0), w.carry_index(ts[decoy], 1)
+    assert c_lo == 0 and c_hi == n - 1 and idec - c_lo < TILE <= ia - c_lo and (ia - c_lo) // TILE == (c_hi - 1 - c_lo) // TILE and (c_hi - c_lo) % TILE
+    assert w.exp_dup.tolist() == [-2]
+    w.check(sim)
+    # ... and without A the decoy and A2, both on B's own stream, are all there is: B is new
+    keep = np.delete(np.arange(n), a)
+    w = Step(b[keep], ts[keep], s2[keep], [int(np.flatnonzero(keep == bb)[0])])
+    assert w.exp_dup.tolist() == [-1] and w.nc == n - 2
+    w.check(sim)
+    # ... nor does the decoy count in the call
+    keep = keep[np.argsort(s2[keep], kind="stable")]                   # the list: grouped by stream again
+    w = Step(b[keep], ts[keep], s2[keep], np.arange(n - 1))
+    assert (w.exp_dup == -1).all() and w.ranges(n - 2)[2] == 0
+    w.check(sim)
+
+
+def test_alone_more_than_two_tiles_of_hearings(sim):
+    """2 * TILE + 10 hearings on stream 1, one on stream 0 behind them, forty more on stream 1: the forty's only match is staged
+    more than two tiles into their workgroup's range."""
+    k = 2 * TILE + 10
+    n = k + 41
+    who = np.ones(n, np.int32)
+    who[k] = 0
+    order = np.argsort(who, kind="stable")
+    w = Step(np.tile(IDENT, (n, 1)), ts_of(1000 + np.arange(n))[order], who[order], np.arange(n))
+    base, last, q_lo, _, _ = w.ranges(n - 1)
+    assert q_lo == 0 and w.place_of(0) == k and k - q_lo >= 2 * TILE and last == n - 1
+    assert w.exp_dup[0] == 1 and (w.exp_dup[1:k + 1] == -1).all() and (w.exp_dup[k + 1:] == 0).all()
+    w.check(sim)
+
+
+def test_alone_a_carry_range_on_both_sides_in_time(sim):
+    """c_lo, c_hi and the carry's tile loop together: 300 records of the call (two workgroups) with a carry of 300 entries
+    out of reach in front, 1200 within the window in front of the workgroup's first place, 1300 within it behind its last, and
+    200 out of reach behind.  B (stream 1) lies in the second workgroup; its only match, A on stream 0, is among the late
+    entries, in the range's last, partial tile; a decoy on stream 1 lies in the first.  A second reply is heard twice in the
+    call, at places 100 and 290: the match lies in [q_lo, c_lo), so the call's tile loop must start at q_lo, not at c_lo."""
+    early, front, back, late, n = 300, 1200, 1300, 200, 300
+    off = np.concatenate([np.arange(early), 10000 - front + np.arange(front), 10000 + n + np.arange(back), 20000 + np.arange(late),
+                          10000 + np.arange(n)])
+    m = len(off)
+    nc = m - n
+    b = fillers(m, 77)
+    s = np.full(m, 2, np.int32)
+    i_decoy, i_a, i_b = early + 5, early + front + 1000, nc + 280
+    for i, st_ in ((i_decoy, 1), (i_a, 0), (i_b, 1)):
+        b[i], s[i] = IDENT, st_
+    s[nc:i_b] = 3                                                      # the list: streams 3, 1, 2
+    b[nc + 100] = b[nc + 290] = fillers(1, 5)[0]
+    ts = ts_of(off)
+    w = Step(b, ts, s, np.arange(nc, m))
+    place = w.place_of(280)
+    base, last, q_lo, c_lo, c_hi = w.ranges(place)
+    assert (base, last) == (WG, n - 1) and place == 280
+    c = w.carry_ts
+    assert c_lo == early and c_hi == nc - late and ((c[c_lo:c_hi] < w.sorted_ts[base]).sum(), (c[c_lo:c_hi] > w.sorted_ts[last]).sum()) == (front, back)
+    assert front > TILE and back > TILE
+    ia, idec = w.carry_index(ts[i_a], 0), w.carry_index(ts[i_decoy], 1)
+    assert idec - c_lo < TILE and (ia - c_lo) // TILE == (c_hi - 1 - c_lo) // TILE == 2 and (c_hi - c_lo) % TILE != 0
+    assert w.ranges(0)[3:] == (early, nc - late) and (w.exp_dup != -1).sum() == 2 and w.exp_dup[280] == -2
+    assert w.exp_dup[290] == 100 and q_lo <= 100 < c_lo and s[nc + 100] != s[nc + 290]
+    w.check(sim)
+    # the same carry without A: nothing matches
+    keep = np.delete(np.arange(m), i_a)
+    w = Step(b[keep], ts[keep], s[keep], np.arange(nc - 1, m - 1))
+    assert np.flatnonzero(w.exp_dup != -1).tolist() == [290]
+    w.check(sim)
+
+
+def test_alone_all_timestamps_equal(sim):
+    """Bit-equal timestamps, 300 in the call and 300 in the carry, window 0.002 and window 0: the list order is the time order,
+    and on equal keys the merge puts the carry first."""
+    n = 300
+    b, _, s = one_reply(2 * n)
+    ts = np.full(2 * n, T0 + 5000 / FS)
+    for window in (0.002, 0.0):
+        w = Step(b[:n], ts[:n], s[:n], np.arange(n), window=window)
+        assert np.array_equal(w.order, np.arange(n)) and w.exp_dup[0] == -1 and (w.exp_dup[1:] == 0).all() and w.ranges(n - 1)[2] == 0
+        w.check(sim)
+        w = Step(b, ts, s, np.arange(n, 2 * n), window=window)
+        assert (w.exp_dup == -2).all() and w.ranges(n - 1)[3:] == (0, n)
+        assert w.exp_merged.tobytes() == np.concatenate([w.carry, w.exp_ent]).tobytes()
+        w.check(sim)
+
+
+def test_alone_window_zero(sim):
+    """window = 0: one sample apart is another transmission, in the call and against the carry."""
+    b, _, s = one_reply(6)
+    off = np.array([5000, 5000, 5001, 5001, 5001, 5002])
+    w = Step(b[:4], ts_of(off[:4]), s[:4], np.arange(4), window=0.0)
+    assert w.exp_dup.tolist() == [-1, 0, -1, 2]
+    w.check(sim)
+    w = Step(b, ts_of(off), s, [4, 5], window=0.0)                     # stream 4 at 5001: streams 2 and 3 were there; stream 5 at 5002: nobody
+    assert w.exp_dup.tolist() == [-2, -1] and w.ranges(0)[3:] == (2, 4)
+    w.check(sim)
+
+
+def test_alone_records_with_marker_zero(sim):
+    """A record without ADSB_BURST_DEMOD takes no part: in the call it is no match and no duplicate, in the carry it is no
+    match, and a call where nobody takes part marks nothing and still merges and moves hi."""
+    b, off, s = one_reply(6)
+    ts = ts_of(off)
+    w = Step(b, ts, s, np.arange(6), dem=[0, 1, 0, 1, 1, 0])
+    assert w.exp_dup.tolist() == [-1, -1, -1, 1, 1, -1] and (w.exp_ent[[0, 2, 5], 3] >> np.uint64(56) == 0).all()
+    assert not w.exp_ent[[0, 2, 5], 1:3].any()
+    w.check(sim)
+    w = Step(b, ts, s, [3, 4, 5], dem=[0, 0, 0, 1, 1, 1])
+    assert w.exp_dup.tolist() == [-1, 0, 0] and w.ranges(0)[3:] == (0, 3)
+    w.check(sim)
+    w = Step(b, ts, s, [3, 4, 5], dem=[1, 1, 1, 0, 0, 0])
+    assert (w.exp_dup == -1).all() and w.exp_state["hi"][0] == ts[5] and w.exp_state["cnt"][0] == 6
+    w.check(sim)
+    # short and long with the same first 56 bits, and a short reply's bytes 7 .. 13, which are not payload
+    b2 = np.tile(IDENT, (4, 1))
+    b2[1, 7:] ^= 0xFF
+    w = Step(b2, ts[:4], s[:4], np.arange(4), long_=[0, 0, 1, 1])
+    assert w.exp_dup.tolist() == [-1, 0, -1, 2]
+    w.check(sim)
+
+
+def test_alone_the_merge_and_the_cut(sim):
+    """k_dedup_merge's edges.  Ties on both sides (the carry first); nc = 0; n = 1; a call wholly behind hi - horizon; an entry
+    at exactly hi - horizon is kept and the double below it is dropped; hi from the carry."""
+    b, _, s = one_reply(12)
+    # ties on both sides: the carry and the call both hold several entries at 4000 and at 6000
+    off = np.array([4000, 6000, 4000, 6000, 6000, 4000, 4000, 6000, 5000, 4000, 6000, 6000])
+    w = Step(b, ts_of(off), s, np.arange(6, 12))
+    st = ((w.exp_merged[:, 3] >> np.uint64(32)) & np.uint64(0xFFFFFF)).tolist()
+    assert st == [0, 2, 5, 6, 9, 8, 1, 3, 4, 7, 10, 11]              # per timestamp: the carry's in its order, then the call's in list order
+    w.check(sim)
+    # nc = 0, and n = 1 with and without a carry
+    w = Step(b[:5], ts_of(off[:5]), s[:5], np.arange(5))
+    assert w.nc == 0 and w.exp_state.tolist() == [(0, 5, T0 + 6000 / FS)]
+    w.check(sim)
+    Step(b[:1], ts_of(off[:1]), s[:1], [0]).check(sim)
+    Step(b[:6], ts_of(off[:6]), s[:6], [2]).check(sim)
+    # the cut, horizon 1: hi = T0 + 3 is the call's last; T0 + 2 is kept, the double below it is not
+    edge = T0 + 2.0
+    ts = np.array([T0, np.nextafter(edge, -np.inf), edge, T0 + 2.5, T0 + 0.5, np.nextafter(edge, -np.inf), edge, T0 + 3.0])
+    w = Step(b[:8], ts, s[:8], np.arange(4, 8))
+    assert T0 + 3.0 - 1.0 == edge and w.exp_state.tolist() == [(4, 4, T0 + 3.0)]
+    assert (w.exp_merged[:4, 0].view(np.float64) < edge).all() and (w.exp_merged[4:, 0].view(np.float64) >= edge).all()
+    w.check(sim)
+    # a call wholly behind hi - horizon, hi the carry's: the cut takes all of it and the old carry's head
+    ts = np.array([T0 + 1.5, T0 + 2.5, T0 + 4.0, T0 + 1.0, T0 + 2.0, T0 + 2.0 + 1 / FS])
+    w = Step(b[:6], ts, s[:6], [3, 4, 5])
+    assert w.exp_state.tolist() == [(5, 1, T0 + 4.0)] and w.exp_dup.tolist() == [-1, -1, 1]
+    w.check(sim)
+    # hi from the carry, the call inside the horizon; and the two last timestamps equal
+    ts = np.array([T0 + 1.5, T0 + 4.0, T0 + 3.5, T0 + 3.75])
+    w = Step(b[:4], ts, s[:4], [2, 3])
+    assert w.exp_state.tolist() == [(1, 3, T0 + 4.0)]
+    w.check(sim)
+    ts = np.array([T0 + 1.5, T0 + 4.0, T0 + 3.5, T0 + 4.0])
+    w = Step(b[:4], ts, s[:4], [2, 3], window=0.0)
+    assert w.exp_state.tolist() == [(1, 3, T0 + 4.0)] and w.exp_dup.tolist() == [-1, -2]
+    w.check(sim)
+
+
+def test_alone_items(sim):
+    """first[] with an empty first, an empty middle and an empty last item, and all three; stream numbers 0 and 0xFFFFFF."""
+    b, off, _ = one_reply(9)
+    s = np.array([0, 0, 0, 0xFFFFFF, 0xFFFFFF, 7, 7, 7, 7], np.int32)
+    ts = ts_of(off[::-1])                                              # the time order is the list reversed
+    for extra, first in ((((0, 11),), [0, 0, 3, 5, 9]), (((1, 11),), [0, 3, 3, 5, 9]), (((3, 11),), [0, 3, 5, 9, 9]),
+                         (((0, 11), (2, 12), (5, 13)), [0, 0, 3, 3, 5, 9, 9])):
+        w = Step(b, ts, s, np.arange(9), extra_items=extra)
+        assert w.first.tolist() == first
+        got = ((w.exp_ent[:, 3] >> np.uint64(32)) & np.uint64(0xFFFFFF)).tolist()
+        assert got == s[::-1].tolist() and w.exp_dup.tolist() == [8, 8, 8, 8, 8, -1, -1, -1, -1]
+        w.check(sim)
+    # the first record of the carry is stream 0xFFFFFF's; stream 0 hears it again
+    w = Step(b[:2], ts_of([1000, 1001]), np.array([0xFFFFFF, 0], np.int32), [1], extra_items=((0, 5), (2, 6)))
+    assert w.exp_dup.tolist() == [-2] and w.first.tolist() == [0, 0, 1, 1]
+    w.check(sim)
+
+
+# One step built by period, as test_mlat.periodic builds its carry: P_PERIOD = 65 records of the call (coprime to 64, 256 and
+# 1024: every hearing drifts over every lane, workgroup place and tile place), all within the window, repeated every
+# P_SPACING = 2^-5 s -- sixteen windows -- from P_EPOCH = 1024 s on.  Every P_CARRY_EVERY-th period also has 65 entries of the
+# carry, interleaved in time with the call's.  Every timestamp is a multiple of 2^-21 s below 2048 s, so the shift is exact and
+# period k's verdicts are period 0's (or, beside the carry, period 0's against period 0's carry), shifted; those two come
+# from find_duplicates.
+P_EPOCH, P_SPACING, P_TICK, P_PERIOD, P_WINDOW, P_CARRY_EVERY = 1024.0, 2.0 ** -5, 2.0 ** -21, 65, 2.0 ** -9, 127
+
+
+def period0():
+    """-> (the call's (tick, bits, stream, marker) in time order, ties in stream order, and the carry's): a long reply heard by
+    streams 0 .. 4 (the carry: by stream 6); a short one heard by streams 5, 6 and 5 again (the carry: by 5); a marker-0
+    record with the long reply's bytes; a reply heard by streams 2 and 6 at the same tick; fillers on all eight streams."""
+    short = IDENT.copy()
+    short[0] = 0x5D                                                    # DF 11
+    call = [(6 + 10 * s_, IDENT, s_, 2) for s_ in range(5)] + [(60, short, 5, 1), (64, short, 6, 1), (90, short, 5, 1), (30, IDENT, 7, 0)]
+    other = fillers(1, 3)[0]
+    call += [(100, other, 2, 2), (100, other, 6, 2)]
+    fb = fillers(2 * P_PERIOD, 9)
+    call += [(200 + 14 * k, fb[k], k % 8, 2) for k in range(P_PERIOD - len(call))]
+    carry = [(21, IDENT, 6, 2), (71, short, 5, 1)]
+    carry += [(201 + 14 * k, fb[P_PERIOD + k], (k + 3) % 8, 2 if k % 5 else 0) for k in range(P_PERIOD - len(carry))]
+    out = []
+    for rows in (call, carry):
+        rows = sorted(rows, key=lambda r: (r[0], r[2]))
+        assert len(rows) == P_PERIOD and len(set((r[0], r[2]) for r in rows)) == P_PERIOD
+        out.append((np.array([r[0] for r in rows], np.int64), np.array([r[1] for r in rows], np.uint8), np.array([r[2] for r in rows], np.int32),
+                    np.array([r[3] for r in rows], np.int32)))
+    return out
+
+
+def periodic_step(periods, horizon, seed=3):
+    """-> (Step, period 0's dup[] without and beside the carry, as places within the period)"""
+    (tick, bits, stream, mk), (ctick, cbits, cstream, cmk) = period0()
+    assert max(tick.max(), ctick.max()) * P_TICK < P_WINDOW < P_SPACING / 8 and np.gcd(P_PERIOD, 64 * 256 * 1024) == 1
+    pay = lambda b, m: [None if m[i] == 0 else (112, b[i].tobytes()) if m[i] == 2 else (56, b[i, :7].tobytes()) for i in range(len(b))]      # noqa: E731
+    t0, c0 = P_EPOCH + tick * P_TICK, P_EPOCH + ctick * P_TICK
+    d_alone, o1 = DR.find_duplicates(pay(bits, mk), t0, stream, [], P_WINDOW)
+    d_carry, o2 = DR.find_duplicates(pay(bits, mk), t0, stream, list(zip(c0.tolist(), pay(cbits, cmk), cstream.tolist())), P_WINDOW)
+    assert np.array_equal(o1, np.arange(P_PERIOD)) and np.array_equal(o2, o1)      # given in time order: a list position is a place
+    assert sorted(set(d_alone.tolist())) != sorted(set(d_carry.tolist())) and (d_carry == -2).sum() >= 6 and (d_alone >= 0).sum() >= 7
+    ks = np.arange(periods)
+    with_carry = ks % P_CARRY_EVERY == 0
+    n = periods * P_PERIOD
+    ts = (P_EPOCH + ks[:, None] * P_SPACING + tick[None, :] * P_TICK).ravel()
+    assert ts[-1] < 2 * P_EPOCH and ((ts.reshape(periods, P_PERIOD) - ks[:, None] * P_SPACING) == t0[None, :]).all()      # the shift is exact
+    cts = (P_EPOCH + ks[with_carry][:, None] * P_SPACING + ctick[None, :] * P_TICK).ravel()
+    kc = int(with_carry.sum())
+    carry = words_of(cts, np.tile(cbits, (kc, 1)), np.tile(cmk, kc), np.tile(cstream, kc))
+    s_all, mk_all, bits_all = np.tile(stream, periods), np.tile(mk, periods), np.tile(bits, (periods, 1))
+    lst = np.argsort(s_all, kind="stable")                             # the list, grouped by stream: list position -> place
+    order = np.empty(n, np.int32)
+    order[lst] = np.arange(n, dtype=np.int32)                          # place -> list position
+    assert (np.diff(ts) >= 0).all()
+    assert np.array_equal(np.lexsort((order, ts)), np.arange(n))       # ascending (ts, list position) is the place order
+    counts = np.bincount(s_all, minlength=8)
+    first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    first, item_stream = np.insert(first, 3, first[3]), np.insert(np.arange(8, dtype=np.int32), 3, 0xABCDEF)      # and an empty item
+    d = np.where(with_carry[:, None], d_carry[None, :], d_alone[None, :])
+    place = np.where(d >= 0, d + ks[:, None] * P_PERIOD, 0).ravel()
+    d = d.ravel()
+    dup = np.empty(n, np.int32)
+    dup[order] = np.where(d >= 0, order[place], d)
+    rng = np.random.default_rng(seed)
+    w = Step.stated(records_of(rng, bits_all, mk_all != 0, mk_all == 2), ts, order, first, item_stream, carry, P_WINDOW, horizon,
+                    words_of(ts, bits_all, mk_all, s_all), dup, seed)
+    return w, d_alone, d_carry
+
+
+def test_a_step_built_by_period(sim):
+    """The builder of tests/test_gpu_dedup_device.py's large case at 300 periods (19 500 records, three periods beside the
+    carry), on the emulator: period 0 alone through Step's own statement gives the same bytes as the builder's."""
+    w, d_alone, d_carry = periodic_step(300, 4.0)
+    assert w.n == 300 * P_PERIOD and w.nc == 3 * P_PERIOD and 0 < w.exp_state["off"][0] < w.n
+    w.check(sim, grids=(3,))
+    (tick, bits, stream, mk), (ctick, cbits, cstream, cmk) = period0()
+    lst = np.argsort(stream, kind="stable")
+    one = Step(np.concatenate([bits[lst], cbits]), P_EPOCH + np.concatenate([tick[lst], ctick]) * P_TICK, np.concatenate([stream[lst], cstream]),
+               np.arange(P_PERIOD), window=P_WINDOW, horizon=4.0, dem=np.concatenate([mk[lst], cmk]) != 0,
+               long_=np.concatenate([mk[lst], cmk]) == 2)
+    assert np.array_equal(np.where(d_carry >= 0, one.order[np.maximum(d_carry, 0)], d_carry), one.exp_dup[one.order])
+    one.check(sim, grids=(1,))
+
+
+ALONE = ("test_alone_one_reply_heard_by_many_streams", "test_alone_the_earliest_match_lies_in_a_later_partial_tile",
+         "test_alone_more_than_two_tiles_of_hearings", "test_alone_a_carry_range_on_both_sides_in_time", "test_alone_all_timestamps_equal",
+         "test_alone_window_zero", "test_alone_records_with_marker_zero", "test_alone_the_merge_and_the_cut", "test_alone_items")
+
+
+def test_alone_names_the_section():
+    """ALONE is what tests/test_gpu_dedup_device.py imports: every test of this section, and nothing else"""
+    assert sorted(ALONE) == sorted(k for k in globals() if k.startswith("test_alone_") and k != "test_alone_names_the_section")
+
+
+def test_the_step_entry_refuses_bad_arguments(sim):
+    """-5: an order that is no permutation, a first[] that does not end at n or goes down, a negative size."""
+    b, off, s = one_reply(4)
+    w = Step(b, ts_of(off), s, np.arange(4))
+
+    def rc_of(**change):
+        v = Step(b, ts_of(off), s, np.arange(4))
+        for k, x in change.items():
+            setattr(v, k, np.asarray(x, getattr(v, k).dtype))
+        v.run(sim, 1, rc=-5)
+    rc_of(order=[0, 1, 1, 3])
+    rc_of(order=[0, 1, 2, 4])
+    rc_of(first=[0, 1, 2, 3, 5])
+    rc_of(first=[0, 2, 1, 3, 4])
+    rc_of(first=[1, 1, 2, 3, 4])
+    w.check(sim, grids=(2,))
 
 
 # ---- random fleets ---------------------------------------------------------------------------------------------------------

@@ -5,7 +5,11 @@ reference decoder fed the merged sequence (tools/make_golden_shared.py) -- and a
 sequence; the pair sort alone; the new translation unit's build facts.
 
 What a green run here does NOT cover: the host's own shared branch of fleet_step, the entry points and the plane calls on a
-shared context -- tests/test_gpu_shared_decode.py."""
+shared context -- tests/test_gpu_shared_decode.py; and everything on the device's side of these seams: what hipcc makes of
+k_shared_sort_scatter's ballots and k_shared_sort_scan's __shfl_up scan with its carry, the real launchers' grid sizing (the
+launches here are the driver's own) and the kernels' second grid-stride round under them, which k_shared_scatter reaches at
+58 255 records and the others above 524 288 -- tests/test_gpu_shared_device.py runs this file's sort cases, unchanged, on the
+MI355X through tests/gpu/shared_device_driver.hip, and adds the chain keys -> sort -> gather -> scatter at both sizes."""
 import ctypes
 import json
 import os
