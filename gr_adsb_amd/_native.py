@@ -90,6 +90,41 @@ class MLAT_RULE(ctypes.Structure):
 
 
 assert ctypes.sizeof(MLAT_RULE) == 24
+# the MLAT track store (include/adsb_hip.h MLAT TRACKS): one row of adsb_stream_mlat_tracks (adsb_mlat_track), the filter rule
+# a caller states (adsb_mlat_track_rule) and one update's totals (adsb_mlat_track_stats)
+TRACK_GAP, TRACK_RESTARTED = 1, 2                         # ADSB_TRACK_*
+MLAT_TRACK_DTYPE = np.dtype([("icao", "<i4"), ("flags", "<u4"), ("n_fixes", "<i4"), ("n_rejected", "<i4"), ("first_ts", "<f8"), ("last_ts", "<f8"),
+                             ("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("vx", "<f8"), ("vy", "<f8"), ("vz", "<f8"), ("rms_m", "<f8"),
+                             ("n_rx", "<i4"), ("misses", "<i4")])
+assert MLAT_TRACK_DTYPE.itemsize == 96
+
+
+class MLAT_TRACK_RULE(ctypes.Structure):
+    _fields_ = [("alpha", ctypes.c_double), ("beta", ctypes.c_double), ("gate_m", ctypes.c_double), ("max_speed_mps", ctypes.c_double),
+                ("max_gap_s", ctypes.c_double), ("max_rms_m", ctypes.c_double), ("min_up_m", ctypes.c_double),
+                ("restart_after", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class MLAT_TRACK_STATS(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int64) for name in ("fixes", "eligible", "unusable", "stale", "rejected", "taken", "started", "tracks")]
+
+
+assert ctypes.sizeof(MLAT_TRACK_RULE) == 64 and ctypes.sizeof(MLAT_TRACK_STATS) == 64
+# the Python layer's defaults of the track rule (the C call has none)
+MLAT_TRACK_DEFAULTS = dict(alpha=0.3, beta=0.05, gate_m=2000.0, max_speed_mps=350.0, max_gap_s=30.0, max_rms_m=500.0, min_up_m=0.0, restart_after=3)
+
+
+def mlat_track_rule(**kw):
+    """-> MLAT_TRACK_RULE: MLAT_TRACK_DEFAULTS with the keywords given over them"""
+    unknown = set(kw) - set(MLAT_TRACK_DEFAULTS)
+    if unknown:
+        raise TypeError("unknown track rule field(s): %s" % ", ".join(sorted(unknown)))
+    v = dict(MLAT_TRACK_DEFAULTS)
+    v.update(kw)
+    return MLAT_TRACK_RULE(float(v["alpha"]), float(v["beta"]), float(v["gate_m"]), float(v["max_speed_mps"]), float(v["max_gap_s"]),
+                           float(v["max_rms_m"]), float(v["min_up_m"]), int(v["restart_after"]), 0)
+
+
 INT64_MIN = -(1 << 63)       # the cutoff that hides nothing
 STREAM_END = 1               # ADSB_STREAM_END: the stream's last item
 STREAM_FRESH_EOB = -(1 << 61)    # the carried end-of-burst offset of a fresh stream
@@ -112,6 +147,7 @@ EXPORTS = [
     "adsb_stream_planes_merged", "adsb_stream_last_order", "adsb_streams_decoder_reset",
     "adsb_streams_set_dedup", "adsb_stream_last_duplicates", "adsb_stream_dedup_stats",
     "adsb_stream_set_ecef", "adsb_stream_mlat", "adsb_stream_mlat_rule", "adsb_stream_mlat_stats", "adsb_geodetic_to_ecef", "adsb_ecef_to_geodetic",
+    "adsb_stream_mlat_track", "adsb_stream_mlat_tracks", "adsb_stream_mlat_tracks_expire", "adsb_stream_mlat_tracks_reset",
     "adsb_reset_stats", "adsb_detect_history", "adsb_numa_info", "adsb_host_alloc_near", "adsb_last_error", "adsb_host_alloc", "adsb_host_free", "adsb_host_register", "adsb_host_unregister",
 ]
 
@@ -236,6 +272,10 @@ def load():
     lib.adsb_stream_mlat.argtypes = [vp, c.c_double, c.c_double, i32, vp, i32, c.POINTER(i32), vp, vp, i32, c.POINTER(i32)]
     lib.adsb_stream_mlat_rule.argtypes = [vp, c.c_double, c.c_double, c.POINTER(MLAT_RULE), vp, vp, i32, c.POINTER(i32), vp, vp, i32, c.POINTER(i32)]
     lib.adsb_stream_mlat_stats.argtypes = [vp, c.POINTER(i32), c.POINTER(c.c_double)]
+    lib.adsb_stream_mlat_track.argtypes = [vp, c.c_double, c.c_double, c.POINTER(MLAT_RULE), c.POINTER(MLAT_TRACK_RULE), c.POINTER(MLAT_TRACK_STATS)]
+    lib.adsb_stream_mlat_tracks.argtypes = [vp, i32, c.c_double, vp, i32, c.POINTER(i32)]
+    lib.adsb_stream_mlat_tracks_expire.argtypes = [vp, c.c_double, c.POINTER(c.c_int64)]
+    lib.adsb_stream_mlat_tracks_reset.argtypes = [vp]
     lib.adsb_geodetic_to_ecef.argtypes = [c.c_double] * 3 + [c.POINTER(c.c_double)] * 3
     lib.adsb_geodetic_to_ecef.restype = None
     lib.adsb_ecef_to_geodetic.argtypes = [c.c_double] * 3 + [c.POINTER(c.c_double)] * 3
@@ -700,6 +740,39 @@ class Context:
         k, u = ctypes.c_int32(0), ctypes.c_double(0)
         self._chk(self.lib.adsb_stream_mlat_stats(self._h, ctypes.byref(k), ctypes.byref(u)))
         return k.value, u.value
+
+    # the MLAT track store (include/adsb_hip.h MLAT TRACKS)
+    def stream_mlat_track(self, rule, track_rule, t_lo=-np.inf, t_hi=np.inf):
+        """One update of the device-side track store from the fixes adsb_stream_mlat_rule(rule) would return for [t_lo, t_hi)
+        (adsb_stream_mlat_track; rule: MLAT_RULE, track_rule: MLAT_TRACK_RULE) -> the call's totals as a dict (MLAT_TRACK_STATS'
+        fields).  No fix comes down."""
+        st = MLAT_TRACK_STATS()
+        self._chk(self.lib.adsb_stream_mlat_track(self._h, float(t_lo), float(t_hi), ctypes.byref(rule), ctypes.byref(track_rule), ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in MLAT_TRACK_STATS._fields_}
+
+    def stream_mlat_tracks(self, min_fixes=1, cutoff=-np.inf, cap=None):
+        """-> MLAT_TRACK_DTYPE[n]: the tracks with n_fixes >= min_fixes and last_ts >= cutoff, in ascending icao
+        (adsb_stream_mlat_tracks).  cap None: a count query first; a cap that is too small is asked again with what is needed."""
+        n = ctypes.c_int32(0)
+        cap = 0 if cap is None else int(cap)
+        for attempt in (0, 1):
+            rows = np.zeros(cap, dtype=MLAT_TRACK_DTYPE)
+            rc = self.lib.adsb_stream_mlat_tracks(self._h, int(min_fixes), float(cutoff), rows.ctypes.data if cap else None, cap, ctypes.byref(n))
+            if rc == -28 and attempt == 0:
+                cap = max(cap, n.value)
+                continue
+            self._chk(rc)
+            return rows[:n.value]
+
+    def expire_mlat_tracks(self, cutoff):
+        """Removes the tracks with last_ts < cutoff (adsb_stream_mlat_tracks_expire) -> their number."""
+        k = ctypes.c_int64(0)
+        self._chk(self.lib.adsb_stream_mlat_tracks_expire(self._h, float(cutoff), ctypes.byref(k)))
+        return k.value
+
+    def reset_mlat_tracks(self):
+        """Forgets every track (adsb_stream_mlat_tracks_reset)."""
+        self._chk(self.lib.adsb_stream_mlat_tracks_reset(self._h))
 
     def stream_decoder_reserve(self, slots):
         """The capacity of the decoders' store, while it holds nothing (adsb_stream_decoder_reserve)."""

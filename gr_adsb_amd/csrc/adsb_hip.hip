@@ -33,6 +33,7 @@
 #include "adsb_dedup.h"
 #include "adsb_mlat.h"
 #include "adsb_mlat_rule.h"
+#include "adsb_mlat_track.h"
 
 #include "adsb_env_hip.h"
 
@@ -200,6 +201,14 @@ struct FleetDec {
   std::vector<double> rx;
   DevBuf d_mlat;
   PinnedBuf h_mlat;
+  // the MLAT track store (adsb_mlat_track.hip): d_rows[cur][0 .. n) in ascending icao; a call merges into the other buffer
+  // and changes cur / n once its counts are down and in range.  Not decoder state: only fleet_close and
+  // adsb_stream_mlat_tracks_reset forget it.  d_work: one call's buffer (adsb_mlat_track.h: Layout); h_cnt: where counts come down.
+  struct Tracks {
+    int cur = 0, n = 0;
+    DevBuf d_rows[2], d_work;
+    PinnedBuf h_cnt;
+  } trk;
 };
 constexpr long long kFleetMinCap = 256, kFleetDefaultCap = 1ll << 16, kFleetMaxCap = 1ll << 27;    // (slot index 2^28 - 1 would sort with kDecNoKey)
 constexpr size_t kFleetSlotBytes = 16 + sizeof(Plane);
@@ -1624,8 +1633,9 @@ int fleet_close(adsb_ctx* c) {
   FleetDec& F = c->fd;
   F.open = false; F.cap = 0; F.n_rows = 0;
   F.start.clear(); F.gen.clear(); F.slots.clear(); F.planes.clear(); F.rx.clear();
-  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen, &F.d_snap, &F.d_ages, &F.d_merged, &F.d_shared, &F.dd.d_carry[0], &F.dd.d_carry[1], &F.dd.d_call, &F.d_mlat}) HIPCHK(c, b->release());
-  for (PinnedBuf* b : {&F.h_recs, &F.h_rows, &F.h_items, &F.h_cnt, &F.h_shared, &F.h_order, &F.h_order_next, &F.dd.h_dup, &F.dd.h_dup_next, &F.h_mlat}) HIPCHK(c, b->release());
+  F.trk.cur = F.trk.n = 0;
+  for (DevBuf* b : {&F.d_store, &F.d_recs, &F.d_items, &F.d_cnt, &F.d_keys, &F.d_sorted, &F.d_tmp, &F.d_ts, &F.d_rows, &F.d_gen, &F.d_snap, &F.d_ages, &F.d_merged, &F.d_shared, &F.dd.d_carry[0], &F.dd.d_carry[1], &F.dd.d_call, &F.d_mlat, &F.trk.d_rows[0], &F.trk.d_rows[1], &F.trk.d_work}) HIPCHK(c, b->release());
+  for (PinnedBuf* b : {&F.h_recs, &F.h_rows, &F.h_items, &F.h_cnt, &F.h_shared, &F.h_order, &F.h_order_next, &F.dd.h_dup, &F.dd.h_dup_next, &F.h_mlat, &F.trk.h_cnt}) HIPCHK(c, b->release());
   return 0;
 }
 
@@ -2493,18 +2503,16 @@ static_assert(sizeof(adsb_mlat_aux) == adsb_mlat_host::kAuxBytes && sizeof(adsb_
 // launch.  rule null: adsb_mlat.hip's groups and Gauss-Newton kernels on layout().  rule given: adsb_mlat_rule.hip's groups and
 // damped solve kernels on layout_rule(), the aux rows (aux may be null) beside the fixes.  min_group: the fewest used
 // hearings a selected group can have, which bounds the group count.
-static int mlat_call(adsb_ctx* c, const char* api, double t_lo, double t_hi, int32_t min_rx, int min_group, const adsb_mlat_rule* rule,
-                     adsb_mlat_fix* fixes, adsb_mlat_aux* aux, int32_t cap, int32_t* n_fixes, int32_t* member_stream, double* member_ts,
-                     int32_t member_cap, int32_t* n_members) {
+// mlat_solve is the call up to and including the solve's launch: the fixes, the aux rows and the member lists are left in
+// F.d_mlat, carved by *L_out, for mlat_call to bring down or for adsb_stream_mlat_track to read where they lie.
+static int mlat_solve(adsb_ctx* c, const char* api, double t_lo, double t_hi, int32_t min_rx, int min_group, const adsb_mlat_rule* rule, int32_t cap,
+                      int32_t* n_fixes, int32_t member_cap, int32_t* n_members, adsb_mlat_host::Layout* L_out) {
   namespace mh = adsb_mlat_host;
   const auto refuse = [&](int code, const char* what, hipError_t he = hipSuccess) {
     char msg[192];
     snprintf(msg, sizeof(msg), "%s: %s", api, what);
     return fail(c, code, msg, he);
   };
-  if (std::isnan(t_lo) || std::isnan(t_hi)) return refuse(-EINVAL, "a bound is NaN");
-  if (!n_fixes || !n_members || cap < 0 || member_cap < 0 || (cap > 0 && !fixes) || (member_cap > 0 && (!member_stream || !member_ts)))
-    return refuse(-EINVAL, "n_fixes / n_members, or the arrays for cap / member_cap > 0, missing");
   int rc;
   if ((rc = require_idle(c, kCallPending))) return rc;
   FleetDec& F = c->fd;
@@ -2515,6 +2523,7 @@ static int mlat_call(adsb_ctx* c, const char* api, double t_lo, double t_hi, int
   HIPCHK(c, hipSetDevice(c->device));
   const hipStream_t st = c->stream;
   const mh::Layout L = rule ? mh::layout_rule((size_t)nc, (size_t)n_streams) : mh::layout((size_t)nc, (size_t)n_streams);
+  *L_out = L;
   const size_t rx_bytes = F.rx.size() * sizeof(double);
   if ((rc = ensure(c, F.d_mlat, L.bytes)) || (rc = ensure_pinned(c, F.h_mlat, rx_bytes + 64))) return rc;
   char* const work = (char*)F.d_mlat.p;
@@ -2544,6 +2553,24 @@ static int mlat_call(adsb_ctx* c, const char* api, double t_lo, double t_hi, int
   } else if ((e = (hipError_t)mh::launch_solve(st, carry, nc, ng, D.window, n_streams, work, L))) {
     return refuse(-EIO, "k_mlat_solve", e);
   }
+  return 0;
+}
+
+static int mlat_call(adsb_ctx* c, const char* api, double t_lo, double t_hi, int32_t min_rx, int min_group, const adsb_mlat_rule* rule,
+                     adsb_mlat_fix* fixes, adsb_mlat_aux* aux, int32_t cap, int32_t* n_fixes, int32_t* member_stream, double* member_ts,
+                     int32_t member_cap, int32_t* n_members) {
+  char msg[192];
+  if (std::isnan(t_lo) || std::isnan(t_hi)) { snprintf(msg, sizeof(msg), "%s: a bound is NaN", api); return fail(c, -EINVAL, msg); }
+  if (!n_fixes || !n_members || cap < 0 || member_cap < 0 || (cap > 0 && !fixes) || (member_cap > 0 && (!member_stream || !member_ts))) {
+    snprintf(msg, sizeof(msg), "%s: n_fixes / n_members, or the arrays for cap / member_cap > 0, missing", api);
+    return fail(c, -EINVAL, msg);
+  }
+  adsb_mlat_host::Layout L;
+  if (const int rc = mlat_solve(c, api, t_lo, t_hi, min_rx, min_group, rule, cap, n_fixes, member_cap, n_members, &L)) return rc;
+  const int ng = *n_fixes, nm = *n_members;
+  if (ng == 0) return 0;
+  const hipStream_t st = c->stream;
+  const char* const work = (const char*)c->fd.d_mlat.p;
   HIPCHK(c, hipMemcpyAsync(fixes, work + L.fixes, (size_t)ng * sizeof(adsb_mlat_fix), hipMemcpyDeviceToHost, st));
   if (rule && aux) HIPCHK(c, hipMemcpyAsync(aux, work + L.aux, (size_t)ng * sizeof(adsb_mlat_aux), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipMemcpyAsync(member_stream, work + L.member_stream, (size_t)nm * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -2561,22 +2588,31 @@ int adsb_stream_mlat(adsb_ctx* c, double t_lo, double t_hi, int32_t min_rx, adsb
                    member_cap, n_members);
 }
 
+// adsb_mlat_rule's argument table, for the entry point `api`: 0, or -EINVAL with its message
+static int mlat_rule_check(adsb_ctx* c, const char* api, const adsb_mlat_rule* rule) {
+  const auto refuse = [&](const char* what) {
+    char msg[192];
+    snprintf(msg, sizeof(msg), "%s: %s", api, what);
+    return fail(c, -EINVAL, msg);
+  };
+  if (!rule) return refuse("rule is NULL");
+  if (rule->solver != ADSB_MLAT_SOLVER_GN && rule->solver != ADSB_MLAT_SOLVER_LM) return refuse("unknown solver");
+  if (rule->flags & ~(ADSB_MLAT_RESTART | ADSB_MLAT_ALTITUDE)) return refuse("unknown flags");
+  if (rule->solver == ADSB_MLAT_SOLVER_GN && rule->flags != 0) return refuse("flags need ADSB_MLAT_SOLVER_LM");
+  if (rule->reserved != 0) return refuse("reserved is not 0");
+  const bool want_alt = (rule->flags & ADSB_MLAT_ALTITUDE) != 0;
+  if (rule->min_rx < (want_alt ? adsb_mlat_host::kMinRxAided : adsb_mlat_host::kMinRx)) return refuse("min_rx < 4 (< 3 with ADSB_MLAT_ALTITUDE)");
+  if (want_alt && !(std::isfinite(rule->alt_weight) && rule->alt_weight > 0.0)) return refuse("alt_weight is not finite and > 0");
+  return 0;
+}
+
 // adsb_stream_mlat with the rule stated by the caller.  _GN is adsb_stream_mlat itself, with empty aux rows; _LM is
 // mlat_call with the rule.
 int adsb_stream_mlat_rule(adsb_ctx* c, double t_lo, double t_hi, const adsb_mlat_rule* rule, adsb_mlat_fix* fixes, adsb_mlat_aux* aux, int32_t cap,
                           int32_t* n_fixes, int32_t* member_stream, double* member_ts, int32_t member_cap, int32_t* n_members) {
   if (!c) return -EINVAL;
   if (const int rc = need_dedup_streams(c, "adsb_stream_mlat_rule")) return rc;
-  if (!rule) return fail(c, -EINVAL, "adsb_stream_mlat_rule: rule is NULL");
-  if (rule->solver != ADSB_MLAT_SOLVER_GN && rule->solver != ADSB_MLAT_SOLVER_LM) return fail(c, -EINVAL, "adsb_stream_mlat_rule: unknown solver");
-  if (rule->flags & ~(ADSB_MLAT_RESTART | ADSB_MLAT_ALTITUDE)) return fail(c, -EINVAL, "adsb_stream_mlat_rule: unknown flags");
-  if (rule->solver == ADSB_MLAT_SOLVER_GN && rule->flags != 0) return fail(c, -EINVAL, "adsb_stream_mlat_rule: flags need ADSB_MLAT_SOLVER_LM");
-  if (rule->reserved != 0) return fail(c, -EINVAL, "adsb_stream_mlat_rule: reserved is not 0");
-  const bool want_alt = (rule->flags & ADSB_MLAT_ALTITUDE) != 0;
-  if (rule->min_rx < (want_alt ? adsb_mlat_host::kMinRxAided : adsb_mlat_host::kMinRx))
-    return fail(c, -EINVAL, "adsb_stream_mlat_rule: min_rx < 4 (< 3 with ADSB_MLAT_ALTITUDE)");
-  if (want_alt && !(std::isfinite(rule->alt_weight) && rule->alt_weight > 0.0))
-    return fail(c, -EINVAL, "adsb_stream_mlat_rule: alt_weight is not finite and > 0");
+  if (const int rc = mlat_rule_check(c, "adsb_stream_mlat_rule", rule)) return rc;
   if (rule->solver == ADSB_MLAT_SOLVER_GN) {
     const int rc = adsb_stream_mlat(c, t_lo, t_hi, rule->min_rx, fixes, cap, n_fixes, member_stream, member_ts, member_cap, n_members);
     if (rc == 0 && aux)
@@ -2585,6 +2621,160 @@ int adsb_stream_mlat_rule(adsb_ctx* c, double t_lo, double t_hi, const adsb_mlat
   }
   return mlat_call(c, "adsb_stream_mlat_rule", t_lo, t_hi, rule->min_rx, adsb_mlat_host::kMinRxAided, rule, fixes, aux, cap, n_fixes, member_stream,
                    member_ts, member_cap, n_members);
+}
+
+// ---- MLAT TRACKS (include/adsb_hip.h): the store of FleetDec::Tracks, adsb_mlat_track.hip's kernels
+static_assert(sizeof(adsb_mlat_track) == adsb_mlat_track_host::kRowBytes && sizeof(adsb_mlat_track_rule) == adsb_mlat_track_host::kRuleBytes &&
+              sizeof(adsb_mlat_track_stats) == 64 && offsetof(adsb_mlat_track, first_ts) == 16 && offsetof(adsb_mlat_track, n_rx) == 88 &&
+              offsetof(adsb_mlat_track_rule, restart_after) == 56 && sizeof(adsb_mlat_fix) == adsb_mlat_track_host::kFixBytes &&
+              sizeof(adsb_mlat_aux) == adsb_mlat_track_host::kAuxBytes && ADSB_MLAT_OK == 0,
+              "adsb_mlat_track.hip reads adsb_mlat_fix and adsb_mlat_aux rows and writes adsb_mlat_track rows");
+
+// One update of the track store: the rule's argument tables, mlat_solve -- the fixes and aux rows stay in F.d_mlat -- then
+// adsb_mlat_track.hip's two launch groups.  The eligible count comes down between them (the sort's size is the host's); the other
+// buffer is given room for every eligible fix to start a track before the launch that merges into it; the run and
+// new-address counts and the totals come down behind it, and only then do cur and n change.
+int adsb_stream_mlat_track(adsb_ctx* c, double t_lo, double t_hi, const adsb_mlat_rule* rule, const adsb_mlat_track_rule* tr,
+                           adsb_mlat_track_stats* stats) {
+  namespace mt = adsb_mlat_track_host;
+  const char* const api = "adsb_stream_mlat_track";
+  if (!c) return -EINVAL;
+  int rc;
+  if ((rc = need_dedup_streams(c, api)) || (rc = mlat_rule_check(c, api, rule))) return rc;
+  const auto refuse = [&](int code, const char* what, hipError_t he = hipSuccess) {
+    char msg[192];
+    snprintf(msg, sizeof(msg), "%s: %s", api, what);
+    return fail(c, code, msg, he);
+  };
+  if (!tr) return refuse(-EINVAL, "track_rule is NULL");
+  const auto gain = [](double v) { return std::isfinite(v) && v > 0.0 && v <= 1.0; };
+  const auto bound = [](double v) { return std::isfinite(v) && v >= 0.0; };
+  if (!gain(tr->alpha) || !gain(tr->beta)) return refuse(-EINVAL, "alpha and beta are finite and in (0, 1]");
+  if (!bound(tr->gate_m) || !bound(tr->max_speed_mps) || !bound(tr->max_gap_s)) return refuse(-EINVAL, "gate_m, max_speed_mps and max_gap_s are finite and >= 0");
+  if (std::isnan(tr->max_rms_m) || std::isnan(tr->min_up_m)) return refuse(-EINVAL, "max_rms_m or min_up_m is NaN");
+  if (tr->restart_after < 1) return refuse(-EINVAL, "restart_after < 1");
+  if (tr->reserved != 0) return refuse(-EINVAL, "track_rule->reserved is not 0");
+  if (std::isnan(t_lo) || std::isnan(t_hi)) return refuse(-EINVAL, "a bound is NaN");
+  FleetDec& F = c->fd;
+  FleetDec::Tracks& T = F.trk;
+  adsb_mlat_track_stats s = {};
+  s.tracks = T.n;
+  const bool lm = rule->solver == ADSB_MLAT_SOLVER_LM;
+  adsb_mlat_host::Layout ML;
+  int32_t ng = 0, nm = 0;
+  if ((rc = mlat_solve(c, api, t_lo, t_hi, rule->min_rx, lm ? adsb_mlat_host::kMinRxAided : adsb_mlat_host::kMinRx, lm ? rule : nullptr, INT32_MAX, &ng,
+                       INT32_MAX, &nm, &ML)))
+    return rc;
+  s.fixes = ng;
+  if (ng > 0) {
+    const hipStream_t st = c->stream;
+    const char* const fixes = (const char*)F.d_mlat.p + ML.fixes;
+    const char* const aux = lm ? (const char*)F.d_mlat.p + ML.aux : nullptr;
+    const mt::Layout L = mt::layout((size_t)ng);
+    if ((rc = ensure(c, T.d_work, L.bytes)) || (rc = ensure_pinned(c, T.h_cnt, 256))) return rc;
+    char* const work = (char*)T.d_work.p;
+    int* const cnts = (int*)T.h_cnt.p;
+    const unsigned long long* const tot = (const unsigned long long*)((char*)T.h_cnt.p + 128);
+    hipError_t e;
+    if ((e = (hipError_t)mt::launch_keys(st, fixes, ng, work, L))) return refuse(-EIO, "the key kernels", e);
+    HIPCHK(c, hipMemcpyAsync(cnts, work + L.cnts, mt::kCntWords * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const int nk = cnts[mt::kCntKeys];
+    if (nk < 0 || nk > ng) return refuse(-EIO, "the eligible count is out of range");
+    s.eligible = nk;
+    if (nk > 0) {
+      if ((long long)T.n + nk > (1ll << 24)) return refuse(-EIO, "more tracks than addresses");
+      DevBuf& next = T.d_rows[T.cur ^ 1];
+      if ((rc = ensure(c, next, ((size_t)T.n + (size_t)nk) * mt::kRowBytes))) return rc;
+      if ((e = (hipError_t)mt::launch_update(st, fixes, aux, nk, tr, T.d_rows[T.cur].p, T.n, next.p, work, L))) return refuse(-EIO, "the update kernels", e);
+      HIPCHK(c, hipMemcpyAsync(cnts, work + L.cnts, mt::kCntWords * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipMemcpyAsync((char*)T.h_cnt.p + 128, work + L.stats, mt::kStatWords * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipStreamSynchronize(st));
+      const int nr = cnts[mt::kCntRuns], nn = cnts[mt::kCntNew];
+      if (nr < 1 || nr > nk || nn < 0 || nn > nr) return refuse(-EIO, "the run counts are out of range");
+      T.cur ^= 1; T.n += nn;
+      s.unusable = (int64_t)tot[mt::kStatUnusable]; s.stale = (int64_t)tot[mt::kStatStale]; s.rejected = (int64_t)tot[mt::kStatRejected];
+      s.taken = (int64_t)tot[mt::kStatTaken]; s.started = (int64_t)tot[mt::kStatStarted];
+      s.tracks = T.n;
+    }
+  }
+  if (stats) *stats = s;
+  return 0;
+}
+
+// The readout and the expiry: the predicate and the compaction over the store, the picked rows gathered into the other
+// buffer, where the readout downloads them and which the expiry makes the store.  expire: no cap applies, and nothing is
+// gathered when every row is kept.  -> *picked
+static int tracks_pick(adsb_ctx* c, const char* api, int32_t min_fixes, double cutoff, int32_t cap, bool expire, int32_t* picked) {
+  namespace mt = adsb_mlat_track_host;
+  FleetDec::Tracks& T = c->fd.trk;
+  const auto refuse = [&](int code, const char* what, hipError_t he = hipSuccess) {
+    char msg[192];
+    snprintf(msg, sizeof(msg), "%s: %s", api, what);
+    return fail(c, code, msg, he);
+  };
+  *picked = 0;
+  if (T.n == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = c->stream;
+  const mt::Layout L = mt::layout((size_t)T.n);
+  int rc;
+  DevBuf& next = T.d_rows[T.cur ^ 1];
+  if ((rc = ensure(c, T.d_work, L.bytes)) || (rc = ensure_pinned(c, T.h_cnt, 256)) || (rc = ensure(c, next, (size_t)T.n * mt::kRowBytes))) return rc;
+  char* const work = (char*)T.d_work.p;
+  int* const cnts = (int*)T.h_cnt.p;
+  hipError_t e;
+  if ((e = (hipError_t)mt::launch_pick(st, T.d_rows[T.cur].p, T.n, min_fixes, cutoff, work, L))) return refuse(-EIO, "the pick kernels", e);
+  HIPCHK(c, hipMemcpyAsync(cnts, work + L.cnts, mt::kCntWords * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const int k = cnts[mt::kCntKeys];
+  if (k < 0 || k > T.n) return refuse(-EIO, "the track count is out of range");
+  *picked = k;
+  if (!expire && k > cap) return refuse(-ENOSPC, "cap is too small (*n)");
+  if (k == 0 || (expire && k == T.n)) return 0;
+  if ((e = (hipError_t)mt::launch_gather(st, T.d_rows[T.cur].p, k, next.p, work, L))) return refuse(-EIO, "k_track_gather", e);
+  return 0;
+}
+
+int adsb_stream_mlat_tracks(adsb_ctx* c, int32_t min_fixes, double cutoff, adsb_mlat_track* rows, int32_t cap, int32_t* n) {
+  const char* const api = "adsb_stream_mlat_tracks";
+  if (!c) return -EINVAL;
+  int rc;
+  if ((rc = need_dedup_streams(c, api))) return rc;
+  if (!n || cap < 0 || (cap > 0 && !rows)) return fail(c, -EINVAL, "adsb_stream_mlat_tracks: n, or rows for cap > 0, missing");
+  if (std::isnan(cutoff)) return fail(c, -EINVAL, "adsb_stream_mlat_tracks: cutoff is NaN");
+  if ((rc = require_idle(c, kCallPending))) return rc;
+  if ((rc = tracks_pick(c, api, min_fixes, cutoff, cap, false, n)) || *n == 0) return rc;
+  FleetDec::Tracks& T = c->fd.trk;
+  HIPCHK(c, hipMemcpyAsync(rows, T.d_rows[T.cur ^ 1].p, (size_t)*n * sizeof(adsb_mlat_track), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int adsb_stream_mlat_tracks_expire(adsb_ctx* c, double cutoff, int64_t* n_removed) {
+  const char* const api = "adsb_stream_mlat_tracks_expire";
+  if (!c) return -EINVAL;
+  int rc;
+  if ((rc = need_dedup_streams(c, api))) return rc;
+  if (std::isnan(cutoff)) return fail(c, -EINVAL, "adsb_stream_mlat_tracks_expire: cutoff is NaN");
+  if ((rc = require_idle(c, kCallPending))) return rc;
+  if (n_removed) *n_removed = 0;
+  FleetDec::Tracks& T = c->fd.trk;
+  int32_t kept = 0;
+  if ((rc = tracks_pick(c, api, INT32_MIN, cutoff, 0, true, &kept))) return rc;
+  if (kept == T.n) return 0;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (n_removed) *n_removed = T.n - kept;
+  T.cur ^= 1; T.n = kept;
+  return 0;
+}
+
+int adsb_stream_mlat_tracks_reset(adsb_ctx* c) {
+  if (!c) return -EINVAL;
+  int rc;
+  if ((rc = need_dedup_streams(c, "adsb_stream_mlat_tracks_reset")) || (rc = require_idle(c, kCallPending))) return rc;
+  c->fd.trk.n = 0;
+  return 0;
 }
 
 int adsb_streams_set_decoder(adsb_ctx* c, int32_t msg_filter) {

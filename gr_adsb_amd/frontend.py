@@ -319,20 +319,82 @@ class Receivers:
         cut = np.full(k, int(cutoffs), dtype=np.int64) if np.ndim(cutoffs) == 0 else np.asarray(cutoffs, dtype=np.int64)
         return self.ctx.expire_stream_planes(cut, ids)
 
-    def merged(self, ids=None, cutoff=None):
+    def merged(self, ids=None, cutoff=None, mlat=False):
         """receivers(ages=True): ONE picture out of every receiver's -- (rows, info), one DECODED_DTYPE row per aircraft any
         stream of `ids` (strictly ascending; None: all) holds, in ascending address order, and its _native.MERGED_DTYPE entry
         (adsb_stream_planes_merged).  Callsign, altitude, velocity and position each come from the receiver that has the field
         and heard the aircraft last (info["src_*"]: which one); num_msgs is the sum, info["last_seen"] the latest clock.
         cutoff: entries with last_seen < cutoff are left out (None: none is); the streams' clocks have to be comparable, i.e.
-        `starts` real times.  _native.plane_entry(row, last_seen) turns a row into the reference's plane_dict entry."""
+        `starts` real times.  _native.plane_entry(row, last_seen) turns a row into the reference's plane_dict entry.
+        mlat=True (receivers(dedup=...) too): -> (rows, info, track_of, tracks): tracks is tracks(min_fixes=1), and track_of[j]
+        the index in it of rows[j]'s address (-1 where it has no track), found with np.searchsorted on the two address-ordered
+        results.  Aircraft known to MLAT alone are in tracks only.  rows and info are what merged() without mlat returns."""
         if not (self.decode and self.ages):
             raise ValueError("merged() needs receivers(ages=True) on a FLAG_STREAM_DECODE | FLAG_PLANE_AGES context")
         if self.shared:
             if ids is not None:
                 raise ValueError("a shared decoder has one table: merged() takes no ids")
             ids = [0]
-        return self.ctx.merged_planes(ids, cutoff)
+        rows, info = self.ctx.merged_planes(ids, cutoff)
+        if not mlat:
+            return rows, info
+        tracks = self.tracks(min_fixes=1)
+        at = np.searchsorted(tracks["icao"], rows["icao"])
+        hit = at < len(tracks)
+        hit[hit] = tracks["icao"][at[hit]] == rows["icao"][hit]
+        return rows, info, np.where(hit, at, -1).astype(np.int32), tracks
+
+    def track(self, t_lo=None, t_hi=None, solver="damped", restart=True, altitude=False, alt_weight=1.0, min_rx=4, **track_rule):
+        """receivers(dedup=..., positions=...): one update of the device-side store of per-aircraft MLAT tracks
+        (adsb_stream_mlat_track; include/adsb_hip.h MLAT TRACKS) from the fixes mlat() with these arguments would return for
+        [t_lo, t_hi) -- the fixes stay on the device -> the call's totals as a dict (fixes, eligible, unusable, stale, rejected,
+        taken, started, tracks).  track_rule: alpha, beta, gate_m, max_speed_mps, max_gap_s, restart_after, max_rms_m, min_up_m
+        over _native.MLAT_TRACK_DEFAULTS (0.3, 0.05, 2000, 350, 30, 3, 500, 0).  A fix no later than its track's last one is stale,
+        so none is taken twice; a rejected fix is not remembered, so let successive calls' ranges adjoin (t_lo = the last
+        call's t_hi) rather than overlap.  The store outlives the carry; tracks() reads it, expire_tracks() and
+        reset_tracks() shrink it."""
+        if not self.dedup:
+            raise ValueError("track() needs receivers(dedup=...)")
+        if solver not in ("gauss-newton", "damped"):
+            raise ValueError("solver is 'gauss-newton' or 'damped'")
+        lo, hi = -np.inf if t_lo is None else t_lo, np.inf if t_hi is None else t_hi
+        if solver == "damped":
+            rule = _native.MLAT_RULE(_native.MLAT_SOLVER_LM, (_native.MLAT_RESTART if restart else 0) | (_native.MLAT_ALTITUDE if altitude else 0),
+                                     int(min_rx), 0, float(alt_weight))
+        else:
+            rule = _native.MLAT_RULE(_native.MLAT_SOLVER_GN, 0, int(min_rx), 0, 0.0)
+        return self.ctx.stream_mlat_track(rule, _native.mlat_track_rule(**track_rule), lo, hi)
+
+    def tracks(self, min_fixes=3, cutoff=None):
+        """The tracks with n_fixes >= min_fixes and last_ts >= cutoff (None: all), in ascending icao (adsb_stream_mlat_tracks):
+        _native.MLAT_TRACK_DTYPE's fields and, computed here in plain NumPy from the row: latitude / longitude (degrees) /
+        altitude_m by ecef_to_geodetic(x, y, z), and speed_kt (horizontal), heading_deg (clockwise from north, [0, 360)) and
+        vertical_rate_fpm from (vx, vy, vz) in the local east / north / up frame at that position."""
+        if not self.dedup:
+            raise ValueError("tracks() needs receivers(dedup=...)")
+        rows = self.ctx.stream_mlat_tracks(min_fixes, -np.inf if cutoff is None else cutoff)
+        extra = ("latitude", "longitude", "altitude_m", "speed_kt", "heading_deg", "vertical_rate_fpm")
+        out = np.zeros(len(rows), dtype=np.dtype(_native.MLAT_TRACK_DTYPE.descr + [(name, "<f8") for name in extra]))
+        for name in _native.MLAT_TRACK_DTYPE.names:
+            out[name] = rows[name]
+        for j, r in enumerate(rows):
+            out["latitude"][j], out["longitude"][j], out["altitude_m"][j] = _native.ecef_to_geodetic(r["x"], r["y"], r["z"])
+        la, lo = np.radians(out["latitude"]), np.radians(out["longitude"])
+        east = -np.sin(lo) * rows["vx"] + np.cos(lo) * rows["vy"]
+        north = -np.sin(la) * np.cos(lo) * rows["vx"] - np.sin(la) * np.sin(lo) * rows["vy"] + np.cos(la) * rows["vz"]
+        up = np.cos(la) * np.cos(lo) * rows["vx"] + np.cos(la) * np.sin(lo) * rows["vy"] + np.sin(la) * rows["vz"]
+        out["speed_kt"] = np.hypot(east, north) * (3600.0 / 1852.0)
+        out["heading_deg"] = np.degrees(np.arctan2(east, north)) % 360.0
+        out["vertical_rate_fpm"] = up * (60.0 / 0.3048)
+        return out
+
+    def expire_tracks(self, cutoff):
+        """Forget the tracks with last_ts < cutoff (adsb_stream_mlat_tracks_expire) -> their number."""
+        return self.ctx.expire_mlat_tracks(cutoff)
+
+    def reset_tracks(self):
+        """Forget every track (adsb_stream_mlat_tracks_reset)."""
+        self.ctx.reset_mlat_tracks()
 
     def mlat(self, t_lo=None, t_hi=None, min_rx=4, solver="gauss-newton", restart=True, altitude=False, alt_weight=1.0):
         """receivers(dedup=..., positions=...): the replies of the carry (the last `horizon` seconds) that at least min_rx
@@ -367,9 +429,17 @@ class Receivers:
             out[name] = col
         return out, ms, mt
 
-    def table(self, timestamp, ids=None, cutoff=None):
-        """The lines the reference's print_planes draws ("Brief") for the merged picture at PDU timestamp `timestamp`."""
-        return _native.plane_table(self.merged(ids, cutoff)[0], timestamp)
+    def table(self, timestamp, ids=None, cutoff=None, mlat=False):
+        """The lines the reference's print_planes draws ("Brief") for the merged picture at PDU timestamp `timestamp`.
+        mlat=True: an aircraft without a position of its own (latitude NaN) that has a track is drawn at the track's latitude
+        and longitude."""
+        if not mlat:
+            return _native.plane_table(self.merged(ids, cutoff)[0], timestamp)
+        rows, _, track_of, tracks = self.merged(ids, cutoff, mlat=True)
+        rows = rows.copy()
+        fill = (track_of >= 0) & np.isnan(rows["latitude"])
+        rows["latitude"][fill], rows["longitude"][fill] = tracks["latitude"][track_of[fill]], tracks["longitude"][track_of[fill]]
+        return _native.plane_table(rows, timestamp)
 
     def state(self, i):
         """(pos, eob, n_overlong) of stream i"""

@@ -133,14 +133,15 @@ def dequantize_iq16(q, full_scale=2.0):
 
 
 def synth_iq_torch(n, fs, bursts_per_s, seed, device, noise_power=1e-3, amp2_range=(0.05, 1.0),
-                   df_choices=None, df_weights=None, snr_db_range=None):
+                   df_choices=None, df_weights=None, snr_db_range=None, addresses=None):
     """Same kind of stream as synth_iq, generated in HBM: by default DF17-length random-payload bursts.
 
     Returns a float32 tensor of shape [n, 2] (interleaved I,Q == complex64 memory layout).
     Payload bits are random (parity irrelevant to framer/demod); layout/amplitudes match synth_iq.
     df_choices / df_weights: per-burst downlink format (its five bits lead the payload; SHORT_DFS bursts end after
     56 bits -- BASELINE config 5's mix).  snr_db_range: burst power = noise_power * 10^(U(range)/10) instead of
-    amp2_range.
+    amp2_range.  addresses: every burst is a DF 17 reply of one of these 24-bit addresses (drawn from a generator of its own,
+    so every other draw is what it is without the argument).
     """
     import torch
 
@@ -156,6 +157,14 @@ def synth_iq_torch(n, fs, bursts_per_s, seed, device, noise_power=1e-3, amp2_ran
     blen = 120 * sps
     starts = torch.randint(0, max(1, n - blen), (nb,), device=device, generator=g)
     bits = torch.randint(0, 2, (nb, 112), device=device, generator=g, dtype=torch.int64)
+    if addresses is not None:
+        g2 = torch.Generator(device=device)
+        g2.manual_seed(seed + 1)
+        aa = torch.tensor(np.asarray(addresses, dtype=np.int64), device=device)[torch.randint(0, len(addresses), (nb,), device=device, generator=g2)]
+        for k in range(5):
+            bits[:, k] = (17 >> (4 - k)) & 1
+        for k in range(24):
+            bits[:, 8 + k] = (aa >> (23 - k)) & 1
     pre = torch.tensor(PREAMBLE_CHIPS.astype(np.int64), device=device).expand(nb, 16)
     data = torch.stack([bits, 1 - bits], dim=2).reshape(nb, 224)
     if df_choices is not None:

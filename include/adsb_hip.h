@@ -661,8 +661,8 @@ int adsb_stream_dedup_stats(adsb_ctx* ctx, int64_t* duplicates, int64_t* carried
  * 2 Msps, 15 m at 20 Msps) and the double's ulp at the magnitude of start: 238 ns, about 71 m, for Unix-epoch starts.  MLAT
  * users should pass starts relative to a session epoch: below 2^23 s the ulp is under 1 ns (0.3 m).  The decoder's
  * last_seen clock works the same either way.  adsb_stream_mlat_stats reports C * ulp(hi), so a caller can see the limit.
- * Sub-sample arrival times, clock offsets between receivers, feeding fixes into the plane table and altitudes other than the
- * reply's own barometric one (DF 18, GNSS height) are not provided.
+ * Sub-sample arrival times, clock offsets between receivers and altitudes other than the reply's own barometric one (DF 18,
+ * GNSS height) are not provided.  (Fixes are fused per aircraft by MLAT TRACKS, below.)
  * THE DAMPED RULE (adsb_stream_mlat_rule with ADSB_MLAT_SOLVER_LM; THE SOLVER above is ADSB_MLAT_SOLVER_GN and stays as it is).
  * Grouping, candidates, USED, d_i, b, the residuals r_i, the rows of J and the arithmetic (double, no contraction) are
  * unchanged.  c = the mean of the R_i, u = c / |c|, up(p) = (p - c) . u.
@@ -759,6 +759,80 @@ int adsb_stream_mlat_rule(adsb_ctx* ctx, double t_lo, double t_hi, const adsb_ml
 /* positioned: streams with a position; ts_ulp_m: ADSB_MLAT_C * ulp(hi), what the double's spacing at the carry's latest
  * timestamp is worth in metres.  Either pointer may be NULL.  -EINVAL without the flag or without open streams. */
 int adsb_stream_mlat_stats(adsb_ctx* ctx, int32_t* positioned, double* ts_ulp_m);
+/* MLAT TRACKS (ADSB_FLAG_STREAM_DEDUP contexts; entry points only: nothing runs and nothing is allocated unless a caller asks).
+ * A store of TRACKS on the device, one per 24-bit address, that outlives the carry: a position p and a velocity v in ECEF
+ * metres and metres per second, the time last_ts of the last fix it took, and counters.  Fixes enter it by the sequential,
+ * outlier-gated rule below; it is read back in ascending icao, as the plane snapshots are.  Time is the fix's ts (the head's
+ * timestamp) throughout.
+ * THE RULE.  One adsb_stream_mlat_track call runs the caller's adsb_mlat_rule over the heads with t_lo <= ts < t_hi exactly
+ * as adsb_stream_mlat_rule would -- the same rows in the same order; they stay on the device -- and takes the ELIGIBLE fixes
+ * (icao >= 0) per address in ascending row order: carry order, which is ascending ts with ties in row order.  Each fix f in
+ * turn meets its address's track T.  All arithmetic is in double with no contraction; |a| = sqrt(a.x*a.x + a.y*a.y + a.z*a.z),
+ * summed in that order.
+ * 1. USABLE iff status == ADSB_MLAT_OK, x, y, z and rms_m are finite, rms_m <= max_rms_m and aux.up_m >= min_up_m (under
+ *    ADSB_MLAT_SOLVER_GN up_m is 0, so min_up_m <= 0 admits those fixes).  A fix that is not usable counts in unusable only.
+ * 2. STALE: if T exists and f.ts <= T.last_ts the fix counts in stale only.  So a fix a track has taken is never taken
+ *    twice: a second call over the same range finds every such fix stale and changes no byte of the store.  (A REJECTED fix
+ *    does not move last_ts and is not remembered: a later call whose range covers it gates it again and counts it again.
+ *    Where outliers matter, let the ranges of successive calls adjoin rather than overlap.)
+ * 3. START: if T does not exist, or f.ts - T.last_ts > max_gap_s: p = f, v = 0, first_ts = last_ts = f.ts, n_fixes = 1,
+ *    misses = 0, rms_m and n_rx the fix's; n_rejected and flags are 0 on a new track and kept on a gap restart, which also sets
+ *    ADSB_TRACK_GAP.
+ * 4. GATE: otherwise dt = f.ts - last_ts, pp = p + v*dt, d = f - pp.  REJECTED iff |d| > gate_m + max_speed_mps * dt: n_rejected
+ *    and misses grow by 1; if misses has reached restart_after the track restarts at this fix as in START with
+ *    ADSB_TRACK_RESTARTED set (how a track begun on a mirror root or an outlier recovers); otherwise nothing else of T changes.
+ * 5. STEP: otherwise p = pp + alpha*d, v = v + (beta/dt)*d, last_ts = f.ts, n_fixes += 1, misses = 0, rms_m and n_rx the fix's.
+ * LIMITS.  The gains are fixed: this is an alpha-beta filter, not a Kalman filter; there is no per-fix covariance, and a fix's
+ * weak height enters as it is.  The velocity is only as good as the fixes' scatter over the time they span.  A corrupted
+ * address/parity reply gives a garbage icao and so a one-fix track: readers filter by min_fixes, and expiry removes such
+ * tracks.  The Python layer's default gains were tried against one simulated aircraft (DESIGN.md 3j says how); that is one
+ * simulation, not a measurement of real traffic.
+ * adsb_stream_mlat_track changes the track store and nothing else: the carry, hi, the decoder, adsb_stream_last_* and the framer
+ * state stay as they were.  stats (may be NULL): fixes = the rows adsb_stream_mlat_rule would return; eligible; unusable; stale;
+ * rejected; taken = the STEP fixes; started = the START fixes, restarts of both kinds included (a fix that is rejected and
+ * restarts its track counts in rejected and in started); tracks = the store's rows after the call.  It refuses what
+ * adsb_stream_mlat_rule refuses, with the same codes; -EINVAL also for: track_rule NULL; alpha or beta not finite or outside
+ * (0, 1]; gate_m, max_speed_mps or max_gap_s negative or not finite; max_rms_m or min_up_m NaN; restart_after < 1;
+ * reserved != 0.  A refused call changes no track.  The store is allocated by the first call that needs it and grows on the
+ * host's decision before the launch that needs the room.
+ * adsb_stream_mlat_tracks: the tracks with n_fixes >= min_fixes and last_ts >= cutoff (-inf: all; NaN: -EINVAL) into
+ * rows[0 .. *n), ascending icao.  cap too small: -ENOSPC with the count in *n and nothing written (rows == NULL with
+ * cap == 0 is a count query).  It changes nothing.
+ * adsb_stream_mlat_tracks_expire removes the tracks with last_ts < cutoff (their number in *n_removed, may be NULL); a later
+ * fix of such an address starts a new track.  adsb_stream_mlat_tracks_reset forgets every track.
+ * The store is not decoder state: adsb_stream_reset, adsb_streams_decoder_reset and adsb_reset keep it;
+ * adsb_stream_mlat_tracks_reset and adsb_streams_close forget it.  All four calls: -EBUSY while submitted tickets are
+ * pending; -EINVAL without ADSB_FLAG_STREAM_DEDUP or without open streams. */
+#define ADSB_TRACK_GAP 1u
+#define ADSB_TRACK_RESTARTED 2u
+typedef struct adsb_mlat_track_rule { /* 64 bytes */
+  double alpha, beta;          /* the gains of position and velocity: (0, 1] */
+  double gate_m, max_speed_mps; /* the gate |d| <= gate_m + max_speed_mps * dt: >= 0 */
+  double max_gap_s;            /* a longer silence restarts the track: >= 0 */
+  double max_rms_m, min_up_m;  /* what makes a fix usable */
+  int32_t restart_after;       /* >= 1: rejected fixes in a row before the track restarts */
+  int32_t reserved;            /* 0 */
+} adsb_mlat_track_rule;
+typedef struct adsb_mlat_track { /* 96 bytes */
+  int32_t icao;
+  uint32_t flags;              /* ADSB_TRACK_* */
+  int32_t n_fixes;             /* taken since the last start, that one included */
+  int32_t n_rejected;
+  double first_ts, last_ts;    /* of the last start; of the last fix taken */
+  double x, y, z;              /* WGS-84 ECEF metres at last_ts */
+  double vx, vy, vz;           /* metres per second */
+  double rms_m;                /* of the last fix taken */
+  int32_t n_rx;                /* of the last fix taken */
+  int32_t misses;              /* rejected fixes since the last one taken */
+} adsb_mlat_track;
+typedef struct adsb_mlat_track_stats { /* 64 bytes */
+  int64_t fixes, eligible, unusable, stale, rejected, taken, started, tracks;
+} adsb_mlat_track_stats;
+int adsb_stream_mlat_track(adsb_ctx* ctx, double t_lo, double t_hi, const adsb_mlat_rule* rule, const adsb_mlat_track_rule* track_rule,
+                           adsb_mlat_track_stats* stats);
+int adsb_stream_mlat_tracks(adsb_ctx* ctx, int32_t min_fixes, double cutoff, adsb_mlat_track* rows, int32_t cap, int32_t* n);
+int adsb_stream_mlat_tracks_expire(adsb_ctx* ctx, double cutoff, int64_t* n_removed);
+int adsb_stream_mlat_tracks_reset(adsb_ctx* ctx);
 /* WGS-84 (a = 6378137 m, f = 1 / 298.257223563), degrees and metres, plain host arithmetic in double.  The inverse is
  * Bowring's start followed by three fixed-point rounds on the latitude; at the poles longitude is 0.  No context. */
 void adsb_geodetic_to_ecef(double lat_deg, double lon_deg, double alt_m, double* x, double* y, double* z);
