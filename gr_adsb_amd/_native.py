@@ -28,6 +28,7 @@ FLAG_DECODE = 512            # opt-in (with FLAG_AIRCRAFT_TABLE): the decoder's 
 FLAG_STREAM_DECODE = 1024    # opt-in: one decoder behind every receiver stream (open_streams), one device step per stream-batch call
 FLAG_STREAM_DECODE_SHARED = 4096   # opt-in, with FLAG_STREAM_DECODE: ONE decoder behind all streams, fed every call's records in time order
 FLAG_STREAM_DEDUP = 8192     # opt-in, with FLAG_STREAM_DECODE | FLAG_STREAM_DECODE_SHARED: a reply heard by several receivers is published once
+FLAG_FEC_SOFT = 16384        # opt-in: soft-decision CRC repair of weak-bit errors from the samples behind the bits (include/adsb_hip.h SOFT REPAIR)
 FLAG_PLANE_AGES = 2048       # opt-in, with FLAG_DECODE or FLAG_STREAM_DECODE: plane_dict's last_seen on the device (planes(seen=True), expire_*)
 # include/adsb_hip.h adsb_decoded: one row per delivered record of a FLAG_DECODE context
 DECODED_DTYPE = np.dtype([("port", "u1"), ("df", "u1"), ("present", "u1"), ("pad0", "u1"), ("icao", "<i4"), ("bits", "u1", (14,)),
@@ -40,6 +41,16 @@ DEC_DUPLICATE = 4            # FLAG_STREAM_DEDUP: another receiver's hearing of 
 DEC_HAS_PLANE, DEC_HAS_CALLSIGN, DEC_HAS_ALTITUDE, DEC_HAS_VELOCITY = 1, 2, 4, 8
 DEC_MSG_FILTERS = {"All Messages": 0, "Extended Squitter Only": 1}
 ABI_VERSION = 5
+# include/adsb_hip.h adsb_soft_fix: one row per delivered record (per tag: demod_work) of a FLAG_FEC_SOFT context
+SOFT_DTYPE = np.dtype([("nflip", "u1"), ("ncand", "u1"), ("bit", "u1", (5,)), ("pad", "u1")])
+assert SOFT_DTYPE.itemsize == 8
+SOFT_FEC_DEFAULTS = dict(n_weak=8, max_flips=3, min_key=0.0)
+
+
+class SOFT_FEC_RULE(ctypes.Structure):
+    _fields_ = [("n_weak", ctypes.c_int32), ("max_flips", ctypes.c_int32), ("min_key", ctypes.c_float), ("flags", ctypes.c_uint32)]
+
+
 # input sample formats (include/adsb_hip.h ADSB_FMT_*): numpy dtype of the flat host array, items per sample
 FMT_FC32, FMT_MAG2, FMT_SC16, FMT_SC8, FMT_CU8 = 0, 1, 2, 3, 4
 FMT_LAYOUT = {FMT_FC32: (np.complex64, 1), FMT_MAG2: (np.float32, 1), FMT_SC16: (np.int16, 2), FMT_SC8: (np.int8, 2),
@@ -135,7 +146,7 @@ EXPORTS = [
     "adsb_submit_iq_device", "adsb_submit_mag2_device", "adsb_submit_iq16_device", "adsb_submit_shard_device", "adsb_wait",
     "adsb_set_iq16_scale", "adsb_process_iq16", "adsb_process_iq16_device",
     "adsb_set_format_scale", "adsb_process_format", "adsb_process_format_device", "adsb_submit_format_device",
-    "adsb_submit_format_host", "adsb_last_confidence", "adsb_set_decoder", "adsb_last_decoded", "adsb_decode_pdus",
+    "adsb_submit_format_host", "adsb_last_confidence", "adsb_set_soft_fec", "adsb_last_soft", "adsb_mode_s_soft_fec", "adsb_set_decoder", "adsb_last_decoded", "adsb_decode_pdus",
     "adsb_framer_work", "adsb_framer_work_passthrough", "adsb_demod_work", "adsb_shard_bounds", "adsb_process_sharded_device", "adsb_shard_device", "adsb_shard_host", "adsb_shard_fixup", "adsb_stitch", "adsb_snr_db", "adsb_mode_s_syndrome", "adsb_mode_s_fec", "adsb_mode_s_aircraft", "adsb_plan_chunks", "adsb_get_stats",
     "adsb_process_sharded_multi", "adsb_device_alloc", "adsb_device_free", "adsb_device_upload", "adsb_clear_pending_events",
     "adsb_process_batch_device", "adsb_process_batch",
@@ -300,6 +311,10 @@ def load():
     lib.adsb_mode_s_syndrome.restype = c.c_uint32
     lib.adsb_mode_s_fec.argtypes = [vp, vp, c.POINTER(i32), c.POINTER(i32)]
     lib.adsb_mode_s_fec.restype = c.c_uint32
+    lib.adsb_mode_s_soft_fec.argtypes = [vp, vp, c.POINTER(SOFT_FEC_RULE), vp, vp]
+    lib.adsb_mode_s_soft_fec.restype = c.c_uint32
+    lib.adsb_set_soft_fec.argtypes = [vp, c.POINTER(SOFT_FEC_RULE)]
+    lib.adsb_last_soft.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
     lib.adsb_mode_s_aircraft.argtypes = [vp, i32, c.POINTER(i32), c.POINTER(i32), c.POINTER(i32)]
     lib.adsb_mode_s_aircraft.restype = c.c_uint32
     lib.adsb_plan_chunks.argtypes = [i64, i64, c.POINTER(i64), c.POINTER(i64)]
@@ -410,6 +425,24 @@ class Context:
             return np.zeros((0, 112), dtype=np.float32)
         buf = (ctypes.c_char * (n.value * 112 * 4)).from_address(p.value)
         v = np.frombuffer(buf, dtype=np.float32).reshape(n.value, 112)
+        return v.copy() if copy else v
+
+    def set_soft_fec(self, n_weak=8, max_flips=3, min_key=0.0):
+        """FLAG_FEC_SOFT contexts: the soft repair's rule (adsb_set_soft_fec): the n_weak weakest bits are candidates, at most
+        max_flips of them are flipped, a candidate's weakness is at least min_key."""
+        rule = SOFT_FEC_RULE(int(n_weak), int(max_flips), float(min_key), 0)
+        self._chk(self.lib.adsb_set_soft_fec(self._h, ctypes.byref(rule)))
+
+    def last_soft(self, copy=True):
+        """FLAG_FEC_SOFT contexts: SOFT_DTYPE rows of the last finished call's records, or of the last demod_work's tags
+        (adsb_last_soft): nflip != 0 marks a record the soft rule repaired, bit[] names the flipped bits."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int32(0)
+        self._chk(self.lib.adsb_last_soft(self._h, ctypes.byref(p), ctypes.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=SOFT_DTYPE)
+        buf = (ctypes.c_char * (n.value * SOFT_DTYPE.itemsize)).from_address(p.value)
+        v = np.frombuffer(buf, dtype=SOFT_DTYPE)
         return v.copy() if copy else v
 
     def set_decoder(self, msg_filter="All Messages", start_timestamp=0.0):
@@ -1209,6 +1242,20 @@ def mode_s_fec(bits14):
     fl = load().adsb_mode_s_fec(b.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(first),
                                 ctypes.byref(nflip))
     return int(fl), out, first.value, nflip.value
+
+
+def mode_s_soft_fec(bits14, key, n_weak=8, max_flips=3, min_key=0.0):
+    """adsb_mode_s_soft_fec: (flags, repaired bits14, SOFT_DTYPE row) of one 14-byte payload and the weakness key[112] of its
+    bits -- the rule FLAG_FEC_SOFT applies on the device (flags: pre-filter bits of the result | BURST_FEC_FIXED on a match)."""
+    b = np.ascontiguousarray(bits14, dtype=np.uint8)
+    k = np.ascontiguousarray(key, dtype=np.float32)
+    assert b.size == 14 and k.size == 112
+    out = np.zeros(14, dtype=np.uint8)
+    row = np.zeros(1, dtype=SOFT_DTYPE)
+    rule = SOFT_FEC_RULE(int(n_weak), int(max_flips), float(min_key), 0)
+    fl = load().adsb_mode_s_soft_fec(b.ctypes.data_as(ctypes.c_void_p), k.ctypes.data_as(ctypes.c_void_p), ctypes.byref(rule),
+                                  out.ctypes.data_as(ctypes.c_void_p), row.ctypes.data_as(ctypes.c_void_p))
+    return int(fl), out, row[0]
 
 
 def mode_s_aircraft(bits14, fec=False):

@@ -398,7 +398,7 @@ class demod(gr.sync_block):
     """PPM bit slicer / PDU publisher (reference python/adsb/demod.py:31-136)."""
 
     def __init__(self, fs, device=0, parity_filter=False, improved=False, framer=None, min_chunk=0, error_corr="None", *,
-                 msg_filter=None):
+                 msg_filter=None, soft_fec=None):
         """framer (extension, default None = an independent block, like the reference's): the framer block of the same
         flowgraph whose output feeds this block.  That framer's device pass has already sliced the bits of every burst
         that ends inside its chunk; a paired demod publishes those PDUs straight from the framer's records -- the same
@@ -431,13 +431,30 @@ class demod(gr.sync_block):
         formats (DF 0/4/5/16/20/21/24) a verdict: the context keeps the decoder's aircraft table on the device
         (FLAG_AIRCRAFT_TABLE: every PDU this block publishes announces its address as the decoder would), and such a PDU is
         kept iff its AA was announced before -- or, with error_corr="Conservative", the decoder's repair accepts it.  Not
-        with framer= (there the framer's pass runs before this block's chunk decides what is published)."""
+        with framer= (there the framer's pass runs before this block's chunk decides what is published).
+
+        soft_fec (extension; default None = no repair beyond error_corr, today's bytes): True, or a dict of rule fields
+        (n_weak, max_flips, min_key: _native.Context.set_soft_fec), turns on the soft-decision CRC repair (FLAG_FEC_SOFT,
+        include/adsb_hip.h SOFT REPAIR): a DF 11/17/18/19 PDU that failed parity and that error_corr did not repair is
+        repaired from the confidence of its own bits -- the subset of its weakest bits that explains the syndrome -- and
+        published repaired, counted in `self.soft_corrected` (`self.corrected` keeps counting Conservative repairs only).
+        This is the usable form of what the reference left unbuilt as error_corr "Brute Force", which stays what it is.
+        With parity_filter=True a soft-repaired PDU passes like a Conservative one.  Not with framer=."""
         if error_corr not in _ERROR_CORR:
             raise ValueError("error_corr must be one of %s, not %r" % (", ".join(_ERROR_CORR), error_corr))
         if msg_filter is not None and msg_filter not in _MSG_FILTER:
             raise ValueError("msg_filter must be None or one of %s, not %r" % (", ".join(_MSG_FILTER), msg_filter))
         if framer is not None and msg_filter == "All Messages":
             raise ValueError('msg_filter="All Messages" needs the demod\'s own device pass: not with framer=')
+        if soft_fec is not None and soft_fec is not True and not isinstance(soft_fec, dict):
+            raise ValueError("soft_fec must be None, True or a dict of rule fields, not %r" % (soft_fec,))
+        if isinstance(soft_fec, dict) and set(soft_fec) - set(_native.SOFT_FEC_DEFAULTS):
+            raise ValueError("soft_fec: unknown rule fields %s" % sorted(set(soft_fec) - set(_native.SOFT_FEC_DEFAULTS)))
+        if framer is not None and soft_fec is not None:
+            raise ValueError("soft_fec needs the demod's own device pass: not with framer=")
+        self._soft = soft_fec is not None
+        self.soft_fec = None if soft_fec is None else dict(_native.SOFT_FEC_DEFAULTS, **(soft_fec if isinstance(soft_fec, dict) else {}))
+        self.soft_corrected = 0
         self.msg_filter = msg_filter
         self._air = bool(parity_filter) and msg_filter == "All Messages"
         self.error_corr = error_corr
@@ -475,7 +492,10 @@ class demod(gr.sync_block):
         self._pmt_port, self._pmt_key = pmt.to_pmt("demodulated"), pmt.to_pmt("burst")
         self.message_port_register_out(self._pmt_port)
         self._ctx = _native.Context(fs, 0.0, device=device, flags=(_native.FLAG_FEC_CONSERVATIVE if self._fec else 0) |
-                                                                   (_native.FLAG_AIRCRAFT_TABLE if self._air else 0))
+                                                                   (_native.FLAG_AIRCRAFT_TABLE if self._air else 0) |
+                                                                   (_native.FLAG_FEC_SOFT if self._soft else 0))
+        if self._soft and self.soft_fec != _native.SOFT_FEC_DEFAULTS:
+            self._ctx.set_soft_fec(**self.soft_fec)
 
     def work(self, input_items, output_items):
         in0 = input_items[0]
@@ -519,13 +539,18 @@ class demod(gr.sync_block):
                 # demod.py:79 indexes with nitems_written(0); equal to nitems_read(0) for this sync block
                 bits, ok, ratio = self._ctx.demod_work(in0, self.nitems_written(0), offs, want_ratio=self.want_confidence)
                 pf = _native.demod_flags(self._ctx.last_demod_flags)
+                if self._soft:
+                    soft = self._ctx.last_soft()["nflip"] != 0
                 self.device_calls += 1
             # one PDU per burst is the only per-burst work the API forces (demod.py:104-110)
             ts0, fs, port, pub = self.start_timestamp, self.fs, self._pmt_port, self.message_port_pub
             to_pmt, to_python, cons = pmt.to_pmt, pmt.to_python, pmt.cons
             if ratio is None and not self.parity_filter and bool(ok.all()):
                 if self._fec:
-                    self.corrected += int(np.count_nonzero(np.asarray(pf) & _native.BURST_FEC_FIXED))
+                    fixed = (np.asarray(pf) & _native.BURST_FEC_FIXED) != 0
+                    self.corrected += int(np.count_nonzero(fixed & ~soft if self._soft else fixed))
+                if self._soft:
+                    self.soft_corrected += int(np.count_nonzero(soft))
                 for i, tag in enumerate(tags):
                     pub(port, cons(to_pmt({"timestamp": ts0 + tag.offset / fs, "snr": to_python(tag.value)[1]}), to_pmt(bits[i])))
                 self.bits = bits[-1]                  # demod.py:95 keeps the last burst's bits on the block
@@ -540,7 +565,9 @@ class demod(gr.sync_block):
                     if self.parity_filter and not _prefilter_pass(int(pf[i]), int(bits[i][:5] @ _DF_WEIGHTS), self._fec, self.msg_filter):
                         self.filtered += 1
                         continue
-                    if self._fec and int(pf[i]) & _native.BURST_FEC_FIXED:
+                    if self._soft and soft[i]:
+                        self.soft_corrected += 1
+                    elif self._fec and int(pf[i]) & _native.BURST_FEC_FIXED:
                         self.corrected += 1
                     self.bits = bits[i]
                     if ratio is not None:
@@ -563,6 +590,8 @@ class demod(gr.sync_block):
             offs = np.array([o for o, _ in pend], dtype=np.int64)
             bits, ok, ratio = self._ctx.demod_work(buf, pos, offs, want_ratio=self.want_confidence)
             pf = _native.demod_flags(self._ctx.last_demod_flags)
+            if self._soft:
+                soft = self._ctx.last_soft()["nflip"] != 0
             for i, (off, value) in enumerate(pend):
                 if not ok[i]:
                     self._pending.append((off, value))    # completed by a later call
@@ -570,7 +599,9 @@ class demod(gr.sync_block):
                 if self.parity_filter and not _prefilter_pass(int(pf[i]), int(bits[i][:5] @ _DF_WEIGHTS), self._fec, self.msg_filter):
                     self.filtered += 1
                     continue
-                if self._fec and int(pf[i]) & _native.BURST_FEC_FIXED:
+                if self._soft and soft[i]:
+                    self.soft_corrected += 1
+                elif self._fec and int(pf[i]) & _native.BURST_FEC_FIXED:
                     self.corrected += 1
                 self.bits = bits[i].copy()
                 if ratio is not None:

@@ -17,11 +17,14 @@ MLAT_SOURCE = "adsb_mlat.hip"
 MLAT_RULE_SOURCE = "adsb_mlat_rule.hip"
 # the MLAT track store's kernels (adsb_stream_mlat_track, the readout and expiry): a sixth unit, for the same reason
 MLAT_TRACK_SOURCE = "adsb_mlat_track.hip"
-DEPS = ["adsb_hip.hip", "adsb_env_hip.h", "adsb_device.h", "adsb_plan.h", "adsb_seam.h", os.path.join("..", "..", "include", "adsb_hip.h"),
+# ADSB_FLAG_FEC_SOFT's kernels (the soft-decision CRC repair) and the rule's host form: a seventh unit, for the same reason
+SOFTFEC_SOURCE = "adsb_softfec.hip"
+DEPS = ["adsb_hip.hip", "adsb_env_hip.h", "adsb_device.h", "adsb_reply_device.h", "adsb_plan.h", "adsb_seam.h", os.path.join("..", "..", "include", "adsb_hip.h"),
         "adsb_shared.hip", "adsb_shared.h", "adsb_shared_device.h", "adsb_dedup.hip", "adsb_dedup.h", "adsb_dedup_device.h",
         "adsb_mlat.hip", "adsb_mlat.h", "adsb_mlat_device.h",
         "adsb_mlat_rule.hip", "adsb_mlat_rule.h", "adsb_mlat_rule_device.h",
-        "adsb_mlat_track.hip", "adsb_mlat_track.h", "adsb_mlat_track_device.h"]
+        "adsb_mlat_track.hip", "adsb_mlat_track.h", "adsb_mlat_track_device.h",
+        "adsb_softfec.hip", "adsb_softfec.h", "adsb_softfec_device.h"]
 # -ffp-contract=off: |IQ|^2 must be two rounded products and one rounded add
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread"]
 
@@ -46,6 +49,7 @@ RES_DEDUP = os.path.join(HERE, "kernel_resources_dedup.json")
 RES_MLAT = os.path.join(HERE, "kernel_resources_mlat.json")
 RES_MLAT_RULE = os.path.join(HERE, "kernel_resources_mlat_rule.json")
 RES_MLAT_TRACK = os.path.join(HERE, "kernel_resources_mlat_track.json")
+RES_SOFTFEC = os.path.join(HERE, "kernel_resources_softfec.json")
 
 
 def _parse_resources(remarks):
@@ -69,14 +73,15 @@ def _parse_resources(remarks):
 def compile_and_link(out, extra_flags=(), verbose=False):
     """The translation units, each compiled with FLAGS + extra_flags side by side, linked into the shared library `out`
     (libadsb_hip.so, or a side copy: tools/kbench.py) -> [the compiler's output per unit: SOURCES, SHARED_SOURCE, DEDUP_SOURCE, MLAT_SOURCE,
-    MLAT_RULE_SOURCE, MLAT_TRACK_SOURCE].  The objects live
+    MLAT_RULE_SOURCE, MLAT_TRACK_SOURCE, SOFTFEC_SOURCE].  The objects live
     in a temporary directory."""
     import shutil
     import tempfile
     compile_flags = [f for f in FLAGS if f != "-shared"] + list(extra_flags)
     tmp = tempfile.mkdtemp(prefix="adsb_build_")
     try:
-        units = [(os.path.join(CSRC, s), os.path.join(tmp, s + ".o")) for s in SOURCES + [SHARED_SOURCE, DEDUP_SOURCE, MLAT_SOURCE, MLAT_RULE_SOURCE, MLAT_TRACK_SOURCE]]
+        units = [(os.path.join(CSRC, s), os.path.join(tmp, s + ".o")) for s in SOURCES + [SHARED_SOURCE, DEDUP_SOURCE, MLAT_SOURCE, MLAT_RULE_SOURCE, MLAT_TRACK_SOURCE,
+                                                                                                  SOFTFEC_SOURCE]]
         jobs = []
         for src, obj in units:
             cmd = [hipcc()] + compile_flags + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", obj]
@@ -104,14 +109,14 @@ def build(force=False, verbose=False):
     """hipcc -> libadsb_hip.so, and beside it kernel_resources.json: the compiler's per-kernel register / LDS / scratch
     report (tests/test_abi.py holds the limits the pipeline relies on: k_detect must leave the tail kernels room), and
     kernel_resources_shared.json / kernel_resources_dedup.json / kernel_resources_mlat.json / kernel_resources_mlat_rule.json /
-    kernel_resources_mlat_track.json: the same for adsb_shared.hip's, adsb_dedup.hip's, adsb_mlat.hip's, adsb_mlat_rule.hip's and
-    adsb_mlat_track.hip's kernels."""
-    if not force and up_to_date() and all(os.path.exists(p) for p in (RES, RES_SHARED, RES_DEDUP, RES_MLAT, RES_MLAT_RULE, RES_MLAT_TRACK)):
+    kernel_resources_mlat_track.json / kernel_resources_softfec.json: the same for adsb_shared.hip's, adsb_dedup.hip's, adsb_mlat.hip's,
+    adsb_mlat_rule.hip's, adsb_mlat_track.hip's and adsb_softfec.hip's kernels."""
+    if not force and up_to_date() and all(os.path.exists(p) for p in (RES, RES_SHARED, RES_DEDUP, RES_MLAT, RES_MLAT_RULE, RES_MLAT_TRACK, RES_SOFTFEC)):
         return LIB
     import json
     remarks = compile_and_link(LIB, verbose=verbose)
     assert len(SOURCES) == 1
-    for path, text in zip((RES, RES_SHARED, RES_DEDUP, RES_MLAT, RES_MLAT_RULE, RES_MLAT_TRACK), remarks):
+    for path, text in zip((RES, RES_SHARED, RES_DEDUP, RES_MLAT, RES_MLAT_RULE, RES_MLAT_TRACK, RES_SOFTFEC), remarks):
         with open(path, "w") as f:
             json.dump(_parse_resources(text), f, indent=1, sort_keys=True)
     return LIB

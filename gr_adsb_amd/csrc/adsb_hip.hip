@@ -40,6 +40,7 @@
 #include "adsb_device.h"
 #include "adsb_plan.h"
 #include "adsb_seam.h"
+#include "adsb_softfec.h"
 #include "../../include/adsb_hip.h"
 
 using namespace adsb;
@@ -101,6 +102,8 @@ struct Slot {
   PinnedPtr<Summary> h_sum;
   PinnedBuf h_out;               // burst records of the finished call
   PinnedBuf h_ratio;             // confidence ratios of the finished call
+  DevBuf d_soft;                 // ADSB_FLAG_FEC_SOFT: one adsb_soft_fix per list slot (adsb_softfec.hip writes one per delivered record)
+  PinnedBuf h_soft;              // ... and the rows of the finished call's records
   Event done, ev0, ev1, det_done, h2d_done;
   Stream stream;                 // this slot's own in-order queue: a SUBMITTED pass runs on it from k_detect to k_compact (see enqueue)
   hipStream_t ds = nullptr;      // the stream this pass's k_detect was queued on ...
@@ -377,6 +380,11 @@ struct adsb_ctx {
   int rec_cap_shift = 0;  // rec_cap multiplier (grows on overflow)
   PinnedBuf h_stage;         // staging for pageable inputs of the blocking entry points
   PinnedBuf h_dm;            // scratch of adsb_demod_work: tag positions in, bits / ok / ratio out
+  // ADSB_FLAG_FEC_SOFT: the rule (adsb_set_soft_fec), and where adsb_last_soft finds the rows of the last adsb_demod_work
+  // (in h_dm) when that was the context's last call
+  adsb_soft_fec_rule soft_rule{8, 3, 0.0f, 0u};
+  const adsb_soft_fix* soft_dm = nullptr;
+  int32_t soft_dm_n = 0;
   static constexpr int kRing = 4;
   PinnedPtr<void> h_ring[kRing];   // chunks for pageable host-fed submissions
   Event ring_done[kRing];
@@ -636,6 +644,18 @@ void launch_fec(hipStream_t st, const Slot& s, Rec* out, const Summary* sum) {
                      (Rec*)(s.host_cap > 0 ? s.h_out.p : nullptr), s.host_cap);
 }
 
+// opt-in soft-decision repair (ADSB_FLAG_FEC_SOFT; adsb_softfec.hip) of a pass's records, in place behind launch_fec: one
+// wavefront per record, the grid capped like k_confidence's, the bound sum->n_kept read on the device; one row per list slot
+int launch_soft(adsb_ctx* c, hipStream_t st, const Slot& s, Rec* out, const Summary* sum) {
+  const long long g = std::min<long long>((s.tot + kWaves - 1) / kWaves, (long long)c->n_cu * 8);
+  const DetectArgs& a = s.args;
+  const int e = adsb_softfec_host::launch_records(st, (unsigned)std::max(1ll, g), s.plan.mode, a.data, a.n, a.origin, a.scale, a.sps, &c->soft_rule,
+                                                  out, &sum->n_kept, (int)s.tot, s.host_cap > 0 && out != (Rec*)s.h_out.p ? s.h_out.p : nullptr,
+                                                  s.host_cap, s.d_soft.p);
+  if (e) return fail(c, -EIO, "soft repair launch", (hipError_t)e);
+  return 0;
+}
+
 // The library's key sort (adsb_device.h: k_dec_sort_*): stable, by the bits [lo_bit, hi_bit), four a pass -- a block histogram
 // (hist: 16 words per tile of keys), one scan, a stable scatter, ping-pong between keys and sorted.  Both ranges in use give an
 // odd number of passes (seven: the decode steps' address and "no key" marker; eleven: the store's keys): the result ends in sorted.
@@ -752,10 +772,11 @@ int enqueue_tail(adsb_ctx* c, Slot& s) {
     t.seq = s.seq;
     if (s.fused) launch_pass_small(ts, a, t);
     else ADSB_BY_MODE(pl.mode, launch_tail_small, ts, a, t);
-    if (c->flags & (ADSB_FLAG_FEC_CONSERVATIVE | ADSB_FLAG_AIRCRAFT_TABLE)) {
+    if (c->flags & (ADSB_FLAG_FEC_CONSERVATIVE | ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_FEC_SOFT)) {
       // the repair / the table step follow the published pass number: the host waits for the event behind them instead
       // of polling
       if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) launch_fec(ts, s, (Rec*)s.h_out.p, &misc->sum);
+      if (c->flags & ADSB_FLAG_FEC_SOFT) { int r_ = launch_soft(c, ts, s, (Rec*)s.h_out.p, &misc->sum); if (r_) return r_; }
       if (pl.air) { int r_ = launch_air_pass(c, s, ts, (Rec*)s.h_out.p); if (r_) return r_; }
       HIPCHK(c, hipEventRecord(s.done, ts));
       return 0;
@@ -802,6 +823,7 @@ int enqueue_tail(adsb_ctx* c, Slot& s) {
                      &misc->sum, (const int*)s.d_seg.p, fmask, fwant, pl.head_n, (Rec*)(s.direct ? s.h_out.p : s.d_out.p), (int)s.tot,
                      a.long_count, a.long_lastp, &misc->acc, s.h_sum, (Rec*)(s.host_cap > 0 ? s.h_out.p : nullptr), s.host_cap);
   if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) launch_fec(ts, s, (Rec*)s.d_out.p, &misc->sum);
+  if (c->flags & ADSB_FLAG_FEC_SOFT) { int r_ = launch_soft(c, ts, s, (Rec*)s.d_out.p, &misc->sum); if (r_) return r_; }
   if (pl.air) { int r_ = launch_air_pass(c, s, ts, (Rec*)s.d_out.p); if (r_) return r_; }
   HIPCHK(c, hipEventRecord(s.done, ts));
   return 0;
@@ -895,6 +917,7 @@ int enqueue_pass(adsb_ctx* c, Slot& s, const Plan& pl, bool submitted) {
       s.host_cap = (int)kHostRecs;
     }
   }
+  if ((c->flags & ADSB_FLAG_FEC_SOFT) && (r = ensure(c, s.d_soft, (size_t)s.tot * sizeof(adsb_soft_fix)))) return r;
   if ((r = ensure(c, s.d_seg, (size_t)(s.tot / kThreads + 2) * sizeof(int)))) return r;
   if ((r = ensure(c, s.d_blk_count, (size_t)nlists * sizeof(int)))) return r;
   if ((r = ensure(c, s.d_blk_lastp, (size_t)nlists * sizeof(long long)))) return r;
@@ -1062,7 +1085,7 @@ int finish_pass(adsb_ctx* c, Slot& s, Summary* sum, int32_t* n_res) {
     int r = in_host ? 0 : ensure_pinned(c, s.h_out, (size_t)(nres > 0 ? nres : 1) * sizeof(Rec), true);
     if (r) return r;
     const Rec* recs_dev = (const Rec*)(s.direct ? s.h_out.p : s.d_out.p);
-    if (nres > 0 && (!in_host || (c->flags & ADSB_FLAG_CONFIDENCE))) {
+    if (nres > 0 && (!in_host || (c->flags & (ADSB_FLAG_CONFIDENCE | ADSB_FLAG_FEC_SOFT)))) {
       // on the pass's own stream (idle: its last kernel has completed); never on a caller-owned one
       // (a submitted pass that shares its stream with the passes behind it -- kernels in line, or ADSB_FLAG_SINGLE_STREAM --
       // copies on the context's record-copy stream: on its own one the copy would wait for everything queued since)
@@ -1090,9 +1113,15 @@ int finish_pass(adsb_ctx* c, Slot& s, Summary* sum, int32_t* n_res) {
                      (const Summary*)&((Misc*)s.d_misc.p)->sum, nres, (float*)s.d_ratio.p);
         HIPCHK(c, hipMemcpyAsync(s.h_ratio.p, s.d_ratio.p, rb, hipMemcpyDeviceToHost, xs));
       }
+      if (c->flags & ADSB_FLAG_FEC_SOFT) {
+        // the records' adsb_soft_fix rows travel with them (adsb_last_soft)
+        if ((r = ensure_pinned(c, s.h_soft, (size_t)nres * sizeof(adsb_soft_fix)))) return r;
+        HIPCHK(c, hipMemcpyAsync(s.h_soft.p, s.d_soft.p, (size_t)nres * sizeof(adsb_soft_fix), hipMemcpyDeviceToHost, xs));
+      }
       HIPCHK(c, hipStreamSynchronize(xs));
       HIPCHK(c, hipGetLastError());
     }
+    if (c->flags & ADSB_FLAG_FEC_SOFT) c->soft_dm = nullptr;
     s.nres = nres;
     *n_res = nres;
     return 0;
@@ -1254,6 +1283,7 @@ int check_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_it
     return fail(c, -EINVAL, "adsb_process_batch: bad argument");
   if (c->flags & (ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE | ADSB_FLAG_CONFIDENCE))
     return fail(c, -EINVAL, "adsb_process_batch: not for ADSB_FLAG_AIRCRAFT_TABLE / _DECODE / _CONFIDENCE contexts (one receiver each)");
+  if (c->flags & ADSB_FLAG_FEC_SOFT) return fail(c, -EINVAL, "adsb_process_batch: not for ADSB_FLAG_FEC_SOFT contexts");
   for (int32_t i = 0; i < n_items; ++i) {
     if (items[i].reserved != 0u) return fail(c, -EINVAL, "adsb_process_batch: item.reserved must be 0");
     if (items[i].n < 0) return fail(c, -EINVAL, "adsb_process_batch: item.n < 0");
@@ -1813,6 +1843,7 @@ int check_stream_batch(adsb_ctx* c, int fmt, const adsb_stream_item* items, int3
     return fail(c, -EINVAL, "adsb_process_stream_batch: bad argument");
   if (c->flags & (ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE | ADSB_FLAG_CONFIDENCE))
     return fail(c, -EINVAL, "adsb_process_stream_batch: not for ADSB_FLAG_AIRCRAFT_TABLE / _DECODE / _CONFIDENCE contexts (one receiver each)");
+  if (c->flags & ADSB_FLAG_FEC_SOFT) return fail(c, -EINVAL, "adsb_process_stream_batch: not for ADSB_FLAG_FEC_SOFT contexts");
   StreamBufs& S = c->sb;
   if (S.st.empty()) return fail(c, -EINVAL, "adsb_process_stream_batch: no streams (adsb_streams_open first)");
   const uintptr_t unit = (uintptr_t)mode_bytes(fmt);
@@ -2102,6 +2133,7 @@ int adsb_create(double fs, float threshold, int device, uint32_t flags, adsb_ctx
   if ((flags & ADSB_FLAG_DECODE) && !(flags & ADSB_FLAG_AIRCRAFT_TABLE)) return -EINVAL;   // the decode step follows the table's
   if ((flags & ADSB_FLAG_STREAM_DECODE) && (flags & (ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE | ADSB_FLAG_CONFIDENCE))) return -EINVAL;
   if ((flags & ADSB_FLAG_PLANE_AGES) && !(flags & (ADSB_FLAG_DECODE | ADSB_FLAG_STREAM_DECODE))) return -EINVAL;   // no planes to age
+  if ((flags & ADSB_FLAG_FEC_SOFT) && (flags & (ADSB_FLAG_STREAM_DECODE | ADSB_FLAG_FRAMER_SLICES))) return -EINVAL;   // one receiver's records; no pairing
   if ((flags & ADSB_FLAG_STREAM_DECODE_SHARED) && !(flags & ADSB_FLAG_STREAM_DECODE)) return -EINVAL;           // no decoder to share
   if ((flags & ADSB_FLAG_STREAM_DEDUP) && !(flags & ADSB_FLAG_STREAM_DECODE_SHARED)) return -EINVAL;             // one decoder, or nothing is heard twice
   if (!out) return -EINVAL;
@@ -2356,6 +2388,7 @@ int adsb_streams_open(adsb_ctx* c, int32_t n_streams) {
   if (n_streams < 1) return fail(c, -EINVAL, "adsb_streams_open: n_streams < 1");
   if (c->flags & (ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE | ADSB_FLAG_CONFIDENCE))
     return fail(c, -EINVAL, "adsb_streams_open: not for ADSB_FLAG_AIRCRAFT_TABLE / _DECODE / _CONFIDENCE contexts (one receiver each)");
+  if (c->flags & ADSB_FLAG_FEC_SOFT) return fail(c, -EINVAL, "adsb_streams_open: not for ADSB_FLAG_FEC_SOFT contexts");
   int rc = require_idle(c, kCallPending);
   if (rc) return rc;
   if (!c->sb.st.empty()) return fail(c, -EINVAL, "adsb_streams_open: streams are open (adsb_streams_close first)");
@@ -2926,6 +2959,29 @@ int adsb_last_confidence(adsb_ctx* c, const float** ratio, int32_t* n) {
   return 0;
 }
 
+int adsb_set_soft_fec(adsb_ctx* c, const adsb_soft_fec_rule* rule) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_FEC_SOFT)) return fail(c, -EINVAL, "context created without ADSB_FLAG_FEC_SOFT");
+  if (!rule) return fail(c, -EINVAL, "rule");
+  if (rule->n_weak < 1 || rule->n_weak > 16) return fail(c, -EINVAL, "soft rule: 1 <= n_weak <= 16");
+  if (rule->max_flips < 1 || rule->max_flips > 5) return fail(c, -EINVAL, "soft rule: 1 <= max_flips <= 5");
+  if (!(rule->min_key >= 0.0f && rule->min_key <= 1.0f)) return fail(c, -EINVAL, "soft rule: 0 <= min_key <= 1");
+  if (rule->flags != 0u) return fail(c, -EINVAL, "soft rule: flags must be 0");
+  { int r = require_idle(c, kCallPending); if (r) return r; }
+  c->soft_rule = *rule;
+  return 0;
+}
+
+int adsb_last_soft(adsb_ctx* c, const adsb_soft_fix** rows, int32_t* n) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_FEC_SOFT)) return fail(c, -EINVAL, "context created without ADSB_FLAG_FEC_SOFT");
+  const Slot& s = c->slot[c->last_slot];
+  if (c->soft_dm) { if (rows) *rows = c->soft_dm; if (n) *n = c->soft_dm_n; return 0; }
+  if (rows) *rows = s.nres > 0 ? (const adsb_soft_fix*)s.h_soft.p : nullptr;
+  if (n) *n = s.nres;
+  return 0;
+}
+
 int adsb_set_decoder(adsb_ctx* c, int32_t msg_filter, double start_timestamp) {
   if (!c) return -EINVAL;
   if (!(c->flags & ADSB_FLAG_DECODE)) return fail(c, -EINVAL, "context created without ADSB_FLAG_DECODE");
@@ -3328,8 +3384,10 @@ int adsb_demod_work(adsb_ctx* c, const float* in0, int64_t n, int64_t nitems_rea
   // in flight.
   const size_t nt = (size_t)ntags;
   const size_t o_bits = nt * 8, o_ok = o_bits + nt * 14, o_ratio = (o_ok + nt + 15) & ~(size_t)15;
-  const size_t total = o_ratio + (ratio ? nt * 112 * sizeof(float) : 0);
+  const size_t o_soft = (o_ratio + (ratio ? nt * 112 * sizeof(float) : 0) + 15) & ~(size_t)15;      // ADSB_FLAG_FEC_SOFT: the tags' rows
+  const size_t total = (c->flags & ADSB_FLAG_FEC_SOFT) ? o_soft + nt * sizeof(adsb_soft_fix) : o_ratio + (ratio ? nt * 112 * sizeof(float) : 0);
   if ((rc = ensure_pinned(c, c->h_dm, total))) return rc;
+  c->soft_dm = nullptr;
   char* h = (char*)c->h_dm.p;
   long long* loc = (long long*)h;
   // local positions of the tags inside in0 (demod.py:79: offset - nitems_written); a tag outside the chunk -- the
@@ -3343,6 +3401,11 @@ int adsb_demod_work(adsb_ctx* c, const float* in0, int64_t n, int64_t nitems_rea
   if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE)
     hipLaunchKernelGGL(k_fec_slices, dim3(step_grid(ntags, kThreads)), dim3(kThreads), 0, c->stream, (unsigned char*)(h + o_bits),
                        (unsigned char*)(h + o_ok), (int)ntags);
+  if (c->flags & ADSB_FLAG_FEC_SOFT) {
+    const int e = adsb_softfec_host::launch_slices(c->stream, step_grid(ntags, kWaves), d, (long long)n, (const long long*)loc, c->sps, &c->soft_rule,
+                                                   (unsigned char*)(h + o_bits), (unsigned char*)(h + o_ok), (int)ntags, h + o_soft);
+    if (e) { (void)hipStreamSynchronize(c->stream); return fail(c, -EIO, "soft repair launch", (hipError_t)e); }
+  }
   if (c->flags & ADSB_FLAG_AIRCRAFT_TABLE) {
     // the slices with ok != 0 are this call's published PDUs, in tag order
     AirArgs aa{};
@@ -3357,6 +3420,7 @@ int adsb_demod_work(adsb_ctx* c, const float* in0, int64_t n, int64_t nitems_rea
   for (size_t t = 0; t < nt; ++t)
     for (int k = 0; k < 112; ++k) bits112[t * 112 + k] = (packed[t * 14 + (k >> 3)] >> (7 - (k & 7))) & 1u;
   memcpy(ok, h + o_ok, nt);
+  if (c->flags & ADSB_FLAG_FEC_SOFT) { c->soft_dm = (const adsb_soft_fix*)(h + o_soft); c->soft_dm_n = (int32_t)ntags; }
   if (ratio) {
     memcpy(ratio, h + o_ratio, nt * 112 * sizeof(float));
     for (size_t t = 0; t < nt; ++t)                            // the kernel leaves the rows of dropped tags untouched
@@ -3389,6 +3453,7 @@ static int shard_post(adsb_ctx* c, Slot& s, const Summary& sum, int32_t* nres_io
       r[w] = r[i];
       // row t of adsb_last_confidence belongs to record t of the delivered list: rows move with their records
       if ((c->flags & ADSB_FLAG_CONFIDENCE) && s.h_ratio.p) memcpy((float*)s.h_ratio.p + (size_t)w * 112, (float*)s.h_ratio.p + (size_t)i * 112, 112 * sizeof(float));
+      if ((c->flags & ADSB_FLAG_FEC_SOFT) && s.h_soft.p) ((adsb_soft_fix*)s.h_soft.p)[w] = ((adsb_soft_fix*)s.h_soft.p)[i];
     }
     ++w;
   }
@@ -3406,8 +3471,8 @@ static int shard_refused(adsb_ctx* c, const void* d_data, adsb_ctx* err_to = nul
   return 0;
 }
 static int confidence_refused(adsb_ctx* c, const char* entry, adsb_ctx* err_to) {
-  if (!(c->flags & ADSB_FLAG_CONFIDENCE)) return 0;
-  snprintf(err_to->err, sizeof(err_to->err), "%s: not for ADSB_FLAG_CONFIDENCE contexts", entry);
+  if (!(c->flags & (ADSB_FLAG_CONFIDENCE | ADSB_FLAG_FEC_SOFT))) return 0;
+  snprintf(err_to->err, sizeof(err_to->err), "%s: not for %s contexts", entry, (c->flags & ADSB_FLAG_CONFIDENCE) ? "ADSB_FLAG_CONFIDENCE" : "ADSB_FLAG_FEC_SOFT");
   return -EINVAL;
 }
 

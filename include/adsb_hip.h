@@ -15,6 +15,7 @@
  *   adsb_submit_*_device / adsb_wait   the same, up to ADSB_MAX_IN_FLIGHT calls in flight (no reference counterpart: pipelining)
  *   adsb_submit_format_host         the same fed from host memory: the SDR source -> framer chain of examples/adsb_rx.py:113-126,180-196
  *   adsb_last_confidence            demod.bit_confidence           python/adsb/demod.py:97-101
+ *   adsb_set_soft_fec / adsb_last_soft   (no reference counterpart: decoder.py:772-776 "Brute Force" is unbuilt; SOFT REPAIR below)
  *   adsb_device_alloc / _free / _upload   (no reference counterpart: device memory for C / ctypes clients of the *_device entries)
  *   adsb_shard_device / adsb_shard_fixup / adsb_stitch   (no reference counterpart: overlapped time shards, host stitch)
  *   adsb_process_sharded_multi      the single process of examples/adsb_rx.py:242-268 (one flowgraph, one IQ source) fed to
@@ -147,6 +148,16 @@ extern "C" {
  * -EINVAL otherwise): a reply heard by several receivers is published once -- see DE-DUPLICATION below.  Without the flag
  * nothing is allocated or launched and no byte of any call changes. */
 #define ADSB_FLAG_STREAM_DEDUP 8192u
+/* Opt-in: soft-decision CRC repair of weak-bit errors -- see SOFT REPAIR below.  A DF 11/17/18/19 reply that failed parity and
+ * that the Conservative table does not explain is repaired from the confidence of its own bits: the subset of its n_weak
+ * weakest bits whose syndromes add up to the reply's.  No reference counterpart: error_corr "Brute Force" only logs "to be
+ * implemented" (decoder.py:772-776), and the reference's decoder never sees the samples.  One small kernel per pass behind the
+ * Conservative repair's, before the table and decode steps, which then see a repaired reply as one that passed parity.
+ * Combines with ADSB_FLAG_FEC_CONSERVATIVE, _LONG_AWARE_GATE, _AIRCRAFT_TABLE, _DECODE, _PLANE_AGES, _CONFIDENCE (the ratios stay
+ * those of the raw slice) and _TIMING; adsb_create returns -EINVAL with ADSB_FLAG_STREAM_DECODE or ADSB_FLAG_FRAMER_SLICES, and
+ * the batch, stream-batch and sharded entry points refuse such a context as they refuse ADSB_FLAG_CONFIDENCE contexts.  Without
+ * the flag nothing is allocated or launched and no byte of any call changes. */
+#define ADSB_FLAG_FEC_SOFT 16384u
 
 /* adsb_burst.flags */
 #define ADSB_BURST_DEMOD 1u /* eob inside the demod input: bits[] valid, a PDU is published (demod.py:82) */
@@ -974,6 +985,55 @@ uint32_t adsb_mode_s_syndrome(const uint8_t bits[14], int32_t* df, int32_t* nbit
  * payload when FEC_FIXED, else a copy of in (in and out may be the same array).  *first_bit / *nflip = the table's pattern
  * (bits first_bit .. first_bit+nflip-1) on a hit, FEC_DF included; -1 / 0 without one.  Out pointers may be NULL. */
 uint32_t adsb_mode_s_fec(const uint8_t in[14], uint8_t out[14], int32_t* first_bit, int32_t* nflip);
+
+/* ---- SOFT REPAIR (ADSB_FLAG_FEC_SOFT) ----------------------------------------------------------------------------------
+ * WHICH RECORDS.  A record with ADSB_BURST_DEMOD and DF 11/17/18/19, without ADSB_BURST_PARITY_OK and without
+ * ADSB_BURST_FEC_DF: its syndrome S = crc(bits[0:L-24]) ^ bits[L-24:L] is non-zero; L = 56 for DF 11, else 112.  The soft
+ * repair runs AFTER the Conservative repair where the context has both, so ADSB_FLAG_FEC_CONSERVATIVE repairs exactly the
+ * records it repairs alone.
+ * WEAKNESS OF BIT i.  x1, x0 = the two samples adsb_last_confidence's ratio is made of, in the input's own format, converted
+ * as everywhere.  hi = x1 > x0 ? x1 : x0, lo = x1 > x0 ? x0 : x1 (the slicer's own comparison).  key = lo / hi, ONE IEEE
+ * float32 division (NumPy's float32 division gives the same bits), if hi > 0 && lo >= 0 && hi < +inf; otherwise 1.0f when
+ * !(hi > 0) and 0.0f in the remaining cases.  A larger key is a weaker bit.
+ * CANDIDATES.  Bits 5 .. L-1 with key >= min_key (bits 0-4 never: a soft repair changes neither the DF nor the length),
+ * sorted by key descending, ties to the lower bit index; the first n_weak are kept, rank 0 the weakest.
+ * SEARCH.  The non-empty subsets of the kept candidates with at most max_flips members; a subset matches when the XOR of
+ * its members' syndromes (bit i: x^(L-1-i) mod G) equals S.  Among the matches the fewest flips win, among those the
+ * smallest mask (mask bit k = rank k).  Integers only: no float sums, no dependence on any order of evaluation.
+ * ON A MATCH.  The bits are flipped, the pre-filter bits recomputed as the Conservative repair does, ADSB_BURST_FEC_FIXED
+ * set.  All 16 bits of adsb_burst.flags are taken: what tells a soft repair from a Conservative one is the record's
+ * adsb_soft_fix row (adsb_last_soft): nflip != 0.  A record the rule does not apply to has an all-zero row; one it applies
+ * to has ncand = the candidates kept and bit[] = the flipped bits ascending, padded with 0xFF.
+ * FALSE REPAIRS (derived, not measured).  A reply of random bits has a uniformly random 24-bit syndrome, and T = sum over
+ * k = 1..max_flips of C(n_weak, k) subsets are tried: it is "repaired" with probability about T / 2^24 -- T = 92: 5.5e-6 at
+ * the defaults (8, 3); T = 6884: 4.1e-4 at the caps (16, 5).  The Mode S CRC has codewords of weight 6, so two different
+ * 3-bit subsets can match the same syndrome: the tie rule above then decides.
+ * OUT OF SCOPE.  The address/parity formats (DF 0/4/5/16/20/21/24): their syndrome is the address, and the verdict needs the
+ * aircraft table. */
+typedef struct adsb_soft_fix { /* 8 bytes */
+  uint8_t nflip;  /* 0: not repaired by this rule */
+  uint8_t ncand;  /* candidates kept (<= n_weak); 0 in the row of a record the rule does not apply to */
+  uint8_t bit[5]; /* the flipped bits, ascending, padded with 0xFF */
+  uint8_t pad;
+} adsb_soft_fix;
+typedef struct adsb_soft_fec_rule { /* 16 bytes */
+  int32_t n_weak;    /* 1 .. 16, default 8 */
+  int32_t max_flips; /* 1 .. 5, default 3 */
+  float min_key;     /* 0 .. 1, default 0 */
+  uint32_t flags;    /* 0 */
+} adsb_soft_fec_rule;
+/* ADSB_FLAG_FEC_SOFT contexts.  -EINVAL for a value outside the ranges above, a NaN min_key or flags != 0; -EBUSY while
+ * tickets are pending.  The rule holds for every call queued afterwards. */
+int adsb_set_soft_fec(adsb_ctx* ctx, const adsb_soft_fec_rule* rule);
+/* *rows -> n adsb_soft_fix in the context's pinned memory: row t belongs to record t of the last finished call (blocking
+ * call or adsb_wait), or to tag t of the last adsb_demod_work.  Valid until the next call on the context. */
+int adsb_last_soft(adsb_ctx* ctx, const adsb_soft_fix** rows, int32_t* n);
+/* The rule for one 14-byte payload of a demodulated burst as plain host arithmetic, beside adsb_mode_s_fec: key[i] = the
+ * weakness of bit i (a NaN key is no candidate), rule = NULL: the defaults (n_weak and max_flips beyond their caps count as
+ * the caps).  Returns the pre-filter bits of out, plus ADSB_BURST_FEC_FIXED on a match; out = the repaired payload then, else a
+ * copy of in.  *fix = the row.  out and fix may be NULL. */
+uint32_t adsb_mode_s_soft_fec(const uint8_t in[14], const float key[112], const adsb_soft_fec_rule* rule, uint8_t out[14],
+                              adsb_soft_fix* fix);
 
 /* The per-PDU rule of ADSB_FLAG_AIRCRAFT_TABLE for one 14-byte payload of a demodulated burst, as plain host arithmetic
  * (fec != 0: the context also has ADSB_FLAG_FEC_CONSERVATIVE).  *aa = the AA of an AP-format reply, else -1.  *announce = the

@@ -24,7 +24,7 @@ def phases_of(device_h):
         raise KeyError(pat)
 
     marks = [
-        ("mag2f(float re", "convert"), ("struct BurstFetch", "long pulses / global gathers"),
+        ("constexpr int det_waves(", "convert"), ("struct BurstFetch", "long pulses / global gathers"),
         ("float noise_median(", "record: median"), ("void rec_store_head(", "record: stores / stage"),
         ("void burst_reduce(", "long pulses / global gathers"), ("void burst_from_window(", "record: window, peak, control"),
         ("constexpr int kStage = 16;", "record: stores / stage"), ("void pend_step(", "record: pending bursts"),
