@@ -29,6 +29,7 @@ FLAG_STREAM_DECODE = 1024    # opt-in: one decoder behind every receiver stream 
 FLAG_STREAM_DECODE_SHARED = 4096   # opt-in, with FLAG_STREAM_DECODE: ONE decoder behind all streams, fed every call's records in time order
 FLAG_STREAM_DEDUP = 8192     # opt-in, with FLAG_STREAM_DECODE | FLAG_STREAM_DECODE_SHARED: a reply heard by several receivers is published once
 FLAG_FEC_SOFT = 16384        # opt-in: soft-decision CRC repair of weak-bit errors from the samples behind the bits (include/adsb_hip.h SOFT REPAIR)
+FLAG_FEC_SOFT_BATCH = 32768  # opt-in: the same repair in process_batch* / process_stream_batch*, each record against its own item's samples (SOFT REPAIR, IN A BATCH)
 FLAG_PLANE_AGES = 2048       # opt-in, with FLAG_DECODE or FLAG_STREAM_DECODE: plane_dict's last_seen on the device (planes(seen=True), expire_*)
 # include/adsb_hip.h adsb_decoded: one row per delivered record of a FLAG_DECODE context
 DECODED_DTYPE = np.dtype([("port", "u1"), ("df", "u1"), ("present", "u1"), ("pad0", "u1"), ("icao", "<i4"), ("bits", "u1", (14,)),
@@ -146,7 +147,7 @@ EXPORTS = [
     "adsb_submit_iq_device", "adsb_submit_mag2_device", "adsb_submit_iq16_device", "adsb_submit_shard_device", "adsb_wait",
     "adsb_set_iq16_scale", "adsb_process_iq16", "adsb_process_iq16_device",
     "adsb_set_format_scale", "adsb_process_format", "adsb_process_format_device", "adsb_submit_format_device",
-    "adsb_submit_format_host", "adsb_last_confidence", "adsb_set_soft_fec", "adsb_last_soft", "adsb_mode_s_soft_fec", "adsb_set_decoder", "adsb_last_decoded", "adsb_decode_pdus",
+    "adsb_submit_format_host", "adsb_last_confidence", "adsb_set_soft_fec", "adsb_last_soft", "adsb_batch_last_soft", "adsb_mode_s_soft_fec", "adsb_set_decoder", "adsb_last_decoded", "adsb_decode_pdus",
     "adsb_framer_work", "adsb_framer_work_passthrough", "adsb_demod_work", "adsb_shard_bounds", "adsb_process_sharded_device", "adsb_shard_device", "adsb_shard_host", "adsb_shard_fixup", "adsb_stitch", "adsb_snr_db", "adsb_mode_s_syndrome", "adsb_mode_s_fec", "adsb_mode_s_aircraft", "adsb_plan_chunks", "adsb_get_stats",
     "adsb_process_sharded_multi", "adsb_device_alloc", "adsb_device_free", "adsb_device_upload", "adsb_clear_pending_events",
     "adsb_process_batch_device", "adsb_process_batch",
@@ -315,6 +316,7 @@ def load():
     lib.adsb_mode_s_soft_fec.restype = c.c_uint32
     lib.adsb_set_soft_fec.argtypes = [vp, c.POINTER(SOFT_FEC_RULE)]
     lib.adsb_last_soft.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
+    lib.adsb_batch_last_soft.argtypes = [vp, c.POINTER(vp), c.POINTER(i32)]
     lib.adsb_mode_s_aircraft.argtypes = [vp, i32, c.POINTER(i32), c.POINTER(i32), c.POINTER(i32)]
     lib.adsb_mode_s_aircraft.restype = c.c_uint32
     lib.adsb_plan_chunks.argtypes = [i64, i64, c.POINTER(i64), c.POINTER(i64)]
@@ -428,7 +430,7 @@ class Context:
         return v.copy() if copy else v
 
     def set_soft_fec(self, n_weak=8, max_flips=3, min_key=0.0):
-        """FLAG_FEC_SOFT contexts: the soft repair's rule (adsb_set_soft_fec): the n_weak weakest bits are candidates, at most
+        """FLAG_FEC_SOFT and FLAG_FEC_SOFT_BATCH contexts: the soft repair's rule (adsb_set_soft_fec): the n_weak weakest bits are candidates, at most
         max_flips of them are flipped, a candidate's weakness is at least min_key."""
         rule = SOFT_FEC_RULE(int(n_weak), int(max_flips), float(min_key), 0)
         self._chk(self.lib.adsb_set_soft_fec(self._h, ctypes.byref(rule)))
@@ -444,6 +446,17 @@ class Context:
         buf = (ctypes.c_char * (n.value * SOFT_DTYPE.itemsize)).from_address(p.value)
         v = np.frombuffer(buf, dtype=SOFT_DTYPE)
         return v.copy() if copy else v
+
+    def last_batch_soft(self):
+        """FLAG_FEC_SOFT_BATCH contexts: SOFT_DTYPE rows of the last process_batch* / process_stream_batch* call, row t for its
+        record t (adsb_batch_last_soft); a copy."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int32(0)
+        self._chk(self.lib.adsb_batch_last_soft(self._h, ctypes.byref(p), ctypes.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=SOFT_DTYPE)
+        buf = (ctypes.c_char * (n.value * SOFT_DTYPE.itemsize)).from_address(p.value)
+        return np.frombuffer(buf, dtype=SOFT_DTYPE).copy()
 
     def set_decoder(self, msg_filter="All Messages", start_timestamp=0.0):
         """FLAG_DECODE contexts: the decoder's msg_filter and the start timestamp of the records' PDUs (adsb_set_decoder)."""

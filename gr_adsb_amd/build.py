@@ -19,12 +19,15 @@ MLAT_RULE_SOURCE = "adsb_mlat_rule.hip"
 MLAT_TRACK_SOURCE = "adsb_mlat_track.hip"
 # ADSB_FLAG_FEC_SOFT's kernels (the soft-decision CRC repair) and the rule's host form: a seventh unit, for the same reason
 SOFTFEC_SOURCE = "adsb_softfec.hip"
+# ADSB_FLAG_FEC_SOFT_BATCH's kernel (the same repair on a batch pass's packed list): an eighth unit, for the same reason
+SOFTFEC_BATCH_SOURCE = "adsb_softfec_batch.hip"
 DEPS = ["adsb_hip.hip", "adsb_env_hip.h", "adsb_device.h", "adsb_reply_device.h", "adsb_plan.h", "adsb_seam.h", os.path.join("..", "..", "include", "adsb_hip.h"),
         "adsb_shared.hip", "adsb_shared.h", "adsb_shared_device.h", "adsb_dedup.hip", "adsb_dedup.h", "adsb_dedup_device.h",
         "adsb_mlat.hip", "adsb_mlat.h", "adsb_mlat_device.h",
         "adsb_mlat_rule.hip", "adsb_mlat_rule.h", "adsb_mlat_rule_device.h",
         "adsb_mlat_track.hip", "adsb_mlat_track.h", "adsb_mlat_track_device.h",
-        "adsb_softfec.hip", "adsb_softfec.h", "adsb_softfec_device.h"]
+        "adsb_softfec.hip", "adsb_softfec.h", "adsb_softfec_device.h",
+        "adsb_softfec_batch.hip", "adsb_softfec_batch.h", "adsb_softfec_batch_device.h"]
 # -ffp-contract=off: |IQ|^2 must be two rounded products and one rounded add
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread"]
 
@@ -50,6 +53,8 @@ RES_MLAT = os.path.join(HERE, "kernel_resources_mlat.json")
 RES_MLAT_RULE = os.path.join(HERE, "kernel_resources_mlat_rule.json")
 RES_MLAT_TRACK = os.path.join(HERE, "kernel_resources_mlat_track.json")
 RES_SOFTFEC = os.path.join(HERE, "kernel_resources_softfec.json")
+RES_SOFTFEC_BATCH = os.path.join(HERE, "kernel_resources_softfec_batch.json")
+ALL_RES = (RES, RES_SHARED, RES_DEDUP, RES_MLAT, RES_MLAT_RULE, RES_MLAT_TRACK, RES_SOFTFEC, RES_SOFTFEC_BATCH)
 
 
 def _parse_resources(remarks):
@@ -73,7 +78,7 @@ def _parse_resources(remarks):
 def compile_and_link(out, extra_flags=(), verbose=False):
     """The translation units, each compiled with FLAGS + extra_flags side by side, linked into the shared library `out`
     (libadsb_hip.so, or a side copy: tools/kbench.py) -> [the compiler's output per unit: SOURCES, SHARED_SOURCE, DEDUP_SOURCE, MLAT_SOURCE,
-    MLAT_RULE_SOURCE, MLAT_TRACK_SOURCE, SOFTFEC_SOURCE].  The objects live
+    MLAT_RULE_SOURCE, MLAT_TRACK_SOURCE, SOFTFEC_SOURCE, SOFTFEC_BATCH_SOURCE].  The objects live
     in a temporary directory."""
     import shutil
     import tempfile
@@ -81,7 +86,7 @@ def compile_and_link(out, extra_flags=(), verbose=False):
     tmp = tempfile.mkdtemp(prefix="adsb_build_")
     try:
         units = [(os.path.join(CSRC, s), os.path.join(tmp, s + ".o")) for s in SOURCES + [SHARED_SOURCE, DEDUP_SOURCE, MLAT_SOURCE, MLAT_RULE_SOURCE, MLAT_TRACK_SOURCE,
-                                                                                                  SOFTFEC_SOURCE]]
+                                                                                                  SOFTFEC_SOURCE, SOFTFEC_BATCH_SOURCE]]
         jobs = []
         for src, obj in units:
             cmd = [hipcc()] + compile_flags + ["-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", obj]
@@ -109,14 +114,14 @@ def build(force=False, verbose=False):
     """hipcc -> libadsb_hip.so, and beside it kernel_resources.json: the compiler's per-kernel register / LDS / scratch
     report (tests/test_abi.py holds the limits the pipeline relies on: k_detect must leave the tail kernels room), and
     kernel_resources_shared.json / kernel_resources_dedup.json / kernel_resources_mlat.json / kernel_resources_mlat_rule.json /
-    kernel_resources_mlat_track.json / kernel_resources_softfec.json: the same for adsb_shared.hip's, adsb_dedup.hip's, adsb_mlat.hip's,
-    adsb_mlat_rule.hip's, adsb_mlat_track.hip's and adsb_softfec.hip's kernels."""
-    if not force and up_to_date() and all(os.path.exists(p) for p in (RES, RES_SHARED, RES_DEDUP, RES_MLAT, RES_MLAT_RULE, RES_MLAT_TRACK, RES_SOFTFEC)):
+    kernel_resources_mlat_track.json / kernel_resources_softfec.json / kernel_resources_softfec_batch.json: the same for adsb_shared.hip's,
+    adsb_dedup.hip's, adsb_mlat.hip's, adsb_mlat_rule.hip's, adsb_mlat_track.hip's, adsb_softfec.hip's and adsb_softfec_batch.hip's kernels."""
+    if not force and up_to_date() and all(os.path.exists(p) for p in ALL_RES):
         return LIB
     import json
     remarks = compile_and_link(LIB, verbose=verbose)
     assert len(SOURCES) == 1
-    for path, text in zip((RES, RES_SHARED, RES_DEDUP, RES_MLAT, RES_MLAT_RULE, RES_MLAT_TRACK, RES_SOFTFEC), remarks):
+    for path, text in zip(ALL_RES, remarks):
         with open(path, "w") as f:
             json.dump(_parse_resources(text), f, indent=1, sort_keys=True)
     return LIB

@@ -41,6 +41,7 @@
 #include "adsb_plan.h"
 #include "adsb_seam.h"
 #include "adsb_softfec.h"
+#include "adsb_softfec_batch.h"
 #include "../../include/adsb_hip.h"
 
 using namespace adsb;
@@ -139,6 +140,10 @@ struct BatchBufs {
   PinnedBuf h_tab;               // the tables as the host builds them
   PinnedBuf h_first;             // device-visible: first[n_items + 1], then kept[n_items]
   PinnedBuf h_out;               // device-visible: the dense list (its head straight from k_batch_pack)
+  // ADSB_FLAG_FEC_SOFT_BATCH (adsb_softfec_batch.hip): the items' samples as a table of its own (the units share no type), one
+  // adsb_soft_fix per slot of the dense list, and the rows of the finished pass's records
+  DevBuf d_soft_items, d_soft_rows;
+  PinnedBuf h_soft_rows;
 };
 
 // adsb_process_stream_batch*: the receiver streams of a context (adsb_streams_open).  Host state per stream, its last
@@ -385,6 +390,11 @@ struct adsb_ctx {
   adsb_soft_fec_rule soft_rule{8, 3, 0.0f, 0u};
   const adsb_soft_fix* soft_dm = nullptr;
   int32_t soft_dm_n = 0;
+  // ADSB_FLAG_FEC_SOFT_BATCH: the per-call switch of the ordinary pass -- set only while batch_core runs an item through
+  // enqueue / finish, so every other entry point of such a context does what it does without the flag -- and the rows of the
+  // last delivered batch call in the order of its out[] (adsb_batch_last_soft)
+  bool soft_fallback = false;
+  std::vector<adsb_soft_fix> batch_soft;
   static constexpr int kRing = 4;
   PinnedPtr<void> h_ring[kRing];   // chunks for pageable host-fed submissions
   Event ring_done[kRing];
@@ -644,6 +654,10 @@ void launch_fec(hipStream_t st, const Slot& s, Rec* out, const Summary* sum) {
                      (Rec*)(s.host_cap > 0 ? s.h_out.p : nullptr), s.host_cap);
 }
 
+// whether the ordinary pass repairs: every pass of an ADSB_FLAG_FEC_SOFT context, and the fallback items of a batch call of an
+// ADSB_FLAG_FEC_SOFT_BATCH one (batch_core)
+inline bool soft_pass(const adsb_ctx* c) { return (c->flags & ADSB_FLAG_FEC_SOFT) != 0 || c->soft_fallback; }
+
 // opt-in soft-decision repair (ADSB_FLAG_FEC_SOFT; adsb_softfec.hip) of a pass's records, in place behind launch_fec: one
 // wavefront per record, the grid capped like k_confidence's, the bound sum->n_kept read on the device; one row per list slot
 int launch_soft(adsb_ctx* c, hipStream_t st, const Slot& s, Rec* out, const Summary* sum) {
@@ -772,11 +786,11 @@ int enqueue_tail(adsb_ctx* c, Slot& s) {
     t.seq = s.seq;
     if (s.fused) launch_pass_small(ts, a, t);
     else ADSB_BY_MODE(pl.mode, launch_tail_small, ts, a, t);
-    if (c->flags & (ADSB_FLAG_FEC_CONSERVATIVE | ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_FEC_SOFT)) {
+    if ((c->flags & (ADSB_FLAG_FEC_CONSERVATIVE | ADSB_FLAG_AIRCRAFT_TABLE)) || soft_pass(c)) {
       // the repair / the table step follow the published pass number: the host waits for the event behind them instead
       // of polling
       if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) launch_fec(ts, s, (Rec*)s.h_out.p, &misc->sum);
-      if (c->flags & ADSB_FLAG_FEC_SOFT) { int r_ = launch_soft(c, ts, s, (Rec*)s.h_out.p, &misc->sum); if (r_) return r_; }
+      if (soft_pass(c)) { int r_ = launch_soft(c, ts, s, (Rec*)s.h_out.p, &misc->sum); if (r_) return r_; }
       if (pl.air) { int r_ = launch_air_pass(c, s, ts, (Rec*)s.h_out.p); if (r_) return r_; }
       HIPCHK(c, hipEventRecord(s.done, ts));
       return 0;
@@ -823,7 +837,7 @@ int enqueue_tail(adsb_ctx* c, Slot& s) {
                      &misc->sum, (const int*)s.d_seg.p, fmask, fwant, pl.head_n, (Rec*)(s.direct ? s.h_out.p : s.d_out.p), (int)s.tot,
                      a.long_count, a.long_lastp, &misc->acc, s.h_sum, (Rec*)(s.host_cap > 0 ? s.h_out.p : nullptr), s.host_cap);
   if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) launch_fec(ts, s, (Rec*)s.d_out.p, &misc->sum);
-  if (c->flags & ADSB_FLAG_FEC_SOFT) { int r_ = launch_soft(c, ts, s, (Rec*)s.d_out.p, &misc->sum); if (r_) return r_; }
+  if (soft_pass(c)) { int r_ = launch_soft(c, ts, s, (Rec*)s.d_out.p, &misc->sum); if (r_) return r_; }
   if (pl.air) { int r_ = launch_air_pass(c, s, ts, (Rec*)s.d_out.p); if (r_) return r_; }
   HIPCHK(c, hipEventRecord(s.done, ts));
   return 0;
@@ -917,7 +931,7 @@ int enqueue_pass(adsb_ctx* c, Slot& s, const Plan& pl, bool submitted) {
       s.host_cap = (int)kHostRecs;
     }
   }
-  if ((c->flags & ADSB_FLAG_FEC_SOFT) && (r = ensure(c, s.d_soft, (size_t)s.tot * sizeof(adsb_soft_fix)))) return r;
+  if (soft_pass(c) && (r = ensure(c, s.d_soft, (size_t)s.tot * sizeof(adsb_soft_fix)))) return r;
   if ((r = ensure(c, s.d_seg, (size_t)(s.tot / kThreads + 2) * sizeof(int)))) return r;
   if ((r = ensure(c, s.d_blk_count, (size_t)nlists * sizeof(int)))) return r;
   if ((r = ensure(c, s.d_blk_lastp, (size_t)nlists * sizeof(long long)))) return r;
@@ -1085,7 +1099,7 @@ int finish_pass(adsb_ctx* c, Slot& s, Summary* sum, int32_t* n_res) {
     int r = in_host ? 0 : ensure_pinned(c, s.h_out, (size_t)(nres > 0 ? nres : 1) * sizeof(Rec), true);
     if (r) return r;
     const Rec* recs_dev = (const Rec*)(s.direct ? s.h_out.p : s.d_out.p);
-    if (nres > 0 && (!in_host || (c->flags & (ADSB_FLAG_CONFIDENCE | ADSB_FLAG_FEC_SOFT)))) {
+    if (nres > 0 && (!in_host || (c->flags & ADSB_FLAG_CONFIDENCE) || soft_pass(c))) {
       // on the pass's own stream (idle: its last kernel has completed); never on a caller-owned one
       // (a submitted pass that shares its stream with the passes behind it -- kernels in line, or ADSB_FLAG_SINGLE_STREAM --
       // copies on the context's record-copy stream: on its own one the copy would wait for everything queued since)
@@ -1113,7 +1127,7 @@ int finish_pass(adsb_ctx* c, Slot& s, Summary* sum, int32_t* n_res) {
                      (const Summary*)&((Misc*)s.d_misc.p)->sum, nres, (float*)s.d_ratio.p);
         HIPCHK(c, hipMemcpyAsync(s.h_ratio.p, s.d_ratio.p, rb, hipMemcpyDeviceToHost, xs));
       }
-      if (c->flags & ADSB_FLAG_FEC_SOFT) {
+      if (soft_pass(c)) {
         // the records' adsb_soft_fix rows travel with them (adsb_last_soft)
         if ((r = ensure_pinned(c, s.h_soft, (size_t)nres * sizeof(adsb_soft_fix)))) return r;
         HIPCHK(c, hipMemcpyAsync(s.h_soft.p, s.d_soft.p, (size_t)nres * sizeof(adsb_soft_fix), hipMemcpyDeviceToHost, xs));
@@ -1319,6 +1333,9 @@ struct BatchResult {
   std::vector<std::vector<adsb_burst>> fb;
   std::vector<unsigned> fb_flags;
   std::vector<int32_t> fb_of;
+  // ADSB_FLAG_FEC_SOFT_BATCH: rows[t] belongs to packed[t], fb_rows[k][t] to fb[k][t]
+  const adsb_soft_fix* rows = nullptr;
+  std::vector<std::vector<adsb_soft_fix>> fb_rows;
 };
 
 // The device pass of a batch: the tables, k_batch, k_batch_pack, k_fec, and the ordinary pass for what is left.
@@ -1344,7 +1361,15 @@ int batch_core(adsb_ctx* c, int fmt, const std::vector<BatchWork>& work, const S
   // the dense list and item_first are 32-bit: a batch whose lists have 2^31 slots or more is refused
   if (packed_cap >= (1ll << 31)) return fail(c, -EINVAL, "adsb_process_batch: batch too large for one call (list slots >= 2^31)");
   const long long kHostRecs = 32768;
-  const size_t tab_bytes = (size_t)n_items * (sizeof(DetectArgs) + sizeof(TailArgs));
+  // ADSB_FLAG_FEC_SOFT_BATCH: the soft repair's own item table behind the two argument tables
+  const bool soft = (c->flags & ADSB_FLAG_FEC_SOFT_BATCH) != 0;
+  typedef adsb_softfec_batch_host::Item SoftItem;
+  static_assert((sizeof(DetectArgs) + sizeof(TailArgs)) % alignof(SoftItem) == 0, "the soft repair's table is aligned behind the others");
+  const size_t soft_tab = (size_t)n_items * (sizeof(DetectArgs) + sizeof(TailArgs));
+  const size_t tab_bytes = soft_tab + (soft ? (size_t)n_items * sizeof(SoftItem) : 0);
+  if (soft && ((r = ensure(c, B.d_soft_items, (size_t)n_items * sizeof(SoftItem))) ||
+               (r = ensure(c, B.d_soft_rows, (size_t)(packed_cap + 1) * sizeof(adsb_soft_fix)))))
+    return r;
   if ((r = ensure(c, B.d_scratch, total + 128))) return r;
   if ((r = ensure(c, B.d_fixed, (size_t)n_items * sizeof(BatchFixed)))) return r;
   if ((r = ensure(c, B.d_da, (size_t)n_items * sizeof(DetectArgs)))) return r;
@@ -1369,8 +1394,11 @@ int batch_core(adsb_ctx* c, int fmt, const std::vector<BatchWork>& work, const S
     const BatchWork& w = work[(size_t)i];
     if (L.slots == 0) { hda[i].n = w.kind == BatchWork::kEmpty ? 0 : -1; continue; }     // empty, or the host's own (too long)
     fill_batch_item(hda[i], hta[i], w.plan, L, sc, fx[i], w.thr, c->scale[fmt], c->sps, long_aware, kWaves);
+    // the samples as the item's k_batch workgroup reads them; the other items' ranges in the dense list are empty
+    if (soft) ((SoftItem*)((char*)B.h_tab.p + soft_tab))[i] = SoftItem{w.plan.d_data, w.plan.n, w.plan.origin, 0};
   }
   if ((r = apply_ext(c, st))) return r;
+  if (soft) HIPCHK(c, hipMemcpyAsync(B.d_soft_items.p, (char*)B.h_tab.p + soft_tab, (size_t)n_items * sizeof(SoftItem), hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(B.d_da.p, hda, (size_t)n_items * sizeof(DetectArgs), hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(B.d_ta.p, hta, (size_t)n_items * sizeof(TailArgs), hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemsetAsync(B.d_fixed.p, 0, (size_t)n_items * sizeof(BatchFixed), st));
@@ -1384,6 +1412,13 @@ int batch_core(adsb_ctx* c, int fmt, const std::vector<BatchWork>& work, const S
   if (c->flags & ADSB_FLAG_FEC_CONSERVATIVE) {
     hipLaunchKernelGGL(k_fec, dim3(step_grid(packed_cap, kThreads)), dim3(kThreads), 0, st, (Rec*)B.d_packed.p,
                        (const Summary*)B.d_tot.p, (int)packed_cap, (Rec*)B.h_out.p, (int)host_cap);
+  }
+  if (soft) {
+    // behind k_fec, on the packed list: item i's records against item i's samples (a stream item's: its staging buffer, which
+    // k_stream_save below only reads), first[] as k_batch_pack has just written it
+    const int e = adsb_softfec_batch_host::launch_items(st, (int)n_items, fmt, B.d_soft_items.p, h_first, c->scale[fmt], c->sps, &c->soft_rule,
+                                                        B.d_packed.p, (int)packed_cap, B.h_out.p, (int)host_cap, B.d_soft_rows.p);
+    if (e) { (void)hipStreamSynchronize(st); return fail(c, -EIO, "soft repair launch", (hipError_t)e); }
   }
   if (hooks) {
     hipLaunchKernelGGL(k_stream_save, dim3(n_items), dim3(kThreads), 0, st, hooks->save, (const TailArgs*)B.d_ta.p,
@@ -1400,6 +1435,12 @@ int batch_core(adsb_ctx* c, int fmt, const std::vector<BatchWork>& work, const S
     HIPCHK(c, hipMemcpyAsync(B.h_out.p, B.d_packed.p, (size_t)nb * sizeof(Rec), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
   }
+  if (soft && nb > 0) {
+    if ((r = ensure_pinned(c, B.h_soft_rows, (size_t)nb * sizeof(adsb_soft_fix)))) return r;
+    HIPCHK(c, hipMemcpyAsync(B.h_soft_rows.p, B.d_soft_rows.p, (size_t)nb * sizeof(adsb_soft_fix), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+  }
+  R->rows = (const adsb_soft_fix*)B.h_soft_rows.p;
   R->packed = (const adsb_burst*)B.h_out.p;
   R->first = h_first;
   R->kept = h_kept;
@@ -1414,6 +1455,9 @@ int batch_core(adsb_ctx* c, int fmt, const std::vector<BatchWork>& work, const S
   // previous call's records, their count and any view the caller holds into that slot's pinned buffer stay as they are; the
   // context's threshold and its list-capacity multiplier are put back afterwards (an item's density says nothing about the
   // caller's other streams).  stats.calls / stats.retries do count these passes.
+  // ADSB_FLAG_FEC_SOFT_BATCH: the pass repairs as an ADSB_FLAG_FEC_SOFT context's does (soft_pass), for these passes only, and
+  // the slot's rows come back with its records.
+  R->fb_rows.assign((size_t)nfb, std::vector<adsb_soft_fix>());
   R->fb.assign((size_t)nfb, std::vector<adsb_burst>());
   R->fb_flags.assign((size_t)nfb, 0u);
   R->fb_of.assign((size_t)n_items, -1);
@@ -1429,11 +1473,14 @@ int batch_core(adsb_ctx* c, int fmt, const std::vector<BatchWork>& work, const S
     Summary s;
     int32_t nres = 0;
     c->thr = work[(size_t)i].thr;
+    c->soft_fallback = soft;
     rc = enqueue(c, fs, pl, false);
     if (rc == 0) rc = finish(c, fs, &s, &nres);
+    c->soft_fallback = false;
     if (rc == 0 && nres > 0) {
       const adsb_burst* src = (const adsb_burst*)fs.h_out.p;
       R->fb[(size_t)k].assign(src, src + nres);
+      if (soft) R->fb_rows[(size_t)k].assign((const adsb_soft_fix*)fs.h_soft.p, (const adsb_soft_fix*)fs.h_soft.p + nres);
     }
     if (rc == 0) R->fb_flags[(size_t)k] = s.flags;
     R->fb_of[(size_t)i] = k++;
@@ -1449,7 +1496,7 @@ int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_item
   *n_out = 0;
   item_first[0] = 0;
   if (n_fallback) *n_fallback = 0;
-  if (n_items == 0) return 0;
+  if (n_items == 0) { c->batch_soft.clear(); return 0; }
   HIPCHK(c, hipSetDevice(c->device));
   int r;
   if ((r = batch_slots_ok(c, items, n_items))) return r;
@@ -1471,15 +1518,21 @@ int run_batch(adsb_ctx* c, int fmt, const adsb_batch_item* items, int32_t n_item
   item_first[n_items] = (int32_t)tot;
   *n_out = (int32_t)tot;
   if (tot > cap) return fail(c, -ENOSPC, "output array too small");
+  const bool soft = (c->flags & ADSB_FLAG_FEC_SOFT_BATCH) != 0;
   if (R.nfb == 0) {
     if (tot > 0) memcpy(out, R.packed, (size_t)tot * sizeof(adsb_burst));
+    if (soft) c->batch_soft.assign(R.rows, R.rows + (tot > 0 ? tot : 0));
     return 0;
   }
+  if (soft) c->batch_soft.assign((size_t)tot, adsb_soft_fix{});
   for (int32_t i = 0; i < n_items; ++i) {
     const int32_t cnt = item_first[i + 1] - item_first[i];
     if (cnt == 0) continue;
-    const adsb_burst* src = R.kept[i] < 0 ? R.fb[(size_t)R.fb_of[(size_t)i]].data() : R.packed + R.first[i];
+    const bool fb = R.kept[i] < 0;
+    const adsb_burst* src = fb ? R.fb[(size_t)R.fb_of[(size_t)i]].data() : R.packed + R.first[i];
     memcpy(out + item_first[i], src, (size_t)cnt * sizeof(adsb_burst));
+    // the item's rows are spliced in with its records
+    if (soft) memcpy(c->batch_soft.data() + item_first[i], fb ? R.fb_rows[(size_t)R.fb_of[(size_t)i]].data() : R.rows + R.first[i], (size_t)cnt * sizeof(adsb_soft_fix));
   }
   return 0;
 }
@@ -1868,7 +1921,7 @@ int run_stream_batch(adsb_ctx* c, int fmt, const adsb_stream_item* items, int32_
   *n_out = 0;
   item_first[0] = 0;
   if (n_fallback) *n_fallback = 0;
-  if (n_items == 0) { c->fd.n_rows = 0; return 0; }
+  if (n_items == 0) { c->fd.n_rows = 0; c->batch_soft.clear(); return 0; }
   HIPCHK(c, hipSetDevice(c->device));
   StreamBufs& S = c->sb;
   const hipStream_t st = c->stream;
@@ -1919,6 +1972,8 @@ int run_stream_batch(adsb_ctx* c, int fmt, const adsb_stream_item* items, int32_
   size_t room = (size_t)R.nb + 1;
   for (const std::vector<adsb_burst>& f : R.fb) room += f.size();
   std::vector<adsb_burst> keep(room);
+  const bool soft = (c->flags & ADSB_FLAG_FEC_SOFT_BATCH) != 0;
+  std::vector<adsb_soft_fix> keep_rows(soft ? room : 0);
   std::vector<StreamState> next((size_t)n_items);
   long long tot = 0;
   for (int32_t i = 0; i < n_items; ++i) {
@@ -1932,6 +1987,16 @@ int run_stream_batch(adsb_ctx* c, int fmt, const adsb_stream_item* items, int32_
     const int w = stream_deliver(src, cnt, keep.data() + tot, plan[(size_t)i].plan, sum_flags, sps,
                                  [](const adsb_burst& b) { return (long long)b.offset; },
                                  [](const adsb_burst& b) { return (unsigned)b.flags; }, &n.eob, &n.overlong);
+    if (soft) {
+      // Rows are dropped with their records, so row t stays with delivered record t: what stream_deliver kept is a subsequence
+      // of src in order, found again by comparing whole records.  A repair changes neither offset, DF nor length (bits 0-4 are
+      // never candidates), so the drops, the carried gate state (eob) and ADSB_BURST_LONG_HINT are what they are without the flag.
+      const adsb_soft_fix* rows = fb ? R.fb_rows[(size_t)R.fb_of[(size_t)i]].data() : R.rows + R.first[i];
+      int t = 0;
+      for (int j = 0; j < cnt && t < w; ++j)
+        if (memcmp(&src[j], &keep[(size_t)(tot + t)], sizeof(adsb_burst)) == 0) keep_rows[(size_t)(tot + t++)] = rows[j];
+      if (t != w) return fail(c, -EIO, "adsb_process_stream_batch: the delivered records are not a subsequence of the pass's");
+    }
     item_first[i] = (int32_t)tot;
     tot += w;
     if (tot >= (1ll << 31)) return fail(c, -EINVAL, "adsb_process_stream_batch: more than 2^31 records");
@@ -1950,6 +2015,7 @@ int run_stream_batch(adsb_ctx* c, int fmt, const adsb_stream_item* items, int32_
     fin = (const adsb_burst*)c->fd.h_recs.p;
   }
   if (tot > 0) memcpy(out, fin, (size_t)tot * sizeof(adsb_burst));
+  if (soft) c->batch_soft.assign(keep_rows.begin(), keep_rows.begin() + tot);
   for (int32_t i = 0; i < n_items; ++i) S.st[(size_t)items[i].stream] = next[(size_t)i];
   return 0;
 }
@@ -2134,6 +2200,9 @@ int adsb_create(double fs, float threshold, int device, uint32_t flags, adsb_ctx
   if ((flags & ADSB_FLAG_STREAM_DECODE) && (flags & (ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE | ADSB_FLAG_CONFIDENCE))) return -EINVAL;
   if ((flags & ADSB_FLAG_PLANE_AGES) && !(flags & (ADSB_FLAG_DECODE | ADSB_FLAG_STREAM_DECODE))) return -EINVAL;   // no planes to age
   if ((flags & ADSB_FLAG_FEC_SOFT) && (flags & (ADSB_FLAG_STREAM_DECODE | ADSB_FLAG_FRAMER_SLICES))) return -EINVAL;   // one receiver's records; no pairing
+  // the batch form: one meaning of "soft" per context, and none of the contexts the batch entry points refuse anyway
+  if ((flags & ADSB_FLAG_FEC_SOFT_BATCH) && (flags & (ADSB_FLAG_FEC_SOFT | ADSB_FLAG_CONFIDENCE | ADSB_FLAG_AIRCRAFT_TABLE | ADSB_FLAG_DECODE |
+                                                      ADSB_FLAG_FRAMER_SLICES))) return -EINVAL;
   if ((flags & ADSB_FLAG_STREAM_DECODE_SHARED) && !(flags & ADSB_FLAG_STREAM_DECODE)) return -EINVAL;           // no decoder to share
   if ((flags & ADSB_FLAG_STREAM_DEDUP) && !(flags & ADSB_FLAG_STREAM_DECODE_SHARED)) return -EINVAL;             // one decoder, or nothing is heard twice
   if (!out) return -EINVAL;
@@ -2961,7 +3030,7 @@ int adsb_last_confidence(adsb_ctx* c, const float** ratio, int32_t* n) {
 
 int adsb_set_soft_fec(adsb_ctx* c, const adsb_soft_fec_rule* rule) {
   if (!c) return -EINVAL;
-  if (!(c->flags & ADSB_FLAG_FEC_SOFT)) return fail(c, -EINVAL, "context created without ADSB_FLAG_FEC_SOFT");
+  if (!(c->flags & (ADSB_FLAG_FEC_SOFT | ADSB_FLAG_FEC_SOFT_BATCH))) return fail(c, -EINVAL, "context created without ADSB_FLAG_FEC_SOFT / _FEC_SOFT_BATCH");
   if (!rule) return fail(c, -EINVAL, "rule");
   if (rule->n_weak < 1 || rule->n_weak > 16) return fail(c, -EINVAL, "soft rule: 1 <= n_weak <= 16");
   if (rule->max_flips < 1 || rule->max_flips > 5) return fail(c, -EINVAL, "soft rule: 1 <= max_flips <= 5");
@@ -2979,6 +3048,14 @@ int adsb_last_soft(adsb_ctx* c, const adsb_soft_fix** rows, int32_t* n) {
   if (c->soft_dm) { if (rows) *rows = c->soft_dm; if (n) *n = c->soft_dm_n; return 0; }
   if (rows) *rows = s.nres > 0 ? (const adsb_soft_fix*)s.h_soft.p : nullptr;
   if (n) *n = s.nres;
+  return 0;
+}
+
+int adsb_batch_last_soft(adsb_ctx* c, const adsb_soft_fix** rows, int32_t* n) {
+  if (!c) return -EINVAL;
+  if (!(c->flags & ADSB_FLAG_FEC_SOFT_BATCH)) return fail(c, -EINVAL, "context created without ADSB_FLAG_FEC_SOFT_BATCH");
+  if (rows) *rows = c->batch_soft.empty() ? nullptr : c->batch_soft.data();
+  if (n) *n = (int32_t)c->batch_soft.size();
   return 0;
 }
 

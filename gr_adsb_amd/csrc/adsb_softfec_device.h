@@ -166,6 +166,7 @@ __global__ void __launch_bounds__(kThreads) k_soft_fec(const void* data, long lo
   }
 }
 
+#ifndef ADSB_SOFTFEC_RULE_ONLY   // (adsb_softfec_batch_device.h takes the rule above and defines no second k_soft_fec_slices)
 // The same for the stand-alone demod's slices: bits14 / ok as k_slice and k_fec_slices leave them (ok's bits 0, 5, 6, 7 = kDemod,
 // kParityOk, kLongFmt, kKnownDf; bits 1 / 2 = kFecFixed / kFecDf >> 13), tag_idx[] local to the float chunk data[n].
 __global__ void __launch_bounds__(kThreads) k_soft_fec_slices(const void* data, long long n, const long long* tag_idx, int sps, Rule R,
@@ -195,5 +196,7 @@ __global__ void __launch_bounds__(kThreads) k_soft_fec_slices(const void* data, 
     if (lane == 0) rows[t] = row;
   }
 }
+
+#endif  // ADSB_SOFTFEC_RULE_ONLY
 
 }  // namespace adsb_softfec

@@ -131,7 +131,9 @@ class FrontEnd:
     # -- many receivers, one GPU: a batch of independent streams in one device pass -------------------
     def process_batch(self, fmt, arrays, thresholds=None, abs_offsets=None):
         """arrays[i]: host array of item i in the format's layout -> (records, item_first); item i's records, those of
-        process_format(fmt, arrays[i]) at thresholds[i], are records[item_first[i]:item_first[i+1]] (Context.process_batch)."""
+        process_format(fmt, arrays[i]) at thresholds[i], are records[item_first[i]:item_first[i+1]] (Context.process_batch).
+        On a FLAG_FEC_SOFT_BATCH context the records are soft-repaired, each against its own item's samples, and
+        ctx.last_batch_soft() holds their SOFT_DTYPE rows, row t for records[t]."""
         return self.ctx.process_batch(fmt, arrays, thresholds, abs_offsets)
 
     def process_batch_tensors(self, fmt, tensors, thresholds=None, abs_offsets=None):
@@ -150,15 +152,17 @@ class FrontEnd:
         return self.ctx.last_batch_fallbacks
 
     # -- many receivers that go on: streams carried across batch calls -----------------------------------
-    def receivers(self, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False, dedup=False, positions=None):
+    def receivers(self, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False, dedup=False, positions=None, soft_fec=False):
         """n receiver streams on this context (Receivers below).  fmt: one of _native.FMT_*, or None: by the arrays' dtype.
         starts / msg_filter: FLAG_STREAM_DECODE contexts, the streams' start timestamps and their decoders' msg_filter.
         ages: the context also has FLAG_PLANE_AGES (ValueError otherwise): .planes(seen=True) and .expire(cutoffs).
         shared: the context also has FLAG_STREAM_DECODE_SHARED (ValueError otherwise): ONE decoder behind all n streams.
         dedup: True, or (window_s, horizon_s): the context also has FLAG_STREAM_DEDUP (ValueError otherwise).
         positions: [(lat_deg, lon_deg, alt_m), ...], the antennas of streams 0, 1, ... on the WGS-84 ellipsoid (None in the
-        list: that stream has none); needs dedup (ValueError otherwise): Receivers.mlat()."""
-        return Receivers(self.ctx, n, fmt, starts, msg_filter, ages, shared, dedup, positions)
+        list: that stream has none); needs dedup (ValueError otherwise): Receivers.mlat().
+        soft_fec: True, or a dict of rule fields (n_weak, max_flips, min_key): the context also has FLAG_FEC_SOFT_BATCH (ValueError
+        otherwise): every push repairs each stream's parity failures from that stream's own samples; Receivers.soft."""
+        return Receivers(self.ctx, n, fmt, starts, msg_filter, ages, shared, dedup, positions, soft_fec)
 
     def shard_tensor(self, t, origin, own_lo, own_hi, stream_len, fmt=0, head_cands=0):
         _after_torch(self.ctx, t)
@@ -205,9 +209,14 @@ class Receivers:
     -2 (the match lies in an earlier push) / the position of the earliest-published match of the last push or finish.
     positions (with dedup): the antennas' (lat_deg, lon_deg, alt_m); mlat() then locates the replies that four or more
     positioned receivers heard, from their arrival times alone (include/adsb_hip.h MULTILATERATION: pass `starts` relative to
-    a session epoch, not Unix times, or the double's spacing costs 71 m)."""
+    a session epoch, not Unix times, or the double's spacing costs 71 m).
+    soft_fec (a context that also has FLAG_FEC_SOFT_BATCH; True, or a dict of rule fields for other than 8 / 3 / 0.0): the
+    soft-decision CRC repair (include/adsb_hip.h SOFT REPAIR, IN A BATCH) runs in every push, each stream's records against its
+    own samples, before the decoders, the de-duplication and mlat() see them; after push() / finish(), .soft holds the list of
+    SOFT_DTYPE row arrays that matches the returned record arrays (nflip != 0: repaired by the soft rule)."""
 
-    def __init__(self, ctx, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False, dedup=False, positions=None):
+    def __init__(self, ctx, n, fmt=None, starts=None, msg_filter=None, ages=False, shared=False, dedup=False, positions=None,
+                 soft_fec=False):
         self.ctx, self.n, self.fmt = ctx, int(n), fmt
         self.decode = bool(getattr(ctx, "flags", 0) & _native.FLAG_STREAM_DECODE)
         self.ages = bool(ages)
@@ -216,6 +225,14 @@ class Receivers:
         self.order = np.zeros(0, dtype=np.int32)
         self.dedup = dedup is not False and dedup is not None
         self.duplicates = np.zeros(0, dtype=np.int32)
+        self.soft = []
+        if soft_fec is not False and soft_fec is not True and not isinstance(soft_fec, dict):
+            raise ValueError("soft_fec: True, or a dict of rule fields")
+        self.soft_fec = None if soft_fec is False else dict(_native.SOFT_FEC_DEFAULTS, **({} if soft_fec is True else soft_fec))
+        if self.soft_fec is not None and set(self.soft_fec) != set(_native.SOFT_FEC_DEFAULTS):
+            raise ValueError("soft_fec: the rule's fields are n_weak, max_flips, min_key")
+        if (self.soft_fec is not None) != bool(getattr(ctx, "flags", 0) & _native.FLAG_FEC_SOFT_BATCH):
+            raise ValueError("soft_fec needs, and its absence excludes, a FLAG_FEC_SOFT_BATCH context")
         if self.dedup != bool(getattr(ctx, "flags", 0) & _native.FLAG_STREAM_DEDUP):
             raise ValueError("dedup needs, and its absence excludes, a FLAG_STREAM_DEDUP context")
         if positions is not None and not self.dedup:
@@ -229,6 +246,8 @@ class Receivers:
         if not self.decode and (starts is not None or msg_filter is not None):      # (before any stream is opened)
             raise ValueError("starts / msg_filter need a FLAG_STREAM_DECODE context")
         ctx.open_streams(self.n)
+        if self.soft_fec is not None and soft_fec is not True:
+            ctx.set_soft_fec(**self.soft_fec)
         if self.decode:
             if msg_filter is not None:
                 ctx.set_streams_decoder(msg_filter)
@@ -247,6 +266,7 @@ class Receivers:
             self.rows = []
             self.order = np.zeros(0, dtype=np.int32)
             self.duplicates = np.zeros(0, dtype=np.int32)
+            self.soft = []
             return []
         arrays = [np.asarray(a) for a in arrays]
         fmt = self._last_fmt = self.fmt if self.fmt is not None else _FMT_OF_DTYPE[arrays[0].dtype]
@@ -254,6 +274,9 @@ class Receivers:
         if self.decode:
             rows = self.ctx.last_stream_decoded()
             self.rows = [rows[first[i]:first[i + 1]] for i in range(len(ids))]
+        if self.soft_fec is not None:
+            soft = self.ctx.last_batch_soft()
+            self.soft = [soft[first[i]:first[i + 1]] for i in range(len(ids))]
         if self.shared:
             self.order = self.ctx.last_stream_order()
         if self.dedup:
@@ -281,6 +304,9 @@ class Receivers:
         if self.decode:
             rows = dict(zip(live, self.rows)) if live else {}
             self.rows = [rows.get(i, np.zeros(0, dtype=_native.DECODED_DTYPE)) for i in ids]
+        if self.soft_fec is not None:
+            soft = dict(zip(live, self.soft)) if live else {}
+            self.soft = [soft.get(i, np.zeros(0, dtype=_native.SOFT_DTYPE)) for i in ids]
         return [out[i] for i in ids]
 
     def planes(self, ids=None, seen=False):

@@ -15,7 +15,7 @@
  *   adsb_submit_*_device / adsb_wait   the same, up to ADSB_MAX_IN_FLIGHT calls in flight (no reference counterpart: pipelining)
  *   adsb_submit_format_host         the same fed from host memory: the SDR source -> framer chain of examples/adsb_rx.py:113-126,180-196
  *   adsb_last_confidence            demod.bit_confidence           python/adsb/demod.py:97-101
- *   adsb_set_soft_fec / adsb_last_soft   (no reference counterpart: decoder.py:772-776 "Brute Force" is unbuilt; SOFT REPAIR below)
+ *   adsb_set_soft_fec / adsb_last_soft / adsb_batch_last_soft   (no reference counterpart: decoder.py:772-776 "Brute Force" is unbuilt; SOFT REPAIR below)
  *   adsb_device_alloc / _free / _upload   (no reference counterpart: device memory for C / ctypes clients of the *_device entries)
  *   adsb_shard_device / adsb_shard_fixup / adsb_stitch   (no reference counterpart: overlapped time shards, host stitch)
  *   adsb_process_sharded_multi      the single process of examples/adsb_rx.py:242-268 (one flowgraph, one IQ source) fed to
@@ -158,6 +158,16 @@ extern "C" {
  * the batch, stream-batch and sharded entry points refuse such a context as they refuse ADSB_FLAG_CONFIDENCE contexts.  Without
  * the flag nothing is allocated or launched and no byte of any call changes. */
 #define ADSB_FLAG_FEC_SOFT 16384u
+/* Opt-in: the same soft-decision repair for MANY receivers -- see SOFT REPAIR, IN A BATCH below.  adsb_process_batch* and
+ * adsb_process_stream_batch* repair the packed record list of the pass against each record's OWN item's samples (one more small
+ * kernel behind the Conservative repair's), so a reply that one distant receiver heard with a few weak wrong bits reaches the
+ * shared decoder, the de-duplication and the multilateration with the payload the other receivers heard.  The rows come back
+ * through adsb_batch_last_soft; the rule is adsb_set_soft_fec's.  Combines with ADSB_FLAG_FEC_CONSERVATIVE, _LONG_AWARE_GATE,
+ * _TIMING and _STREAM_DECODE (with _SHARED, _DEDUP, _PLANE_AGES).  adsb_create returns -EINVAL with ADSB_FLAG_FEC_SOFT (one
+ * meaning per context) and with ADSB_FLAG_CONFIDENCE, _AIRCRAFT_TABLE, _DECODE or _FRAMER_SLICES (the batch entry points refuse
+ * those contexts anyway).  The context's other entry points return exactly what they return without the flag; the sharded
+ * drivers do not repair.  Without the flag nothing is allocated or launched and no byte of any call changes. */
+#define ADSB_FLAG_FEC_SOFT_BATCH 32768u
 
 /* adsb_burst.flags */
 #define ADSB_BURST_DEMOD 1u /* eob inside the demod input: bits[] valid, a PDU is published (demod.py:82) */
@@ -1008,6 +1018,16 @@ uint32_t adsb_mode_s_fec(const uint8_t in[14], uint8_t out[14], int32_t* first_b
  * k = 1..max_flips of C(n_weak, k) subsets are tried: it is "repaired" with probability about T / 2^24 -- T = 92: 5.5e-6 at
  * the defaults (8, 3); T = 6884: 4.1e-4 at the caps (16, 5).  The Mode S CRC has codewords of weight 6, so two different
  * 3-bit subsets can match the same syndrome: the tie rule above then decides.
+ * IN A BATCH (ADSB_FLAG_FEC_SOFT_BATCH).  Item i's records and rows of adsb_process_batch* are those of adsb_process_format on an
+ * ADSB_FLAG_FEC_SOFT context with the same rule and the same Conservative flag, over item i's samples at its threshold: a
+ * record's samples are its own item's, never a neighbour's.  A stream's records and rows over all adsb_process_stream_batch*
+ * calls are those of ONE such call over the concatenated chunks, with the existing stream-batch deviations; a repair changes
+ * neither offset, DF nor length, so what a stream carries from call to call is what it carries without the flag.  Items the
+ * library runs through its ordinary pass (longer than ADSB_BATCH_ITEM_MAX, or with overflowed lists) are repaired there; their
+ * records and rows take the item's place.  In a fleet the derived false-repair odds above hold PER HEARING: a false repair
+ * produces an essentially random payload, which joins another receiver's group (de-duplication, multilateration) only if it
+ * equals that receiver's payload within the window -- another factor of about 2^-88 for a long reply -- so it can feed no
+ * multilateration fix; it can still touch its own address's plane in the decoder, exactly as on one receiver.
  * OUT OF SCOPE.  The address/parity formats (DF 0/4/5/16/20/21/24): their syndrome is the address, and the verdict needs the
  * aircraft table. */
 typedef struct adsb_soft_fix { /* 8 bytes */
@@ -1022,12 +1042,16 @@ typedef struct adsb_soft_fec_rule { /* 16 bytes */
   float min_key;     /* 0 .. 1, default 0 */
   uint32_t flags;    /* 0 */
 } adsb_soft_fec_rule;
-/* ADSB_FLAG_FEC_SOFT contexts.  -EINVAL for a value outside the ranges above, a NaN min_key or flags != 0; -EBUSY while
+/* ADSB_FLAG_FEC_SOFT and ADSB_FLAG_FEC_SOFT_BATCH contexts.  -EINVAL for a value outside the ranges above, a NaN min_key or flags != 0; -EBUSY while
  * tickets are pending.  The rule holds for every call queued afterwards. */
 int adsb_set_soft_fec(adsb_ctx* ctx, const adsb_soft_fec_rule* rule);
 /* *rows -> n adsb_soft_fix in the context's pinned memory: row t belongs to record t of the last finished call (blocking
  * call or adsb_wait), or to tag t of the last adsb_demod_work.  Valid until the next call on the context. */
 int adsb_last_soft(adsb_ctx* ctx, const adsb_soft_fix** rows, int32_t* n);
+/* ADSB_FLAG_FEC_SOFT_BATCH contexts (-EINVAL otherwise).  *rows -> n adsb_soft_fix in the context's memory: row t belongs to
+ * out[t] of the last adsb_process_batch* / adsb_process_stream_batch* call that delivered its records (n = 0 before the first).
+ * Valid until the next call on the context.  adsb_last_soft and adsb_last_result stay what they are. */
+int adsb_batch_last_soft(adsb_ctx* ctx, const adsb_soft_fix** rows, int32_t* n);
 /* The rule for one 14-byte payload of a demodulated burst as plain host arithmetic, beside adsb_mode_s_fec: key[i] = the
  * weakness of bit i (a NaN key is no candidate), rule = NULL: the defaults (n_weak and max_flips beyond their caps count as
  * the caps).  Returns the pre-filter bits of out, plus ADSB_BURST_FEC_FIXED on a match; out = the repaired payload then, else a
